@@ -15,7 +15,17 @@ a tolerance that is never met; the timed region is the whole C-ABI call (it incl
 Multi-GPU: independent images shard across ranks (no data-path collective, weak scaling); RCCL is used only for the
 barrier and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys:
+Prints ONE JSON line (rank 0).  A plain run sets up, runs the converged solve (final PSNR) and the untimed pre-roll, times
+the K steps and prints the contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), final_psnr_db,
+outer_iterations_to_tol_1e-5, pre_roll_steps (every untimed iteration that ran before the timed region: converged solve,
+clock ramp-up, --warmup) and switches (SBTV_* variables set).
+
+  --dump-outputs DIR  after the timed steps, writes what the timed SALSA_v2 call returned (rank 0's image) as float64
+                DIR/<name>.npy: x (the 2048x2048 image after step K, 32 MiB), objective, distance, mses, numA, numAt.
+                The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+  --full        everything else the benchmark measures or checks, each block after the timed steps (--no-cpu-baseline,
+                --no-batched, --no-extras and --no-extra-configs leave single blocks out):
+  loop_ms_per_step_device  device time of the timed loop per step (sbtv_last_timing)
   roofline      the dominant kernel (temporally fused Chambolle iteration).  Five iterations share one pass over
                 memory, so SURVEY.md section 8d's 5 x 40 B/px is not a bound (it exceeds the HBM peak).  Neither limit of
                 the chip is saturated by a launch as a whole: `valu_issue_frac` (fp64 VALU instructions of one launch
@@ -36,8 +46,7 @@ Prints ONE JSON line (rank 0).  Besides the contract keys:
                 SAPG Gaussian 4 shared chains at 2048^2
   psnr_matches_fixture  final PSNR and stopping iteration of the converged solve against the committed oracle fixture
                 (tests/golden/large_configs.npz; |dPSNR| <= 1e-3 dB and the same iteration)
-  pre_roll_steps  every untimed iteration that ran before the timed region (converged solve, clock ramp-up, --warmup)
-  cpu_baseline  the NumPy oracle on the host cores (N = 1 only), final_psnr_db, switches (SBTV_* variables set)
+  cpu_baseline  the NumPy oracle on the host cores (N = 1 only)
   batched       four 2048x2048 images per GPU in one call (two lanes per context): image-iterations/s; N = 1: also the one-stream
                 rate; N > 1: aggregate over the ranks (north_star: scaling on batched images)
 """
@@ -529,6 +538,18 @@ def extra_configs(ctx, dev, iters):
     return out
 
 
+def dump_outputs(path, out):
+    """--dump-outputs: the arrays the timed SALSA_v2 call returned to its caller, one float64 .npy each (x: 32 MiB).
+    `times` is left out: wall-clock readings of the iterations, not a result of the computation."""
+    import numpy as np
+    import sbtv
+    os.makedirs(path, exist_ok=True)
+    x, numA, numAt, objective, distance, _times, mses = out
+    for name, a in (("x", sbtv.to_host(x)), ("objective", objective), ("distance", distance), ("mses", mses),
+                    ("numA", numA), ("numAt", numAt)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def dry_run(args, rank, world):
     """Rendezvous + barrier + max-reduction of a fake time without touching a GPU (tests of the launch path)."""
     import torch
@@ -625,6 +646,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the auxiliary blocks: rooflines, fixture check, 512x512 and batched rates, configs[2..4], "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the timed call returned (rank 0) as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batched", action="store_true", help="skip the auxiliary 4-image batch measurement")
     ap.add_argument("--no-extras", action="store_true", help="skip the 512x512 block and the per-pass timings")
@@ -636,6 +662,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launch path only: rendezvous, barrier, one JSON line")
     ap.add_argument("--group", action="store_true", help="single process: one sbtv.Group over --gpus devices (sbtv_SALSA_v2_sharded_dev)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.group or args.dry_run):
+        ap.error("--dump-outputs needs the timed path of the multi-process mode (not --group / --dry-run)")
     if args.group:
         return group_mode(args)
 
@@ -710,8 +738,10 @@ def main():
     elapsed = time.perf_counter() - t0
     gc.enable()
     assert len(out[3]) - 1 == args.steps
-    tm = ctx.last_timing()
+    tm = ctx.last_timing() if args.full else None
     final_psnr = psnr(x, sbtv.to_host(xg))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
@@ -721,7 +751,7 @@ def main():
     # N > 1: north_star asks for the 512 x 512 throughput at every GPU count as well - every rank times the same 400-step
     # solve of its own 512^2 image between barriers, the slowest rank counts (no per-sample host statistics here)
     multi_512 = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         x5m, y5m, s5m, _ = make_problem(seed=1 + rank, size=512)
         y5md, x5md = sbtv.to_device(y5m, dev), sbtv.to_device(x5m, dev)
         tau5m = THETA * s5m ** 2
@@ -744,7 +774,7 @@ def main():
 
     # ... and north_star's "scaling on batched images": four 2048 x 2048 images per GPU in one call (two lanes per context)
     multi_batched = None
-    if world > 1 and not args.no_batched:
+    if world > 1 and args.full and not args.no_batched:
         nbm, kbm = 4, 100
         ybm, xbm = sbtv.to_device(np.stack([y] * nbm), dev), sbtv.to_device(np.stack([x] * nbm), dev)
         solve(10, -1.0, ybm, xbm)
@@ -762,11 +792,11 @@ def main():
                          "value_is": "median of 3 calls, each the slowest rank between two barriers; two lanes per context"}
         del ybm, xbm
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras
     # auxiliary, outside the timed region: the same solve on a batch of 4 independent images in one call (the
     # natural unit when many images share a GPU); reported as image-iterations/s, never as `value`
     batched = None
-    if rank == 0 and world == 1 and not args.no_batched:
+    if rank == 0 and world == 1 and args.full and not args.no_batched:
         nb, ksteps = 4, max(100, args.steps // 4)
         yb = sbtv.to_device(np.stack([y] * nb), dev)          # column-major image memory per image
         xb = sbtv.to_device(np.stack([x] * nb), dev)
@@ -794,7 +824,6 @@ def main():
     if rank == 0:
         value = world * args.steps / elapsed
         ms_per_step = 1e3 * elapsed / args.steps
-        pmc, pmc_state = load_pmc()
         line = {
             "metric": "SALSA outer-iters/sec + final PSNR, 2048x2048 Gaussian blur",
             "value": value, "unit": "SALSA outer-iterations/s", "n_gpus": world, "steps": args.steps,
@@ -811,29 +840,31 @@ def main():
                        # otherwise the solve repeats exactly): profiles/r03_chambolle_errsubset.md, SBTV_ERR_SUBSET=0 = full sums
                        "prox_stop_rule": "exact (chambolle_prox_TV_stop.m:131), checked after the launches on lower-bound step sums"},
             "final_psnr_db": final_psnr, "outer_iterations_to_tol_1e-5": n_conv,
-            # rank 0 solves the problem of the committed fixture (seed 1): the PSNR half of the metric, checked
-            "psnr_matches_fixture": fixture_check("salsa2048", final_psnr, n_conv),
             # every untimed iteration this rank ran before the timed region
             "pre_roll_steps": {"converged_solve": n_conv, "clock_rampup": RAMPUP, "warmup": args.warmup,
                                "total": n_conv + RAMPUP + args.warmup},
             "world_size_seen": dist.get_world_size() if world > 1 else 1,
             "backend": dist.get_backend() if world > 1 else None,
             "switches": sbtv.switches(),
-            "loop_ms_per_step_device": tm["loop_ms"] / args.steps,
-            "roofline": chambolle_roofline(tm, SIZE, pmc, pmc_state, ctx.prox_variant(SIZE, SIZE)["kind"],
-                                           launch_split(ctx, SIZE) if extras else None),
         }
-        # step level: bytes the whole outer iteration moves / measured step time
-        model_step = model_step_bytes(SIZE)
-        step = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "model_bytes_per_step": model_step,
-                "model": "fused design per outer iteration: 2 Chambolle launches (40 + 48 B/px), forward column FFT of "
-                         "u+bu (24), row pass with H and Y (48), inverse column FFT + bookkeeping (56)",
-                "achieved": model_step / (ms_per_step * 1e-3) / 1e9}
-        step["frac"] = step["achieved"] / HBM_PEAK_GBS
-        if pmc and pmc.get("bytes_per_outer_iteration"):
-            step["traffic"] = pmc["bytes_per_outer_iteration"]
-            step["traffic_frac"] = step["traffic"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
-        line["step_roofline"] = step
+        if args.full:
+            # rank 0 solves the problem of the committed fixture (seed 1): the PSNR half of the metric, checked
+            line["psnr_matches_fixture"] = fixture_check("salsa2048", final_psnr, n_conv)
+            pmc, pmc_state = load_pmc()
+            line["loop_ms_per_step_device"] = tm["loop_ms"] / args.steps
+            line["roofline"] = chambolle_roofline(tm, SIZE, pmc, pmc_state, ctx.prox_variant(SIZE, SIZE)["kind"],
+                                                  launch_split(ctx, SIZE) if extras else None)
+            # step level: bytes the whole outer iteration moves / measured step time
+            model_step = model_step_bytes(SIZE)
+            step = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "model_bytes_per_step": model_step,
+                    "model": "fused design per outer iteration: 2 Chambolle launches (40 + 48 B/px), forward column FFT of "
+                             "u+bu (24), row pass with H and Y (48), inverse column FFT + bookkeeping (56)",
+                    "achieved": model_step / (ms_per_step * 1e-3) / 1e9}
+            step["frac"] = step["achieved"] / HBM_PEAK_GBS
+            if pmc and pmc.get("bytes_per_outer_iteration"):
+                step["traffic"] = pmc["bytes_per_outer_iteration"]
+                step["traffic_frac"] = step["traffic"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
+            line["step_roofline"] = step
         if extras:
             line["passes"] = pass_block(ctx, SIZE, ("cols_fwd", "rows_salsa", "cols_inv_post", "prox10_warm"), 50)
             # BASELINE configs[1] / north_star: the same solve on 512 x 512 man.png
@@ -907,7 +938,7 @@ def main():
                 line["extra_configs"] = extra_configs(ctx, dev, args.extra_iters)
             except Exception as e:           # an auxiliary block must not take the headline line down with it
                 line["extra_configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(x, noise, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if world > 1:

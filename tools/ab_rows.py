@@ -9,7 +9,7 @@ for rnd in range(rounds):
     for v in ("1", "0"):
         lab = os.environ.get("AB_ROWS_LIB", os.path.join(ROOT, "semi-blind-image-deblurring-problems-with-tv_amd", "lib", "libsbtv_lab.so"))
         env = dict(os.environ, SBTV_ROWS_SUB=v, SBTV_LIBRARY=lab)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
         except Exception:

@@ -4,7 +4,7 @@
 # 1. rocprofv3 --kernel-trace --stats      -> profiles/<tag>_kernel_stats.csv
 # 2. three separate --pmc passes (SQ activity / FETCH_SIZE / WRITE_SIZE; never combined with tracing)
 #                                          -> profiles/<tag>_pmc.json, profiles/pmc_current.json
-# 3. plain bench line (reads pmc_current)  -> profiles/<tag>_bench.json
+# 3. full bench line (reads pmc_current)   -> profiles/<tag>_bench.json
 set -eo pipefail
 TAG=${1:?tag}
 R=$PWD
@@ -25,7 +25,7 @@ echo "pmc write done"
 cd "$R"
 python3 tools/summarize_profiles.py "$TAG" "$O/stats" "$O/pmc_sq" "$O/pmc_fetch" "$O/pmc_write"
 # the bench line last: it then finds profiles/pmc_current.json of THIS source revision and carries roofline.traffic
-python3 bench.py --steps 500 --warmup 20 > "$O/bench.json" 2> "$O/bench.err"
+python3 bench.py --steps 500 --warmup 20 --full > "$O/bench.json" 2> "$O/bench.err"
 cp "$O/bench.json" "profiles/${TAG}_bench.json"
 echo "bench done"; tail -c 600 "$O/bench.json"; echo
 mkdir -p gpurun_out/profiles_$TAG
