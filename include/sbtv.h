@@ -327,6 +327,41 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                         double *logpi_wu, double *gx, double *grads, double *eb,
                         double *x_last, sbtv_allreduce_fn reduce_fn, void *reduce_user, int flags);
 
+/* ---- posterior moments of the MYULA samples (no entry point of the reference: the `weldford` accumulator that
+ * SAPG/SAPG_algorithm_Guassian.m:233-235,246,292-293 and run_Gaussian_demo.m:291-295 leave commented out, its class not
+ * shipped) ----------------------------------------------------------------------------------------------------------
+ * sbtv_SAPG_algorithm_moments / sbtv_myula_moments run exactly the chain of sbtv_SAPG_algorithm / sbtv_myula (no bit of
+ * the traces, EB estimates, last sample or Philox counters changes) and also return the per-pixel posterior mean (the
+ * MMSE image) and variance of the samples, accumulated on the device in Welford form while each sample is produced.
+ *   Iterations: iteration 1 is the state the loop starts from - for SAPG the state after the warm-up (the X of ii = 1 of
+ *     SAPG_algorithm_Guassian.m:98), for MYULA y; iteration ii is the sample X after the MYULA step of iteration ii.  SAPG
+ *     runs ii = 2..samples, sbtv_myula ii = 2..samples-1 (SALSA/myula.m:13; its last iteration is max(1, samples-1)).
+ *     Warm-up samples are never used.
+ *   Selection: the iterations first, first + thin, ... up to the last iteration.  first = 0 means op->burnIn for SAPG
+ *     (where the reference creates its accumulator, ii == op.burnIn) and 1 for MYULA.  thin >= 1.  thin < 1, first < 0 or
+ *     first beyond the last iteration -> SBTV_ERR_BADARG before any GPU work.
+ *   Outputs per chain: post_mean, post_var = M2 / (n-1) (the unbiased sample variance; all zeros for n = 1) and
+ *     post_count = n, the number of samples used.  Layout [batch][M*N] (pooled: [1][M*N]), column-major like every image
+ *     here; post_mean / post_var are device pointers with SBTV_DEVICE_PTRS, post_count [batch or 1] is always a host
+ *     array.  post_mean is required, post_var and post_count may be NULL.
+ *   pooled = 1: one moment set over all chains of the call, formed from the per-chain sets with Chan's pairwise
+ *     combination in chain order 0, 1, 2, ... (a lane split does not change the bits).  Only for chains of ONE posterior:
+ *     SAPG with share_gradients = 1, MYULA chains with the same y, taps, theta and sigma2; otherwise SBTV_ERR_BADARG.
+ *   The two accumulators (mean and M2, 16 B per pixel each) cost 32 B of memory traffic per pixel and selected iteration;
+ *   unselected iterations launch the plain kernels. */
+typedef struct sbtv_moments_opts {
+    int first;                /* first iteration used (0: burnIn for SAPG, 1 for MYULA)                */
+    int thin;                 /* every thin-th iteration from `first` (>= 1)                           */
+    int pooled;               /* 1: one set over all chains of the call                                */
+} sbtv_moments_opts;
+int sbtv_SAPG_algorithm_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                                const sbtv_sapg_opts *op, const double *x0, const double *noise,
+                                double *thetas, double *ps, double *sigmas, double *logpi,
+                                double *logpi_wu, double *gx, double *grads, double *eb,
+                                double *x_last, sbtv_allreduce_fn reduce_fn, void *reduce_user,
+                                const sbtv_moments_opts *mo, double *post_mean, double *post_var,
+                                long long *post_count, int flags);
+
 /* Plain MYULA chain at fixed parameters: replaces  xMAP = myula(op, im)  (SALSA/myula.m:1-22) with the closures
  * of SALSA/run_deblur_tv.m:126,131:  proxG(x,lambda,theta) = chambolle_prox_TV_stop(x,'lambda',lambda*theta,
  * 'maxiter',chambolleit),  gradF(x) = AT(A x - y)/sigma2.  x starts at y; samples-2 steps
@@ -337,6 +372,12 @@ int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const do
                double lambda, double gamma, const double *theta, const double *sigma2, int samples,
                int chambolleit, unsigned long long seed, int chain_offset, const double *noise,
                double *x_out, int flags);
+/* sbtv_myula with the posterior moments of its samples (see sbtv_SAPG_algorithm_moments above) */
+int sbtv_myula_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                       double lambda, double gamma, const double *theta, const double *sigma2, int samples,
+                       int chambolleit, unsigned long long seed, int chain_offset, const double *noise,
+                       double *x_out, const sbtv_moments_opts *mo, double *post_mean, double *post_var,
+                       long long *post_count, int flags);
 
 /* ---- a-9: largest eigenvalue of A'A by power iteration --------------------
  * Replaces max_eigenval(A,At,params,im_size,tol,max_iter,verbose)

@@ -168,11 +168,13 @@ __global__ __launch_bounds__(EWB) void fista_momentum_kernel(const double *__res
 
 // ---- MYULA step (SAPG/SAPG_algorithm_Guassian.m:80-81,161):
 //   X = abs( X + gam*(prox - X)/lamb - gam*gradF + sqrt(2 gam) * Z ),  gradF = grad / sigma2
+// MOM: the new sample also updates the running mean / M2 of the posterior moments (MomArgs), while it is in registers
+template <bool MOM>
 __global__ __launch_bounds__(EWB) void myula_step_kernel(double *__restrict__ X, const double *__restrict__ prox,
                                                           const double *__restrict__ grad,
                                                           const double *__restrict__ Z,
                                                           const double *__restrict__ sigma2, double gam, double lamb,
-                                                          double sq2g, size_t P, RngArgs rng, ProxArm arm) {
+                                                          double sq2g, size_t P, RngArgs rng, ProxArm arm, MomArgs mom) {
     const int b = blockIdx.y;
     if (arm.ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
         ProxCtrl c = arm.ctrl[b];          // prox_reset(keep_cur = false) for the cold-start prox that follows
@@ -191,6 +193,8 @@ __global__ __launch_bounds__(EWB) void myula_step_kernel(double *__restrict__ X,
     const size_t base = (size_t)b * P;
     const double s2 = sigma2[b];
     const unsigned step = rng.step_dev ? (unsigned)rng.step_dev[0] : rng.step;
+    const int k = MOM ? mom_sample(mom) : 0;
+    const double rk = 1.0 / (double)(k > 0 ? k : 1);
     for (size_t q = (size_t)blockIdx.x * EWB + threadIdx.x; q < P / 2; q += (size_t)gridDim.x * EWB) {
         const size_t o = base + 2 * q;
         const double2 xv = *reinterpret_cast<const double2 *>(X + o);
@@ -202,16 +206,18 @@ __global__ __launch_bounds__(EWB) void myula_step_kernel(double *__restrict__ X,
         r.x = myula_nocontract(xv.x, pv.x, gv.x, 1.0, zv.x, gam, lamb, s2, sq2g);
         r.y = myula_nocontract(xv.y, pv.y, gv.y, 1.0, zv.y, gam, lamb, s2, sq2g);
         *reinterpret_cast<double2 *>(X + o) = r;
+        if (MOM && k > 0) moments_pair(mom, o, r, k, rk);
     }
 }
 
 // ---- plain MYULA chain (SALSA/myula.m:16): no abs(), the reference's own grouping of the terms
 //   x = (1 - gam/lamb) x - gam (grad/sigma2 - prox/lamb) + sqrt(2 gam) z
+template <bool MOM>
 __global__ __launch_bounds__(EWB) void myula_plain_kernel(double *__restrict__ X, const double *__restrict__ prox,
                                                            const double *__restrict__ grad,
                                                            const double *__restrict__ Z,
                                                            const double *__restrict__ sigma2, double gam, double lamb,
-                                                           double sq2g, size_t P, RngArgs rng, ProxArm arm) {
+                                                           double sq2g, size_t P, RngArgs rng, ProxArm arm, MomArgs mom) {
     const int b = blockIdx.y;
     if (arm.ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
         ProxCtrl c = arm.ctrl[b];
@@ -229,6 +235,8 @@ __global__ __launch_bounds__(EWB) void myula_plain_kernel(double *__restrict__ X
     }
     const size_t base = (size_t)b * P;
     const double s2 = sigma2[b], keep = 1.0 - gam / lamb;
+    const int k = MOM ? mom_sample(mom) : 0;
+    const double rk = 1.0 / (double)(k > 0 ? k : 1);
     for (size_t q = (size_t)blockIdx.x * EWB + threadIdx.x; q < P / 2; q += (size_t)gridDim.x * EWB) {
         const size_t o = base + 2 * q;
         const double2 xv = *reinterpret_cast<const double2 *>(X + o);
@@ -240,6 +248,39 @@ __global__ __launch_bounds__(EWB) void myula_plain_kernel(double *__restrict__ X
         r.x = (keep * xv.x - gam * (gv.x / s2 - pv.x / lamb)) + sq2g * zv.x;
         r.y = (keep * xv.y - gam * (gv.y / s2 - pv.y / lamb)) + sq2g * zv.y;
         *reinterpret_cast<double2 *>(X + o) = r;
+        if (MOM && k > 0) moments_pair(mom, o, r, k, rk);
+    }
+}
+
+// iteration 1 of the chain (its start state) as the accumulator's first sample
+__global__ __launch_bounds__(EWB) void moments_seed_kernel(const double *__restrict__ X, double *__restrict__ mean,
+                                                           double *__restrict__ m2, size_t n2) {
+    const MomArgs m{mean, m2, 1, nullptr, 1, 1};
+    for (size_t q = (size_t)blockIdx.x * EWB + threadIdx.x; q < n2; q += (size_t)gridDim.x * EWB)
+        moments_pair(m, 2 * q, *reinterpret_cast<const double2 *>(X + 2 * q), 1, 1.0);
+}
+
+// outputs of the accumulators: per chain mean and m2 / (n-1) (raw: m2), or (pooled) Chan's pairwise combination of the
+// chains in chain order 0, 1, 2, ...: n = na + nb, d = mean_b - mean_a, mean = mean_a + d nb / n,
+// M2 = M2_a + M2_b + d^2 na nb / n (the arithmetic of sbtv.combine_moments)
+__global__ __launch_bounds__(EWB) void moments_finish_kernel(const double *__restrict__ mean, const double *__restrict__ m2,
+                                                             size_t P, int batch, double n, int pooled, int raw,
+                                                             double *__restrict__ mean_out, double *__restrict__ var_out) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    for (size_t i = (size_t)blockIdx.x * EWB + threadIdx.x; i < P; i += (size_t)gridDim.x * EWB) {
+        double mu = mean[(size_t)b * P + i], s = m2[(size_t)b * P + i], na = n;
+        if (pooled) {
+            for (int c = 1; c < batch; ++c) {
+                const double mb = mean[(size_t)c * P + i], sb = m2[(size_t)c * P + i];
+                const double nt = na + n, d = mb - mu;
+                mu = mu + d * (n / nt);
+                s = (s + sb) + d * d * (na * n / nt);
+                na = nt;
+            }
+        }
+        mean_out[(size_t)b * P + i] = mu;
+        if (var_out) var_out[(size_t)b * P + i] = raw ? s : (na > 1.0 ? s / (na - 1.0) : 0.0);
     }
 }
 
@@ -248,13 +289,41 @@ __global__ __launch_bounds__(EWB) void myula_plain_kernel(double *__restrict__ X
 // --------------------------------------------------------------------------
 int myula_plain_step(sbtv_ctx *ctx, double *X, const double *prox, const double *grad, const double *Z,
                      const double *sigma2_dev, double gam, double lamb, size_t P, int batch, const RngArgs *rng,
-                     const ProxArm *arm) {
+                     const ProxArm *arm, const MomArgs *mom) {
     if (!Z && !rng) return fail(ctx, SBTV_ERR_BADARG, "myula_plain_step: neither a noise array nor generator arguments");
     const RngArgs r = rng ? *rng : RngArgs{0ull, 0u, 0u, nullptr};
     const ProxArm pa = arm ? *arm : ProxArm{nullptr, nullptr, 0, 0.0, 0.0, nullptr};
-    hipLaunchKernelGGL(myula_plain_kernel, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
-                       sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa);
+    if (mom)
+        hipLaunchKernelGGL(myula_plain_kernel<true>, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
+                           sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa, *mom);
+    else
+        hipLaunchKernelGGL(myula_plain_kernel<false>, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
+                           sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa, MomArgs{});
     SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int moments_seed(sbtv_ctx *ctx, const double *X, double *mean, double *m2, size_t P, int batch) {
+    const size_t n = P * batch;
+    hipLaunchKernelGGL(moments_seed_kernel, dim3(ew_blocks(n)), dim3(EWB), 0, ctx->stream, X, mean, m2, n / 2);
+    SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int moments_finish(sbtv_ctx *ctx, const double *mean, const double *m2, size_t P, int batch, long long n, const MomReq &req) {
+    const int pooled = req.pooled && !req.raw;
+    const size_t nout = P * (pooled ? 1 : batch);
+    double *mo = nullptr, *vo = nullptr;
+    const int fl = req.dev ? SBTV_DEVICE_PTRS : SBTV_HOST_PTRS;
+    SBTV_TRY(stage_out_buf(ctx, "mom.mean_out", req.mean, nout, fl, &mo));
+    if (req.var) SBTV_TRY(stage_out_buf(ctx, "mom.var_out", req.var, nout, fl, &vo));
+    hipLaunchKernelGGL(moments_finish_kernel, dim3(ew_blocks(2 * P), pooled ? 1 : batch), dim3(EWB), 0, ctx->stream, mean,
+                       m2, P, batch, (double)n, pooled, req.raw ? 1 : 0, mo, vo);
+    SBTV_HIP(ctx, hipGetLastError());
+    SBTV_TRY(stage_out_copy(ctx, req.mean, mo, nout, fl));
+    if (req.var) SBTV_TRY(stage_out_copy(ctx, req.var, vo, nout, fl));
+    if (req.count)
+        for (size_t c = 0; c < (pooled ? 1 : (size_t)batch); ++c) req.count[c] = pooled ? n * batch : n;
     return 0;
 }
 
@@ -304,12 +373,16 @@ int fista_momentum(sbtv_ctx *ctx, const double *x, const double *xold, double *y
 
 int myula_step(sbtv_ctx *ctx, double *X, const double *prox, const double *grad, const double *Z,
                const double *sigma2_dev, double gam, double lamb, size_t P, int batch, const RngArgs *rng,
-               const ProxArm *arm) {
+               const ProxArm *arm, const MomArgs *mom) {
     if (!Z && !rng) return fail(ctx, SBTV_ERR_BADARG, "myula_step: neither a noise array nor generator arguments");
     const RngArgs r = rng ? *rng : RngArgs{0ull, 0u, 0u, nullptr};
     const ProxArm pa = arm ? *arm : ProxArm{nullptr, nullptr, 0, 0.0, 0.0, nullptr};
-    hipLaunchKernelGGL(myula_step_kernel, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
-                       sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa);
+    if (mom)
+        hipLaunchKernelGGL(myula_step_kernel<true>, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
+                           sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa, *mom);
+    else
+        hipLaunchKernelGGL(myula_step_kernel<false>, dim3(ew_blocks(P), batch), dim3(EWB), 0, ctx->stream, X, prox, grad, Z,
+                           sigma2_dev, gam, lamb, sqrt(2 * gam), P, r, pa, MomArgs{});
     SBTV_HIP(ctx, hipGetLastError());
     return 0;
 }

@@ -1139,7 +1139,7 @@ int fft_cols_inv_sub(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double 
 }
 int fft_cols_inv_myula(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double scale, double *X, const double *prox,
                        const double *Z, const double *sigma2_dev, double gam, double lamb, const RngArgs *rng,
-                       const ProxArm *arm) {
+                       const ProxArm *arm, const MomArgs *mom) {
     if (!fft_cols_inv_step_ok(pl)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_myula: size not on the wave-granular path");
     if (!Z && !rng) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_myula: neither a noise array nor generator arguments");
     ColsPost post;
@@ -1153,7 +1153,15 @@ int fft_cols_inv_myula(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, doubl
     if (rng) post.mrng = *rng;
     if (arm) post.marm = *arm;
     const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
-    if (pl.n1 == 1024)
+    if (mom) {
+        post.mom = *mom;
+        if (pl.n1 == 1024)
+            hipLaunchKernelGGL((cols_inv_wave_kernel<10, 16, 16 | 128>), grid, block, 0, ctx->stream, S, (double *)nullptr,
+                               pl.tw_n1, pl.tw_M, pl.N, scale, (const int *)nullptr, post);
+        else
+            hipLaunchKernelGGL((cols_inv_wave_kernel<9, 8, 16 | 128>), grid, block, 0, ctx->stream, S, (double *)nullptr,
+                               pl.tw_n1, pl.tw_M, pl.N, scale, (const int *)nullptr, post);
+    } else if (pl.n1 == 1024)
         hipLaunchKernelGGL((cols_inv_wave_kernel<10, 16, 16>), grid, block, 0, ctx->stream, S, (double *)nullptr, pl.tw_n1,
                            pl.tw_M, pl.N, scale, (const int *)nullptr, post);
     else

@@ -283,7 +283,8 @@ __device__ __forceinline__ double2 step_nocontract(double2 y, double a, double2 
 
 // column pass, inverse: tiled packed half spectrum -> real columns (times `scale`); POST: + SALSA bookkeeping
 // (see fft_cols_inv_kernel).  Partial sums: one per COLUMN (post.partials[b][6][N]).
-// PM: 0 plain; 8 gradient step into post.ystep; 16 MYULA step of post.ystep; 64 x and post.g = x - post.bu_in; 1 + (2 if post.tru) + (4 if post.xprev): bookkeeping pass (compile-time so that the epilogue is one
+// PM: 0 plain; 8 gradient step into post.ystep; 16 MYULA step of post.ystep (+ 128: and the running mean / M2 of the
+// posterior moments, post.mom); 64 x and post.g = x - post.bu_in; 1 + (2 if post.tru) + (4 if post.xprev): bookkeeping pass (compile-time so that the epilogue is one
 // straight-line block the scheduler can software-pipeline)
 template <int LOG2N, int V, int PM>
 __global__ __launch_bounds__(64 * TW, 2) void cols_inv_wave_kernel(const double2 *__restrict__ S, double *__restrict__ x,
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(64 * TW, 2) void cols_inv_wave_kernel(const double2
             const double2 xv = cscale(v[s], scale);
             yp[lane + s * 64] = step_nocontract(yv[s], post.alpha, xv);
         }
-    } else if constexpr (PM == 16) {
+    } else if constexpr ((PM & ~128) == 16) {
         // MYULA step on the column still in registers (the gradient is never stored): see fft_cols_inv_myula
         if (post.marm.ctrl && blockIdx.x == 0 && threadIdx.x == 0) {
             ProxCtrl c = post.marm.ctrl[b];      // prox_reset(keep_cur = false) for the cold-start prox that follows
@@ -369,6 +370,13 @@ __global__ __launch_bounds__(64 * TW, 2) void cols_inv_wave_kernel(const double2
         const double s2 = post.msig2[b];
         const unsigned step = post.mrng.step_dev ? (unsigned)post.mrng.step_dev[0] : post.mrng.step;
         const size_t q0 = (size_t)j * n;               // pair index of the column's first row pair within the image
+        constexpr bool MOM = (PM & 128) != 0;
+        int mk = 0;
+        double mrk = 1.0;
+        if constexpr (MOM) {
+            mk = mom_sample(post.mom);
+            mrk = 1.0 / (double)(mk > 0 ? mk : 1);
+        }
         constexpr int CH = 4;
 #pragma unroll
         for (int c0 = 0; c0 < V; c0 += CH) {
@@ -389,6 +397,9 @@ __global__ __launch_bounds__(64 * TW, 2) void cols_inv_wave_kernel(const double2
                 r.x = myula_nocontract(xv[q].x, pv[q].x, gv.x, 1.0, zv[q].x, post.mgam, post.mlamb, s2, post.msq2g);
                 r.y = myula_nocontract(xv[q].y, pv[q].y, gv.y, 1.0, zv[q].y, post.mgam, post.mlamb, s2, post.msq2g);
                 xp[e] = r;
+                // the new sample is still in registers: +32 B per pixel, X is not read again
+                if constexpr (MOM)
+                    if (mk > 0) moments_pair(post.mom, 2 * (colbase + e), r, mk, mrk);
             }
             __builtin_amdgcn_sched_barrier(0);
         }

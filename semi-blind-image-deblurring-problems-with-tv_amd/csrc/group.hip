@@ -370,9 +370,11 @@ int salsa_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, con
 
 int sapg_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, const sbtv_sapg_opts *op, const double *x0,
                  const double *noise, double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu,
-                 double *gx, double *grads, double *eb, double *x_last, int flags) {
+                 double *gx, double *grads, double *eb, double *x_last, int flags, const MomReq *mom) {
     if (!g) return SBTV_ERR_BADARG;
     if (!y || !op || n_items < 1 || M < 2 || N < 2) return gfail(g, SBTV_ERR_BADARG, "SAPG_algorithm_sharded: missing required argument");
+    if (mom && mom->pooled && !mom->raw)
+        return gfail(g, SBTV_ERR_BADARG, "SAPG_algorithm_sharded: pooled moments are combined by the caller");
     const int ns = active_shards(g, n_items);
     if (noise && ns > 1 && (flags & SBTV_DEVICE_PTRS))
         return gfail(g, SBTV_ERR_BADARG, "SAPG_algorithm_sharded: injected noise must be a host array (it is re-packed per shard)");
@@ -402,12 +404,18 @@ int sapg_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, cons
         }
         users[r] = ShardUser{g, r};
         const bool coll = shared && ns > 1;
-        return sbtv_SAPG_algorithm(g->ctxs[r], shared ? y : y + b * P, M, N, (int)nb, &o, off(x0, b * P), nzp,
-                                   off(thetas, b * S), off(ps, b * 2 * S), off(sigmas, b * S), off(logpi, b * S),
-                                   off(logpi_wu, b * W), off(gx, b * S), off(grads, b * 4 * S), off(eb, b * 4),
-                                   off(x_last, b * P),
-                                   coll ? reinterpret_cast<sbtv_allreduce_fn>(&group_allreduce) : nullptr,
-                                   coll ? &users[r] : nullptr, flags | (coll ? SBTV_REDUCE_DEVICE : 0));
+        MomReq mr{};
+        if (mom) {                                       // this shard's chains of the per-chain moment outputs
+            mr = *mom;
+            mr.mean = mom->mean + b * P;
+            mr.var = off(mom->var, b * P);
+            mr.count = off(mom->count, b);
+        }
+        return sapg_impl(g->ctxs[r], shared ? y : y + b * P, M, N, (int)nb, &o, off(x0, b * P), nzp, off(thetas, b * S),
+                         off(ps, b * 2 * S), off(sigmas, b * S), off(logpi, b * S), off(logpi_wu, b * W), off(gx, b * S),
+                         off(grads, b * 4 * S), off(eb, b * 4), off(x_last, b * P),
+                         coll ? reinterpret_cast<sbtv_allreduce_fn>(&group_allreduce) : nullptr, coll ? &users[r] : nullptr,
+                         flags | (coll ? SBTV_REDUCE_DEVICE : 0), mom ? &mr : nullptr);
     });
 }
 

@@ -752,9 +752,31 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
 // ---------------------------------------------------------------------------
 // a-6: plain MYULA chain at fixed parameters (SALSA/myula.m:1-22)
 // ---------------------------------------------------------------------------
-int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille, double lambda,
-               double gamma, const double *theta, const double *sigma2, int samples, int chambolleit,
-               unsigned long long seed, int chain_offset, const double *noise, double *x_out, int flags) {
+}  // extern "C"
+
+namespace sbtv {
+// iterations of the accumulator: first, first + thin, ... <= last; 0 when iteration ii is not one of them
+static inline int mom_sample_of(const MomReq *mr, int ii) {
+    if (!mr || ii < mr->first || (ii - mr->first) % mr->thin != 0) return 0;
+    return (ii - mr->first) / mr->thin + 1;
+}
+static inline long long mom_count(const MomReq &mr, int last) { return (last - mr.first) / mr.thin + 1; }
+// sbtv_moments_opts -> MomReq: checks first / thin (first = 0 -> first0) against the last iteration `last`
+static int mom_resolve(sbtv_ctx *ctx, const char *who, const sbtv_moments_opts *mo, int first0, int last, double *post_mean,
+                       double *post_var, long long *post_count, int flags, MomReq *out) {
+    if (!mo || !post_mean) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": moments options and post_mean are required");
+    const int first = mo->first == 0 ? first0 : mo->first;
+    if (mo->thin < 1 || first < 1 || first > last)
+        return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": need thin >= 1 and 1 <= first <= the last iteration");
+    *out = MomReq{first, mo->thin, mo->pooled ? 1 : 0, post_mean, post_var, post_count, (flags & SBTV_DEVICE_PTRS) != 0,
+                  false};
+    return 0;
+}
+
+static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                      double lambda, double gamma, const double *theta, const double *sigma2, int samples, int chambolleit,
+                      unsigned long long seed, int chain_offset, const double *noise, double *x_out, int flags,
+                      const MomReq *mom) {
     if (!ctx) return SBTV_ERR_BADARG;
     if (!y || !taps || !theta || !sigma2 || !x_out || batch < 1 || samples < 2 || !(lambda > 0.0) || !(gamma > 0.0) ||
         chain_offset < 0)
@@ -774,6 +796,11 @@ int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const do
     const bool noise_host = noise && !(flags & SBTV_DEVICE_PTRS);
     double *X = nullptr, *prox = nullptr, *grad = nullptr, *Z = nullptr, *par = nullptr, *acc = nullptr;
     double2 *S = nullptr, *Hs = nullptr, *Ys = nullptr;
+    double *pm_mean = nullptr, *pm_m2 = nullptr;          // running mean / M2 of the samples [batch][P]
+    if (mom) {
+        SBTV_TRY(ws_get_t(ctx, "myula.pm_mean", cnt, &pm_mean));
+        SBTV_TRY(ws_get_t(ctx, "myula.pm_m2", cnt, &pm_m2));
+    }
     SBTV_TRY(stage_out_buf(ctx, "myula.X", x_out, cnt, flags, &X));
     SBTV_TRY(ws_get_t(ctx, "myula.prox", cnt, &prox));
     SBTV_TRY(ws_get_t(ctx, "myula.grad", cnt, &grad));
@@ -801,6 +828,7 @@ int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const do
         SBTV_TRY(spec_unpack(ctx, fp, S, Ys));
     }
     SBTV_HIP(ctx, hipMemcpyAsync(X, yd, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));   // x = op.y  (:3,11)
+    if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));            // iteration 1 = y
     const double inv_scale = 1.0 / ((double)fp.n1 * N);
     SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, 1e-3, 0.249, false, nullptr));
     const ProxArm arm{pp.ctrl, lam_d, chambolleit, 1e-3, 0.249, nullptr};
@@ -825,11 +853,55 @@ int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const do
             zd = noise + step * cnt;
         }
         const RngArgs r{seed, (unsigned)step, (unsigned)chain_offset, nullptr};
-        SBTV_TRY(myula_plain_step(ctx, X, prox, grad, zd, sig_d, gamma, lambda, P, batch, &r, &arm));   // :16
+        const MomArgs ma{pm_mean, pm_m2, mom_sample_of(mom, ii), nullptr, 1, 1};
+        SBTV_TRY(myula_plain_step(ctx, X, prox, grad, zd, sig_d, gamma, lambda, P, batch, &r, &arm,
+                                  ma.k > 0 ? &ma : nullptr));                                       // :16
     }
+    if (mom) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(*mom, samples > 2 ? samples - 1 : 1), *mom));
     SBTV_TRY(stage_out_copy(ctx, x_out, X, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return canary_epilogue(ctx, 0);
+}
+}  // namespace sbtv
+
+extern "C" {
+
+int sbtv_myula(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille, double lambda,
+               double gamma, const double *theta, const double *sigma2, int samples, int chambolleit,
+               unsigned long long seed, int chain_offset, const double *noise, double *x_out, int flags) {
+    return myula_impl(ctx, y, M, N, batch, taps, taille, lambda, gamma, theta, sigma2, samples, chambolleit, seed,
+                      chain_offset, noise, x_out, flags, nullptr);
+}
+
+int sbtv_myula_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                       double lambda, double gamma, const double *theta, const double *sigma2, int samples, int chambolleit,
+                       unsigned long long seed, int chain_offset, const double *noise, double *x_out,
+                       const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    MomReq mr;
+    SBTV_TRY(mom_resolve(ctx, "myula_moments", mo, 1, samples > 2 ? samples - 1 : 1, post_mean, post_var, post_count, flags,
+                         &mr));
+    if (mr.pooled && batch > 1) {
+        // pooling needs chains of ONE posterior: the same y, taps, theta and sigma2 in every chain
+        const size_t P = (size_t)M * N, t2 = (size_t)taille * taille;
+        bool same = y && taps && theta && sigma2 && M > 0 && N > 0 && taille > 0;
+        for (int b = 1; same && b < batch; ++b)
+            same = theta[b] == theta[0] && sigma2[b] == sigma2[0] && !memcmp(taps, taps + b * t2, sizeof(double) * t2);
+        if (same) {
+            std::vector<double> yh;
+            const double *yv = y;
+            if (flags & SBTV_DEVICE_PTRS) {
+                SBTV_HIP(ctx, hipSetDevice(ctx->device));
+                yh.resize(P * batch);
+                SBTV_HIP(ctx, hipMemcpy(yh.data(), y, sizeof(double) * P * batch, hipMemcpyDeviceToHost));
+                yv = yh.data();
+            }
+            for (int b = 1; same && b < batch; ++b) same = !memcmp(yv, yv + b * P, sizeof(double) * P);
+        }
+        if (!same) return fail(ctx, SBTV_ERR_BADARG, "myula_moments: pooled = 1 needs chains with the same y, taps, theta and sigma2");
+    }
+    return myula_impl(ctx, y, M, N, batch, taps, taille, lambda, gamma, theta, sigma2, samples, chambolleit, seed,
+                      chain_offset, noise, x_out, flags, &mr);
 }
 
 // ---------------------------------------------------------------------------
@@ -839,6 +911,33 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                         const double *x0, const double *noise, double *thetas, double *ps, double *sigmas,
                         double *logpi, double *logpi_wu, double *gx, double *grads, double *eb, double *x_last,
                         sbtv_allreduce_fn reduce_fn, void *reduce_user, int flags) {
+    return sapg_impl(ctx, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb, x_last,
+                     reduce_fn, reduce_user, flags, nullptr);
+}
+
+int sbtv_SAPG_algorithm_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op,
+                                const double *x0, const double *noise, double *thetas, double *ps, double *sigmas,
+                                double *logpi, double *logpi_wu, double *gx, double *grads, double *eb, double *x_last,
+                                sbtv_allreduce_fn reduce_fn, void *reduce_user, const sbtv_moments_opts *mo,
+                                double *post_mean, double *post_var, long long *post_count, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!op) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm_moments: bad arguments");
+    MomReq mr;
+    SBTV_TRY(mom_resolve(ctx, "SAPG_algorithm_moments", mo, op->burnIn, op->samples, post_mean, post_var, post_count, flags,
+                         &mr));
+    if (mr.pooled && !op->share_gradients && batch > 1)
+        return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm_moments: pooled = 1 needs chains of one posterior (share_gradients = 1)");
+    return sapg_impl(ctx, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb, x_last,
+                     reduce_fn, reduce_user, flags, &mr);
+}
+
+}  // extern "C"
+
+namespace sbtv {
+int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op, const double *x0,
+              const double *noise, double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu, double *gx,
+              double *grads, double *eb, double *x_last, sbtv_allreduce_fn reduce_fn, void *reduce_user, int flags,
+              const MomReq *mom) {
     if (!ctx) return SBTV_ERR_BADARG;
     if (!y || !op || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: bad arguments");
     if (op->kind < 0 || op->kind > 2) return fail(ctx, SBTV_ERR_PSF, "SAPG_algorithm: unknown PSF kind");
@@ -861,8 +960,26 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
     if (!reduce_fn && !(flags & (SBTV_SAPG_HOST_LOOP | SBTV_REDUCE_DEVICE)) && !(noise && (flags & SBTV_DEVICE_PTRS))) {
         if (sbtv_group *lg = lanes_group(ctx, batch, shared != 0)) {
             LaneCall lc(ctx, lg);
-            return lc.done(sapg_sharded(lg, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb,
-                                        x_last, flags), batch);
+            if (!mom || !mom->pooled)
+                return lc.done(sapg_sharded(lg, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads,
+                                            eb, x_last, flags, mom), batch);
+            // pooled moments: every lane hands its chains' mean / M2 to this context, which pools them in chain order
+            // afterwards (the same arithmetic as on one stream)
+            const size_t cntl = (size_t)M * N * batch;
+            double *lm = nullptr, *l2 = nullptr;
+            SBTV_TRY(ws_get_t(ctx, "sapg.pm_lanes_mean", cntl, &lm));
+            SBTV_TRY(ws_get_t(ctx, "sapg.pm_lanes_m2", cntl, &l2));
+            MomReq lr = *mom;
+            lr.mean = lm;
+            lr.var = l2;
+            lr.count = nullptr;
+            lr.dev = true;
+            lr.raw = true;
+            SBTV_TRY(lc.done(sapg_sharded(lg, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb,
+                                          x_last, flags, &lr), batch));
+            SBTV_TRY(moments_finish(ctx, lm, l2, (size_t)M * N, batch, mom_count(*mom, op->samples), *mom));
+            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            return canary_epilogue(ctx, 0);
         }
     }
     FftPlan fp, fps;
@@ -887,6 +1004,11 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
     SBTV_TRY(ws_get_t(ctx, "sapg.prox", cnt, &prox));
     SBTV_TRY(ws_get_t(ctx, "sapg.grad", cnt, &grad));
     SBTV_TRY(ws_get_t(ctx, "sapg.Z", cnt, &Z));
+    double *pm_mean = nullptr, *pm_m2 = nullptr;          // running mean / M2 of the samples [batch][P]
+    if (mom) {
+        SBTV_TRY(ws_get_t(ctx, "sapg.pm_mean", cnt, &pm_mean));
+        SBTV_TRY(ws_get_t(ctx, "sapg.pm_m2", cnt, &pm_m2));
+    }
     double2 *S = nullptr, *Hs = nullptr, *D1s = nullptr, *D2s = nullptr, *Ys = nullptr, *S1 = nullptr;
     const size_t spec = fp.u_img;
     SBTV_TRY(ws_get_t(ctx, "sapg.S", (size_t)batch * fp.s_img, &S));
@@ -1061,18 +1183,28 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
     // normals are drawn inside the step kernel (no Z array is written or read); injected noise goes through Z.
     // The step kernel also re-arms the prox control blocks for the cold-start prox that always follows it.
     const ProxArm arm{pp.ctrl, lam_d, op->chambolleit, 1e-3, 0.249, nullptr};
+    // Posterior moments: the step of SAPG iteration main_ii (0 in the warm-up) also updates the running mean / M2 when
+    // the iteration is selected; a captured iteration (in_graph) decides that on the device from u.it[0] == ii.
+    int main_ii = 0;
+    int *it_dev = nullptr;                    // device iteration counter of the device-resident loop (set below)
     auto myula = [&](bool in_graph) -> int {
         const bool fused = grad_in_S;
         grad_in_S = false;
+        MomArgs ma{pm_mean, pm_m2, 0, nullptr, mom ? mom->first : 1, mom ? mom->thin : 1};
+        if (mom && main_ii > 0) {
+            if (in_graph) ma.it = it_dev;
+            else ma.k = mom_sample_of(mom, main_ii);
+        }
+        const MomArgs *mp = (ma.k > 0 || ma.it) ? &ma : nullptr;
         if (noise) {
             SBTV_TRY(next_noise());
-            if (fused) return fft_cols_inv_myula(ctx, fp, S, inv_scale, X, prox, Z, sig_d, gam, lamb, nullptr, &arm);
-            return myula_step(ctx, X, prox, grad, Z, sig_d, gam, lamb, P, batch, nullptr, &arm);
+            if (fused) return fft_cols_inv_myula(ctx, fp, S, inv_scale, X, prox, Z, sig_d, gam, lamb, nullptr, &arm, mp);
+            return myula_step(ctx, X, prox, grad, Z, sig_d, gam, lamb, P, batch, nullptr, &arm, mp);
         }
         const RngArgs r{op->seed, (unsigned)noise_step, (unsigned)op->chain_offset, in_graph ? step_d : nullptr};
         if (!in_graph) ++noise_step;
-        if (fused) return fft_cols_inv_myula(ctx, fp, S, inv_scale, X, prox, nullptr, sig_d, gam, lamb, &r, &arm);
-        return myula_step(ctx, X, prox, grad, nullptr, sig_d, gam, lamb, P, batch, &r, &arm);
+        if (fused) return fft_cols_inv_myula(ctx, fp, S, inv_scale, X, prox, nullptr, sig_d, gam, lamb, &r, &arm, mp);
+        return myula_step(ctx, X, prox, grad, nullptr, sig_d, gam, lamb, P, batch, &r, &arm, mp);
     };
     // prox = chambolle(X, lambda*theta, cold start); armed: the MYULA step before it has reset the control blocks
     // Inside the device-resident loop the prox runs in the multi-buffer optimistic mode: its Chambolle launches go back to
@@ -1102,7 +1234,8 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
     // launch-bound).  The graph body reads every per-iteration value (taps, lambda*theta, sigma^2, noise step)
     // from the device parameter block, which its first node refreshes from the pinned staging block.
     const bool params_move = !(op->fix_p[0] && (npar < 2 || op->fix_p[1]));
-    bool use_graph = (noise == nullptr) && graph_wanted(cnt);
+    // (the host-side loop has no device iteration counter to select the moments' samples from: it launches eagerly then)
+    bool use_graph = (noise == nullptr) && graph_wanted(cnt) && !(mom && !dev_loop);
     hipGraphExec_t g_warm = nullptr, g_main = nullptr;
     struct GraphGuard {
         hipGraphExec_t *a, *b;
@@ -1209,6 +1342,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
             u.prox_k = op->chambolleit; u.prox_base = op->chambolleit / nlp; u.prox_extra = op->chambolleit % nlp;
         }
         u.scal = scal_d; u.chain = chain_d; u.par = par; u.delta = delta_d; u.it = it_d; u.red = red_d; u.G = G_d;
+        it_dev = it_d;
         const size_t bs = (size_t)batch * samples;
         u.tr_theta = tr_d; u.tr_sigma = tr_d + bs; u.tr_logpi = tr_d + 2 * bs; u.tr_gx = tr_d + 3 * bs;
         u.tr_p = tr_d + 4 * bs; u.tr_grads = tr_d + 6 * bs; u.tr_wu = tr_d + 10 * bs;
@@ -1318,6 +1452,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
         SBTV_TRY(fetch_scalars());
         std::vector<double> logpi0(batch);
         for (int b = 0; b < batch; ++b) logpi0[b] = log_pi(b, theta[b], sig2[b]);                  // :131
+        if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));          // iteration 1
         SBTV_TRY(do_prox(false));                                      // proxGX = proxG(X, thetas(1))   (:134)
         const bool in_stream = shared && reduce_dev;
         if (in_stream) SBTV_HIP(ctx, hipMemsetAsync(red_d, 0, sizeof(double) * 8, ctx->stream));
@@ -1336,6 +1471,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
         }
         for (int ii = 2; ii <= samples; ++ii) {
             collective_done = false;
+            main_ii = ii;
             if (local_rc == 0) {
                 bool replayed = false;
                 int rc = (ii == inject_ii) ? fail(ctx, SBTV_ERR_NOMEM, "SAPG_algorithm: injected failure (SBTV_TEST_FAIL_SAPG)") : 0;
@@ -1377,6 +1513,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
             else
                 SBTV_TRY(stage_out_copy(ctx, x_last, X, cnt, flags));
         }
+        if (mom) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(*mom, samples), *mom));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double *h_theta = tr.data(), *h_sigma = h_theta + bs, *h_logpi = h_theta + 2 * bs, *h_gx = h_theta + 3 * bs,
                      *h_p = h_theta + 4 * bs, *h_grads = h_theta + 6 * bs, *h_wu = h_theta + 10 * bs;
@@ -1440,6 +1577,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
         if (logpi) logpi[(size_t)b * samples] = log_pi(b, theta[b], sig2[b]);   // :131
         if (op->burnIn == 1) { sum_th[b] += theta[b]; sum_s[b] += sig2[b]; sum_p0[b] += p0[b]; sum_p1[b] += p1[b]; }
     }
+    if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));              // iteration 1
     SBTV_TRY(upload_lam_sigma(theta));
     SBTV_TRY(do_prox(false));                                      // proxGX = proxG(X, thetas(1))   (:134)
     // device work of SAPG iteration ii up to the scalars it needs on the host.  In the shared-gradient mode a failure
@@ -1476,6 +1614,7 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
     };
     for (int ii = 2; ii <= samples; ++ii) {
         const int i0 = ii - 1;
+        main_ii = ii;
         const int rc_dev = iterate_device(ii);
         if (rc_dev != 0 && !(shared && reduce_fn)) return rc_dev;
         const double delta = op->d_scale * (pow((double)ii + op->iter_offset, -op->d_exp) / dimX);     // :55
@@ -1552,9 +1691,10 @@ int sbtv_SAPG_algorithm(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
         else
             SBTV_TRY(stage_out_copy(ctx, x_last, X, cnt, flags));
     }
+    if (mom) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(*mom, samples), *mom));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     (void)nsteps_noise;
     return canary_epilogue(ctx, 0);
 }
 
-}  // extern "C"
+}  // namespace sbtv

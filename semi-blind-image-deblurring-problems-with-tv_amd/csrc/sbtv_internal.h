@@ -255,6 +255,64 @@ __device__ __forceinline__ double myula_nocontract(double x, double p, double v,
     const double g = v * scale;
     return fabs(((x + gam * (p - x) / lamb) - gam * (g / s2)) + sq2g * z);
 }
+// ---- posterior moments of the MYULA samples (sbtv_SAPG_algorithm_moments, sbtv_myula_moments)
+// Welford update of one pixel's running mean / M2 with sample number k of the accumulator (rk = 1/k): ONE definition for
+// every kernel that accumulates (element-wise steps, the epilogue of the inverse column pass, the seed of iteration 1), no
+// contraction anywhere in it, so every path gives the same bits.  k = 1 starts the accumulator (the buffers' previous
+// contents are not read).
+__device__ __forceinline__ void welford_nocontract(double &mean, double &m2, double x, int k, double rk) {
+#pragma clang fp contract(off)
+    if (k == 1) {
+        mean = x;
+        m2 = 0.0;
+        return;
+    }
+    const double d = x - mean;
+    mean = mean + d * rk;
+    m2 = m2 + d * (x - mean);
+}
+// what a MYULA step kernel accumulates: mean / m2 [batch][P] (device).  Eager launches carry the sample number k > 0 of
+// the iteration (unselected iterations launch the plain kernels); a captured graph passes k = 0 and the kernel derives it
+// from the iteration counter in device memory: iteration ii = it[0] is sample (ii - first) / thin + 1 when ii >= first and
+// thin divides ii - first, else nothing is accumulated.
+struct MomArgs {
+    double *mean, *m2;
+    int k;
+    const int *it;
+    int first, thin;
+};
+__device__ __forceinline__ int mom_sample(const MomArgs &m) {
+    if (m.k > 0) return m.k;
+    const int ii = m.it[0];
+    if (ii < m.first || (ii - m.first) % m.thin != 0) return 0;
+    return (ii - m.first) / m.thin + 1;
+}
+// two neighbouring pixels (offset o, even) of the accumulators take the sample pair r (sample number k > 0, rk = 1/k)
+__device__ __forceinline__ void moments_pair(const MomArgs &m, size_t o, double2 r, int k, double rk) {
+    double2 mu = make_double2(0.0, 0.0), s = make_double2(0.0, 0.0);
+    if (k > 1) {
+        mu = *reinterpret_cast<const double2 *>(m.mean + o);
+        s = *reinterpret_cast<const double2 *>(m.m2 + o);
+    }
+    welford_nocontract(mu.x, s.x, r.x, k, rk);
+    welford_nocontract(mu.y, s.y, r.y, k, rk);
+    *reinterpret_cast<double2 *>(m.mean + o) = mu;
+    *reinterpret_cast<double2 *>(m.m2 + o) = s;
+}
+// a moments request of sbtv_SAPG_algorithm_moments / sbtv_myula_moments after argument checks (first resolved, >= 1)
+struct MomReq {
+    int first, thin, pooled;
+    double *mean, *var;         // [batch or 1][P]; device pointers when dev
+    long long *count;           // host, [batch or 1]; may be null
+    bool dev;
+    bool raw;                   // var receives M2 per chain (a lane of a pooled call: the parent pools)
+};
+// iteration 1 (the start state) as sample 1: mean = X, m2 = 0
+int moments_seed(sbtv_ctx *ctx, const double *X, double *mean, double *m2, size_t P, int batch);
+// mean / m2 of `batch` chains of n samples each -> req's outputs: per chain (var = m2 / (n-1), 0 for n = 1), or pooled over
+// the chains with Chan's pairwise combination in chain order 0, 1, 2, ...; raw: m2 instead of var (no pooling)
+int moments_finish(sbtv_ctx *ctx, const double *mean, const double *m2, size_t P, int batch, long long n, const MomReq &req);
+
 // where the in-kernel generator of the MYULA step takes its counters from
 struct RngArgs {
     unsigned long long seed;
@@ -290,7 +348,13 @@ int salsa_sharded(::sbtv_group *g, const double *y, int M, int N, int n_items, c
                   int *numA, int *numAt, int *n_outer, int flags);
 int sapg_sharded(::sbtv_group *g, const double *y, int M, int N, int n_items, const sbtv_sapg_opts *op,
                  const double *x0, const double *noise, double *thetas, double *ps, double *sigmas, double *logpi,
-                 double *logpi_wu, double *gx, double *grads, double *eb, double *x_last, int flags);
+                 double *logpi_wu, double *gx, double *grads, double *eb, double *x_last, int flags,
+                 const MomReq *mom = nullptr);
+// sbtv_SAPG_algorithm with an optional moments request (sapg.hip)
+int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op, const double *x0,
+              const double *noise, double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu, double *gx,
+              double *grads, double *eb, double *x_last, sbtv_allreduce_fn reduce_fn, void *reduce_user, int flags,
+              const MomReq *mom);
 int fista_sharded(::sbtv_group *g, const double *b, int M, int N, int n_items, const double *taps, int taille,
                   const double *tau, double L, int prox_iters, int stopcriterion, double tolerance, int maxiters,
                   int zero_start, const double *true_x, double *x_out, double *objective, double *mses, int *n_iter,
@@ -456,6 +520,7 @@ struct ColsPost {
     double mgam = 0.0, mlamb = 0.0, msq2g = 0.0;
     RngArgs mrng = {0ull, 0u, 0u, nullptr};
     ProxArm marm = {nullptr, nullptr, 0, 0.0, 0.0, nullptr};
+    MomArgs mom = {nullptr, nullptr, 0, nullptr, 1, 1};   // MYULA mode with moments (PM bit 128)
 };
 // X <- | X + gam (prox - X)/lamb - gam (scale colIFFT(S))/sigma2 + sqrt(2 gam) Z |  with the gradient still in the
 // registers of the inverse column pass (same bits as fft_cols_inv followed by myula_step); Z: injected noise or null
@@ -463,7 +528,7 @@ struct ColsPost {
 // does.  Sizes of the wave-granular column pass only (fft_cols_inv_step_ok).
 int fft_cols_inv_myula(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double scale, double *X, const double *prox,
                        const double *Z, const double *sigma2_dev, double gam, double lamb, const RngArgs *rng,
-                       const ProxArm *arm);
+                       const ProxArm *arm, const MomArgs *mom = nullptr);
 int fft_cols_blocks(const FftPlan &pl);
 // y <- y - alpha * (scale * colIFFT(S)) with the transform's output still in registers (my_fista.m:25: the gradient is
 // never written); only for the sizes of the wave-granular column pass (fft_cols_inv_step_ok), same bits as
@@ -532,10 +597,10 @@ int fista_momentum(sbtv_ctx *ctx, const double *x, const double *xold, double *y
 // Z == nullptr: the normals are drawn in the kernel from `rng` (the numbers randn_kernel would have stored)
 int myula_step(sbtv_ctx *ctx, double *X, const double *prox, const double *grad, const double *Z,
                const double *sigma2_dev, double gam, double lamb, size_t P, int batch, const RngArgs *rng = nullptr,
-               const ProxArm *arm = nullptr);
+               const ProxArm *arm = nullptr, const MomArgs *mom = nullptr);
 int myula_plain_step(sbtv_ctx *ctx, double *X, const double *prox, const double *grad, const double *Z,
                      const double *sigma2_dev, double gam, double lamb, size_t P, int batch, const RngArgs *rng,
-                     const ProxArm *arm);
+                     const ProxArm *arm, const MomArgs *mom = nullptr);
 int fft_cols_fwd_f(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const double *add, double2 *S, const int *frozen,
                    double *tvp = nullptr);
 bool fft_cols_tv_ok(const FftPlan &pl);

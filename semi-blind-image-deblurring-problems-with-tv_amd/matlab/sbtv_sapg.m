@@ -44,9 +44,19 @@ pwu = libpointer('doublePtr', zeros(1,W)); pgx = libpointer('doublePtr', zeros(1
 pgr = libpointer('doublePtr', zeros(S,4)); peb = libpointer('doublePtr', zeros(1,4));
 pxl = libpointer('doublePtr', zeros(M,N));
 x0 = []; if isfield(op,'X0'), x0 = op.X0; end
+post = isfield(op, 'posterior') && op.posterior;       % results.posteriormean / posteriorvar (:233-246,292-293)
 tic;
-rc = calllib('libsbtv', 'sbtv_SAPG_algorithm', ctx, y, int32(M), int32(N), int32(1), o, x0, [], ...
-             pth, pps, psg, plp, pwu, pgx, pgr, peb, pxl, [], [], int32(0));
+if post
+    mo = libstruct('sbtv_moments_opts');
+    mo.first = int32(getf(op, 'posterior_first', 0));    % 0: op.burnIn, where the reference creates its accumulator
+    mo.thin = int32(getf(op, 'posterior_thin', 1)); mo.pooled = int32(0);
+    ppm = libpointer('doublePtr', zeros(M,N)); ppv = libpointer('doublePtr', zeros(M,N));
+    rc = calllib('libsbtv', 'sbtv_SAPG_algorithm_moments', ctx, y, int32(M), int32(N), int32(1), o, x0, [], ...
+                 pth, pps, psg, plp, pwu, pgx, pgr, peb, pxl, [], [], mo, ppm, ppv, [], int32(0));
+else
+    rc = calllib('libsbtv', 'sbtv_SAPG_algorithm', ctx, y, int32(M), int32(N), int32(1), o, x0, [], ...
+                 pth, pps, psg, plp, pwu, pgx, pgr, peb, pxl, [], [], int32(0));
+end
 if rc ~= 0, error('sbtv:SAPG', '%s', calllib('libsbtv', 'sbtv_last_error', ctx)); end
 eb = peb.Value;
 results.execTimeFindParameters = toc;                       % fields of SAPG_algorithm_Guassian.m:250-306
@@ -69,6 +79,9 @@ rc = calllib('libsbtv', 'sbtv_err_psf', int32(kind), int32(o.psf_size), [ps(:,1)
 if rc ~= 0, error('sbtv:SAPG', '%s', calllib('libsbtv', 'sbtv_last_error', [])); end
 results.err_psf = perr.Value;
 results.Xlast_sample = reshape(pxl.Value, M, N);
+if post                                                    % unbiased variance M2/(n-1) (include/sbtv.h)
+    results.posteriormean = reshape(ppm.Value, M, N); results.posteriorvar = reshape(ppv.Value, M, N);
+end
 results.options = op;
 end
 

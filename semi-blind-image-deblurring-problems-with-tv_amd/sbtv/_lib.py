@@ -54,6 +54,10 @@ class sbtv_sapg_opts(C.Structure):
                 ("seed", C.c_ulonglong), ("chain_offset", C.c_int), ("iter_offset", C.c_int)]
 
 
+class sbtv_moments_opts(C.Structure):
+    _fields_ = [("first", C.c_int), ("thin", C.c_int), ("pooled", C.c_int)]
+
+
 def vptr(a):
     """void* of a NumPy array's data.  (numpy's `a.ctypes` builds a helper object on every access, ~25 us a time: with
     seven output arrays that was a third of the fixed cost of a SALSA call.)  The caller keeps `a` alive."""
@@ -103,7 +107,11 @@ SIGNATURES = {
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),
+    "sbtv_SAPG_algorithm_moments": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P, ALLREDUCE_FN, _P, C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
     "sbtv_myula": (_I, [_P, _P, _I, _I, _I, _P, _I, _D, _D, _P, _P, _I, _I, C.c_ulonglong, _I, _P, _P, _I]),
+    "sbtv_myula_moments": (_I, [_P, _P, _I, _I, _I, _P, _I, _D, _D, _P, _P, _I, _I, C.c_ulonglong, _I, _P, _P,
+                                C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
     "sbtv_max_eigenval": (_I, [_P, _P, _I, _P, _I, _I, _D, _I, _P, _P, _I]),
     "sbtv_PSNR": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
     "sbtv_MSE": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),

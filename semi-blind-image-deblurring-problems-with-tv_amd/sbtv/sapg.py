@@ -76,11 +76,63 @@ def demo_setup(kind, x, noise, evMax, BSNR=30.0, true_params=None, BSNR_min=None
                 th_init=th_init, dimX=dimX)
 
 
+def _moments_opts(posterior):
+    """posterior = True | dict(first=0, thin=1, pooled=False) -> sbtv_moments_opts (first = 0: the entry point's default,
+    burnIn for SAPG, 1 for MYULA)."""
+    p = {} if posterior is True else dict(posterior)
+    unknown = set(p) - {"first", "thin", "pooled"}
+    if unknown:
+        raise ValueError(f"posterior: unknown keys {sorted(unknown)}")
+    mo = L.sbtv_moments_opts()
+    mo.first = int(p.get("first", 0))
+    mo.thin = int(p.get("thin", 1))
+    mo.pooled = 1 if p.get("pooled", False) else 0
+    return mo
+
+
+def _moment_buffers(like, n):
+    """mean / var outputs for n images in the memory kind of `like` (an L.Images), and the host count array."""
+    if like.torch:
+        import torch
+        mk = lambda: L.Images(torch.empty((n, like.N, like.M), dtype=torch.float64, device=like.t.device).permute(0, 2, 1),
+                              _fresh=True)
+    else:
+        mk = lambda: L.Images(np.zeros((n, like.M, like.N)))
+    return mk(), mk(), np.zeros(n, dtype=np.int64)
+
+
+def combine_moments(parts):
+    """(count, mean, var) of the union of sample sets given as (count, mean, var) triples (var = M2 / (count-1), the
+    unbiased form of sbtv_SAPG_algorithm_moments; 0 for count 1): Chan's pairwise combination in the order given,
+    n = na + nb, d = mean_b - mean_a, mean = mean_a + d nb / n, M2 = M2_a + M2_b + d^2 na nb / n.  For chains spread over
+    processes (sbtv.dist.split_chains) or calls; pure NumPy.  The moments' pooled = 1 forms its set the same way."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_moments: no parts")
+    n0, mean, var = parts[0]
+    na = float(n0)
+    mu = np.array(mean, dtype=np.float64)
+    m2 = np.array(var, dtype=np.float64) * (na - 1.0) if na > 1 else np.zeros_like(mu)
+    for nb, mb, vb in parts[1:]:
+        nb = float(nb)
+        mb = np.asarray(mb, dtype=np.float64)
+        sb = np.asarray(vb, dtype=np.float64) * (nb - 1.0) if nb > 1 else np.zeros_like(mb)
+        nt = na + nb
+        d = mb - mu
+        mu = mu + d * (nb / nt)
+        m2 = (m2 + sb) + d * d * (na * nb / nt)
+        na = nt
+    var_out = m2 / (na - 1.0) if na > 1 else np.zeros_like(mu)
+    return int(na), mu, var_out
+
+
 def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=None, ctx=None, reduce_dev_fn=None,
-          host_loop=False):
+          host_loop=False, posterior=None):
     """reduce_fn(user, buf, n): host all-reduce of the shared-gradient sums (selects the host-side parameter loop);
     reduce_dev_fn(user, dev_ptr, n, stream): in-stream all-reduce on the device buffer (`dist.make_device_allreduce_fn`),
-    the loop stays device-resident; host_loop=True forces the host-side loop (SBTV_SAPG_HOST_LOOP)."""
+    the loop stays device-resident; host_loop=True forces the host-side loop (SBTV_SAPG_HOST_LOOP).
+    posterior = True | dict(first, thin, pooled): also the posterior mean / variance of the samples
+    (sbtv_SAPG_algorithm_moments), returned as results['posteriormean'], ['posteriorvar'], ['posterior_count']."""
     if reduce_fn is not None and reduce_dev_fn is not None:
         raise ValueError("give reduce_fn or reduce_dev_fn, not both")
     ctx = ctx or L.default_context()
@@ -161,6 +213,9 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
             xl = L.Images(torch.empty((nch, N, M), dtype=torch.float64, device=yi.t.device).permute(0, 2, 1))
         else:
             xl = L.Images(np.zeros((nch, M, N)))
+    if posterior is not None and posterior is not False and getattr(ctx, "is_group", False):
+        raise NotImplementedError("posterior moments over a sbtv.Group: run the shards' chains per call and "
+                                  "sbtv.combine_moments their results")
     if getattr(ctx, "is_group", False):
         # several GPUs behind this process (sbtv.Group): images / chains dealt to the devices in contiguous blocks; with
         # share_gradients the six gradient sums are exchanged in-process, in-stream (no reduce_fn needed or accepted)
@@ -171,6 +226,13 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
         ctx.check(ctx.lib.sbtv_SAPG_algorithm_sharded(ctx.h, yptr, M, N, nch, C.byref(o), x0i.ptr if x0i else None, nz_ptr,
                                                       vp(thetas), vp(ps), vp(sigmas), vp(logpi), vp(logpi_wu), vp(gx),
                                                       vp(grads), vp(eb), xl.ptr))
+    elif posterior is not None and posterior is not False:
+        mo = _moments_opts(posterior)
+        pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else nch)
+        ctx.check(ctx.lib.sbtv_SAPG_algorithm_moments(ctx.h, yptr, M, N, nch, C.byref(o), x0i.ptr if x0i else None, nz_ptr,
+                                                      vp(thetas), vp(ps), vp(sigmas), vp(logpi), vp(logpi_wu), vp(gx),
+                                                      vp(grads), vp(eb), xl.ptr, cb, None, C.byref(mo), pm.ptr, pv.ptr,
+                                                      vp(pc), yi.flags | xflags), yi.flags)
     else:
         ctx.check(ctx.lib.sbtv_SAPG_algorithm(ctx.h, yptr, M, N, nch, C.byref(o), x0i.ptr if x0i else None, nz_ptr,
                                               vp(thetas), vp(ps), vp(sigmas), vp(logpi), vp(logpi_wu), vp(gx), vp(grads),
@@ -199,6 +261,15 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
             results[b][tolkey] = t
         results[b]["err_psf"] = _err_psf(kind, o.psf_size, ps[b, :len(names)], [o.p_true[q] for q in range(len(names))],
                                          o.phi)
+    if posterior is not None and posterior is not False:
+        # results.posteriormean / results.posteriorvar of SAPG_algorithm_Guassian.m:292-293 (pooled: the same set in every
+        # chain's results)
+        ms, vs = L.images_result(pm, False), L.images_result(pv, False)
+        for b in range(nch):
+            q = 0 if mo.pooled else b
+            results[b]["posteriormean"] = ms[q]
+            results[b]["posteriorvar"] = vs[q]
+            results[b]["posterior_count"] = int(pc[q])
     return results
 
 
@@ -301,3 +372,43 @@ def myula(op, im=None, noise=None, ctx=None):
                                  int(_get(op, "chain_offset", 0)), nz_ptr, xo.ptr, yi.flags), yi.flags)
     y = _get(op, "y")
     return L.images_result(xo, (y.dim() == 2) if yi.torch else yi.squeeze)
+
+
+def myula_moments(op, im=None, noise=None, posterior=True, ctx=None):
+    """myula (SALSA/myula.m) with the posterior mean / variance of its samples (sbtv_myula_moments):
+    dict(x = last sample, mean, var, count).  posterior = True | dict(first=1, thin=1, pooled=False); iteration 1 is y,
+    iteration ii the sample of step ii (ii = 2..samples-1).  Other arguments as for sbtv.myula."""
+    ctx = ctx or L.default_context()
+    A = _get(op, "A")
+    if not isinstance(A, BlurOperator):
+        raise TypeError("op.A must be the sbtv.BlurOperator the closures op.gradF / op.proxG are built from")
+    yi = L.Images(_get(op, "y"))
+    B, M, N = yi.B, yi.M, yi.N
+    s2 = _get(op, "sigma2")
+    if s2 is None:
+        s2 = np.asarray(_get(op, "sigma"), dtype=np.float64) ** 2
+    keep = [L.dvec(_get(op, "theta_op"), B), L.dvec(s2, B)]
+    taps = A._cm(B)
+    xo = L.empty_like_images(yi)
+    nz_ptr, nz_keep = None, None
+    if noise is not None:
+        if L._is_torch(noise):
+            nz_keep, nz_ptr = noise, C.c_void_p(noise.data_ptr())
+        else:
+            a = np.asarray(noise, dtype=np.float64)
+            if a.ndim == 3:
+                a = a[:, None]
+            nz_keep = L.column_major_images(a.reshape((-1,) + a.shape[2:])).reshape(a.shape[:2] + (a.shape[3], a.shape[2]))
+            nz_ptr = L.vptr(nz_keep)
+    mo = _moments_opts(posterior)
+    pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else B)
+    ctx.check(ctx.lib.sbtv_myula_moments(ctx.h, yi.ptr, M, N, B, L.vptr(taps), A.taille,
+                                         float(_get(op, "lambda")), float(_get(op, "gamma")), keep[0][1], keep[1][1],
+                                         int(_get(op, "samples")), int(_get(op, "chambolleit", 25)),
+                                         int(_get(op, "seed", 1)), int(_get(op, "chain_offset", 0)), nz_ptr, xo.ptr,
+                                         C.byref(mo), pm.ptr, pv.ptr, L.vptr(pc), yi.flags), yi.flags)
+    y = _get(op, "y")
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    one = sq and not mo.pooled
+    return dict(x=L.images_result(xo, sq), mean=L.images_result(pm, one or mo.pooled),
+                var=L.images_result(pv, one or mo.pooled), count=int(pc[0]) if (one or mo.pooled) else pc.copy())

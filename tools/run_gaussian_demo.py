@@ -3,7 +3,11 @@
 observation model -> evMax -> SAPG (MYULA) estimates of theta, PSF parameters, sigma^2 -> SALSA_v2 MAP image.
 
   python tools/run_gaussian_demo.py [--kind gaussian|moffat|laplace] [--samples 20000 --warmup 15000]
-                                    [--image tests/golden/wheel_512.npy]
+                                    [--image tests/golden/wheel_512.npy] [--posterior] [--out DIR]
+
+--posterior also accumulates the posterior mean (MMSE image) and variance of the MYULA samples from burnIn on
+(sbtv_SAPG_algorithm_moments; the reference's commented-out `weldford` block, SAPG_algorithm_Guassian.m:233-246 and its
+figure, run_Gaussian_demo.m:291-295) and, with --out, writes them next to the MAP image.
 
 The default image is the one the three demos load: images/wheel.png (entry 8 of the directory listing,
 run_Gaussian_demo.m:100,117; run_moffat_demo.m:108,116; run_laplace_demo.m:83,90).
@@ -40,6 +44,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=15000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default="", help="directory for the results .npz, the trace figure (SVG) and the images (PGM)")
+    ap.add_argument("--posterior", action="store_true", help="posterior mean / std of the samples from burnIn on")
     a = ap.parse_args()
     d = DEMO[a.kind]
     x = np.load(a.image).astype(np.float64)
@@ -67,9 +72,13 @@ def main():
           "laplace": sbtv.SAPG_algorithm_laplace}[a.kind]
     yd = sbtv.to_device(st["y"])
     t0 = time.perf_counter()
-    out = fn(yd, op, c)
+    out = fn(yd, op, c, posterior=True) if a.posterior else fn(yd, op, c)
     t_sapg = time.perf_counter() - t0
     theta_EB, sigma_EB, res = out[0], out[-2], out[-1]
+    if a.posterior:
+        res["posteriormean"], res["posteriorvar"] = sbtv.to_host(res["posteriormean"]), sbtv.to_host(res["posteriorvar"])
+        print(f"posterior: {res['posterior_count']} samples, MMSE PSNR = {sbtv.PSNR(x, res['posteriormean']):.3f} dB, "
+              f"mean std = {np.sqrt(res['posteriorvar']).mean():.4f}")
     p_EB = [res[nm + "_EB"] for nm in d["names"]]
     print(f"SAPG: {a.warmup} warm-up + {a.samples} iterations in {t_sapg:.2f} s "
           f"({1e3 * t_sapg / (a.warmup + a.samples):.3f} ms/iteration)")
@@ -100,6 +109,9 @@ def main():
         sbtv.plot_traces(os.path.join(a.out, f"{a.kind}_traces.svg"), res, true_values=true)
         for nm, img in (("x", x), ("y", st["y"]), ("xMAP", xm)):
             sbtv.save_image(os.path.join(a.out, f"{a.kind}_{nm}.pgm"), img, 0.0, 255.0)
+        if a.posterior:            # run_Gaussian_demo.m:291-295 (commented out there): posterior mean and std
+            sbtv.save_image(os.path.join(a.out, f"{a.kind}_posteriormean.pgm"), res["posteriormean"], 0.0, 255.0)
+            sbtv.save_image(os.path.join(a.out, f"{a.kind}_posteriorstd.pgm"), np.sqrt(res["posteriorvar"]))
         print("wrote results, traces and images to", a.out)
 
 
