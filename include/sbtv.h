@@ -465,8 +465,9 @@ int sbtv_CoRAL_v2_sharded(sbtv_group *g, const double *y, int M, int N, int n_it
  *   host -> device, seconds, bytes device -> host, seconds}.  Arrays of >= 4 MB passed with SBTV_HOST_PTRS move through
  *   four copy lanes (pinned chunks, own streams, SBTV_STAGE_THREADS = 0..4); smaller ones through a plain hipMemcpyAsync.
  * sbtv_diag_prox_variant: which TV-prox kernel a (M, N, batch) problem takes: out = {columns per wave, waves per
- *   workgroup, waves per SIMD requested, rows per lane, tiles per image, 2 = streaming pipeline kernel / 1 = temporally
- *   fused tile kernel / 0 = the one-iteration kernels (odd M, SBTV_SINGLE_STEP)} — lets a parity test assert which kernel it exercised.
+ *   workgroup, waves per SIMD requested, rows per lane, tiles per image, 1 = temporally fused tile kernel / 0 = the
+ *   one-iteration kernels (odd M, SBTV_SINGLE_STEP)} — lets a parity test assert which kernel it exercised.  (Value 2,
+ *   the retired streaming pipeline kernel, is no longer returned.)
  * sbtv_diag_time_pass: times ONE pass of the hot path on scratch data of the given shape with HIP events on the
  *   context stream (`reps` launches after two untimed ones) -> average ms per launch and the algorithmic bytes of one
  *   launch.  pass: 0 forward column FFT of u+bu; 1 row pass with the SALSA spectral solve (forward FFT, operator,

@@ -501,7 +501,6 @@ struct RowsParams {
     int shared_spec;        // 1: H / Y / D1 / D2 hold ONE spectrum shared by every image of the batch
     int fold;               // pipelined row kernel: > 0 = the batch folded into grid.x (see the kernel), else 0
     size_t u_img;           // elements of one operator spectrum per image
-    int u_ld;               // leading dimension of the row-major operator spectra (tiled mode)
     int u_tiled;            // operator spectra in the tiled layout U[(l/4)][k][l%4], k = 0..n1
 };
 
@@ -573,10 +572,9 @@ __device__ __forceinline__ double2 spec_apply_cs(double2 V, double2 H, double2 Y
     return Xh;
 }
 
-// TILED: S is in the tiled layout (a workgroup's RK rows x 4 columns are then 64 RK contiguous bytes) and the operator
-// spectra are row-major U[k][l] (fft_wave.inc); otherwise S[l][k] and U[l][k].
-template <int LOG2N, int RK, int OP, bool TILED = false>
-__global__ __launch_bounds__(RK *((1 << LOG2N) / 8), (TILED && RK == 2) ? 4 : 1) void fft_rows_kernel(RowsParams p) {
+// S[l][k] and U[l][k] (the tiled layout of the wave mode has its own row kernel, rows_pipe_kernel in fft_wave.inc)
+template <int LOG2N, int RK, int OP>
+__global__ __launch_bounds__(RK *((1 << LOG2N) / 8), 1) void fft_rows_kernel(RowsParams p) {
     constexpr int N = 1 << LOG2N, T = N / 8;
     constexpr int LDSI = RK * N;
     constexpr int LDSN = LDSI + ((LDSI >> 5) << 2) + 8;
@@ -600,8 +598,9 @@ __global__ __launch_bounds__(RK *((1 << LOG2N) / 8), (TILED && RK == 2) ? 4 : 1)
     const double2 *__restrict__ in = p.Sin + ibase;
     RowsX<RK> X{lds, LDSN, q};
     double2 v[8];
-    auto sidx = [&](int l) -> size_t { return TILED ? s_tiled(k, l, n1) : (size_t)l * n1 + k; };
-    auto uidx = [&](int kk, int l) -> size_t { return (TILED && p.u_tiled) ? u_tiled(kk, l, n1) : (size_t)l * (n1 + 1) + kk; };
+    auto sidx = [&](int l) -> size_t { return (size_t)l * n1 + k; };
+    // (p.n1 = n1; reading it through p keeps the generated code of the measured kernel)
+    auto uidx = [&](int kk, int l) -> size_t { return (size_t)l * (p.n1 + 1) + kk; };
 #pragma unroll
     for (int s = 0; s < 8; ++s) v[s] = in[sidx(t + s * T)];
     // Small workgroups (<= 256 threads: images up to 512^2 and the RK = 1 / 2 variants) have registers to spare and are
@@ -833,7 +832,7 @@ __global__ __launch_bounds__(64) void psf_spectrum_kernel(PsfSets ps, int taille
     // tiled layout U[(l/4)][k][l%4]: four lanes share one k and own the four slots of a 64-byte piece, so that a wave's
     // store is one contiguous kilobyte (one k per lane left every store instruction with 16 bytes in each of 64 lines:
     // 2.8 TB/s on the 134 MB the SAPG loop writes per iteration)
-    const int k = (tiled == 1) ? blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2) : blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = tiled ? blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2) : blockIdx.x * blockDim.x + threadIdx.x;
     if (k > n1) return;
     const double *h = taps + (size_t)b * taille * taille;
     double2 c[TN];
@@ -854,7 +853,7 @@ __global__ __launch_bounds__(64) void psf_spectrum_kernel(PsfSets ps, int taille
         c[nn] = cc;
     }
     double2 *ub = U + (size_t)b * (n1 + 1) * N;
-    if (tiled == 1) {
+    if (tiled) {
         const int c4 = threadIdx.x & 3;
         const int t0 = blockIdx.y * lch, t1 = min(t0 + lch, N >> 2);
         for (int lt = t0; lt < t1; ++lt) {
@@ -873,14 +872,11 @@ __global__ __launch_bounds__(64) void psf_spectrum_kernel(PsfSets ps, int taille
 #pragma unroll
         for (int nn = 0; nn < TN; ++nn)
             if (TT || nn < taille) acc = cadd(acc, cmul(c[nn], tw_N[(l * nn) & (N - 1)]));
-        ub[tiled ? ((size_t)(l >> 2) * (n1 + 1) + k) * 4 + (l & 3) : (size_t)l * (n1 + 1) + k] = acc;
+        ub[(size_t)l * (n1 + 1) + k] = acc;
     }
 }
 
 #include "fft_wave.inc"
-#ifdef SBTV_LAB
-#include "fft_rows_sub.inc"
-#endif
 #include "fft_any.inc"
 
 // ---------------------------------------------------------------------------
@@ -895,83 +891,6 @@ static inline bool wave_enabled() {
     }();
     return on;
 }
-// row pass of the tiled sizes: the wave-granular kernel (SBTV_ROWS_KERNEL=wave) or the workgroup kernel (default: in
-// the solver loops, where H / Y come from HBM, it is the faster one - profiles/r02_fft_insitu.md)
-// (lab build only: it lost in the loop, profiles/r02_fft_lab.md; the default library does not carry the kernel)
-static inline bool rows_wave() {
-#ifdef SBTV_LAB
-    static const bool on = [] {
-        const char *e = getenv("SBTV_ROWS_KERNEL");
-        return e && e[0] == 'w' && e[1] == 'a';
-    }();
-    return on;
-#else
-    return false;
-#endif
-}
-// lab build, SBTV_ROWS_SUB=1: the row pass of the wave-granular sizes as four wave-local sub-transforms per row
-// (rows_sub_kernel, fft_rows_sub.inc; operator spectra sub-row-major).  Round 3's fourth structural attempt on this pass: it
-// ties with the software-pipelined kernel on every loop (profiles/r03_rows_sub_ab.md), so the default library keeps that one
-static inline bool rows_sub() {
-#ifdef SBTV_LAB
-    static const bool on = [] {
-        const char *e = getenv("SBTV_ROWS_SUB");
-        return e && e[0] == '1';
-    }();
-    return on && !rows_wave();
-#else
-    return false;
-#endif
-}
-// operator spectra tiled like S (default) or column-major U[l][k] (SBTV_U_TILED=0, the round-1 layout) in the wave mode
-static inline bool u_tiled_wanted() {
-#ifdef SBTV_LAB
-    static const bool on = [] {
-        const char *e = getenv("SBTV_U_TILED");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-#else
-    return true;
-#endif
-}
-// software-pipelined row pass (rows_pipe_kernel) for the sizes of the wave mode; SBTV_ROWS_PIPE=0: the workgroup row
-// kernel on the tiled layout instead (A/B runs: profiles/r02_rows_pipe.md)
-static inline bool rows_pipe(int log2n) {
-    (void)log2n;
-#ifdef SBTV_LAB
-    static const bool on = [] {
-        const char *e = getenv("SBTV_ROWS_PIPE");
-        return !(e && (e[0] == '0' || e[0] == '2'));
-    }();
-    return on;
-#else
-    return true;
-#endif
-}
-// lab: SBTV_ROWS_PIPE=2 = the workgroup row kernel with TWO rows per 512-thread workgroup on the tiled layout (74 KB of LDS,
-// no operand prefetch: two workgroups fit a CU) - round 3's "two independent workgroups per CU" experiment
-static inline int rows_wg_rk() {
-#ifdef SBTV_LAB
-    static const int rk = [] {
-        const char *e = getenv("SBTV_ROWS_PIPE");
-        return (e && e[0] == '2') ? 2 : 4;
-    }();
-    return rk;
-#else
-    return 4;
-#endif
-}
-#ifdef SBTV_LAB
-static inline int rows_v(int dflt) {     // values per thread of the wave-granular row pass (tuning hook: SBTV_ROWS_V=8|16)
-    static const int v = [] {
-        const char *e = getenv("SBTV_ROWS_V");
-        return e ? atoi(e) : 0;
-    }();
-    return (v == 8 || v == 16) ? v : dflt;
-}
-#endif
-
 int fft_plan(sbtv_ctx *ctx, int M, int N, int batch, FftPlan *pl) {
     if (M < 2 || N < 2 || M > 4096 || N > 4096)
         return fail(ctx, SBTV_ERR_SIZE, "blur operator: 2 <= M, N <= 4096");
@@ -983,7 +902,6 @@ int fft_plan(sbtv_ctx *ctx, int M, int N, int batch, FftPlan *pl) {
         pl->generic = 1;
         pl->wave = 0;
         pl->n1 = M;                       // so that 1 / (n1 N) is the inverse scale and S has n1 x N entries
-        pl->u_ld = 0;
         pl->u_tiled = 0;
         pl->s_img = pl->u_img = (size_t)M * N;
         pl->tw_n1 = nullptr;
@@ -995,11 +913,9 @@ int fft_plan(sbtv_ctx *ctx, int M, int N, int batch, FftPlan *pl) {
     pl->n1 = M / 2;
     pl->s_img = (size_t)pl->n1 * N;
     pl->wave = (wave_enabled() && (M == 1024 || M == 2048) && (N == 1024 || N == 2048)) ? 1 : 0;
-    // operator spectra: row-major U[k][l] with a padded leading dimension for the wave-granular row kernel, the
-    // column-major U[l][k] (leading dimension M/2 + 1, u_ld = 0) otherwise
-    pl->u_ld = (pl->wave && rows_wave()) ? N + 16 : 0;
-    pl->u_tiled = (pl->wave && rows_sub()) ? 2 : ((pl->wave && !rows_wave() && u_tiled_wanted()) ? 1 : 0);   // 2: U[k][l%4][l/4]
-    pl->u_img = pl->u_ld ? (size_t)(pl->n1 + 1) * pl->u_ld : (size_t)(pl->n1 + 1) * N;
+    // operator spectra: tiled like S in the wave mode, column-major U[l][k] (leading dimension M/2 + 1) otherwise
+    pl->u_tiled = pl->wave;
+    pl->u_img = (size_t)(pl->n1 + 1) * N;
     SBTV_TRY(twiddle_get(ctx, pl->n1, &pl->tw_n1));
     SBTV_TRY(twiddle_get(ctx, M, &pl->tw_M));
     SBTV_TRY(twiddle_get(ctx, N, &pl->tw_N));
@@ -1213,57 +1129,22 @@ int fft_cols_inv_post(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double
     return 0;
 }
 
-// rows per workgroup of the row pass: 4 (64-byte segments) from N = 512 on, 8 below; N = 2048 may use
-// 2 (SBTV_ROWS_RK=2: 512-thread workgroups, two per CU so load / FFT / store phases overlap)
+// rows per workgroup of the row pass: 4 (64-byte segments) from N = 512 on, 8 below
 static inline int rows_rk(const FftPlan &pl) {
-#ifdef SBTV_LAB
-    static const int rk2048 = [] {
-        const char *e = getenv("SBTV_ROWS_RK");
-        return (e && atoi(e) == 2) ? 2 : 4;
-    }();
-#else
-    const int rk2048 = 4;
-#endif
     const int N = pl.N;
     if (N == 4096) return 2;                 // two 4096-point rows fill the LDS exchange buffer (128 KB)
-    if (N == 2048) return rk2048;
     const int rk = (N >= 512) ? 4 : 8;
     // small images: fewer rows per workgroup (more workgroups) when the grid of ONE image would leave most CUs
     // idle; a function of the image size only (see cols_nseq)
     const int small = (N == 512) ? 1 : (N == 256) ? 2 : rk;
     return (pl.n1 / rk < 128) ? small : rk;
 }
-bool fft_rows_csalsa_ok(const FftPlan &pl) {
-    if (pl.generic) return false;
-#ifdef SBTV_LAB
-    if (pl.wave && rows_wave()) return false;   // the lab's wave-granular row kernel does not carry it
-#endif
-    return true;
-}
+bool fft_rows_csalsa_ok(const FftPlan &pl) { return !pl.generic; }
 int fft_rows_blocks(const FftPlan &pl) {
     if (pl.generic) return ANY_SPEC_BLOCKS;
-    if (pl.wave) return (rows_wave() || rows_sub()) ? pl.n1 / 2 : (rows_pipe(0) ? pl.n1 / 4 : pl.n1 / rows_wg_rk());
+    if (pl.wave) return pl.n1 / 4;
     return pl.n1 / rows_rk(pl);
 }
-
-#ifdef SBTV_LAB
-template <int L, int V>
-static void launch_rows_wave(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p) {
-    const dim3 grid(pl.n1 / 2, pl.batch), block(2 * ((1 << L) / V));
-    switch (p.op) {
-        case OP_NONE: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_NONE>), grid, block, 0, ctx->stream, p); break;
-        case OP_MUL_H: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_MUL_H>), grid, block, 0, ctx->stream, p); break;
-        case OP_MUL_HC: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_MUL_HC>), grid, block, 0, ctx->stream, p); break;
-        case OP_INVLS: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_INVLS>), grid, block, 0, ctx->stream, p); break;
-        case OP_SALSA: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_SALSA>), grid, block, 0, ctx->stream, p); break;
-        case OP_RESID: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_RESID>), grid, block, 0, ctx->stream, p); break;
-        case OP_GRAD: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_GRAD>), grid, block, 0, ctx->stream, p); break;
-        case OP_ATA: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_ATA>), grid, block, 0, ctx->stream, p); break;
-        case OP_GRADF: hipLaunchKernelGGL((rows_wave_kernel<L, V, OP_GRADF>), grid, block, 0, ctx->stream, p); break;
-        default: break;
-    }
-}
-#endif
 
 template <int L>
 static void launch_rows_pipe(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p0) {
@@ -1295,34 +1176,11 @@ static void launch_rows_pipe(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams 
 #undef SBTV_ROWS_OP
 }
 
-#ifdef SBTV_LAB
-template <int L>
-static void launch_rows_sub(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p) {
-    const dim3 grid(pl.n1 / 2, pl.batch), block((1 << L) / 4);
-#define SBTV_ROWS_OP(OP_)                                                                                     \
-    case OP_: hipLaunchKernelGGL((rows_sub_kernel<L, OP_>), grid, block, 0, ctx->stream, p); break;
-    switch (p.op) {
-        SBTV_ROWS_OP(OP_NONE)
-        SBTV_ROWS_OP(OP_MUL_H)
-        SBTV_ROWS_OP(OP_MUL_HC)
-        SBTV_ROWS_OP(OP_INVLS)
-        SBTV_ROWS_OP(OP_SALSA)
-        SBTV_ROWS_OP(OP_RESID)
-        SBTV_ROWS_OP(OP_GRAD)
-        SBTV_ROWS_OP(OP_ATA)
-        SBTV_ROWS_OP(OP_GRADF)
-        SBTV_ROWS_OP(OP_CSALSA)
-        default: break;
-    }
-#undef SBTV_ROWS_OP
-}
-#endif
-
-template <int L, int RK, bool TILED = false>
+template <int L, int RK>
 static void launch_rows(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p) {
     const dim3 grid(pl.n1 / RK, pl.batch), block(RK * ((1 << L) / 8));
 #define SBTV_ROWS_OP(OP_)                                                                                     \
-    case OP_: hipLaunchKernelGGL((fft_rows_kernel<L, RK, OP_, TILED>), grid, block, 0, ctx->stream, p); break;
+    case OP_: hipLaunchKernelGGL((fft_rows_kernel<L, RK, OP_>), grid, block, 0, ctx->stream, p); break;
     switch (p.op) {
         SBTV_ROWS_OP(OP_NONE)
         SBTV_ROWS_OP(OP_MUL_H)
@@ -1360,54 +1218,18 @@ int fft_rows(sbtv_ctx *ctx, const FftPlan &pl, const double2 *Sin, double2 *Sout
     p.shared_spec = a.shared_spec;
     p.fold = 0;
     p.u_img = pl.u_img;
-    p.u_ld = pl.u_ld;
     p.u_tiled = pl.u_tiled;
     if (a.op == OP_CSALSA && !fft_rows_csalsa_ok(pl)) return fail(ctx, SBTV_ERR_SIZE, "row pass: OP_CSALSA is not built for this plan");
     if (pl.generic) return any_rows(ctx, pl, p, Sout);
     const int L = ilog2(pl.N);
     if (L > 12) return fail(ctx, SBTV_ERR_SIZE, "row FFT: N must be <= 4096");
-#ifdef SBTV_LAB
-    if (pl.wave && rows_sub()) {
-        if (L == 11) launch_rows_sub<11>(ctx, pl, p);
-        else launch_rows_sub<10>(ctx, pl, p);
-        SBTV_HIP(ctx, hipGetLastError());
-        return 0;
-    }
-#endif
-    if (pl.wave && !rows_wave()) {
-        if (rows_pipe(L)) {
-            // software-pipelined row pass (two row pairs per workgroup, loads in flight across the arithmetic)
-            if (L == 11) launch_rows_pipe<11>(ctx, pl, p);
-            else launch_rows_pipe<10>(ctx, pl, p);
-            SBTV_HIP(ctx, hipGetLastError());
-            return 0;
-        }
-#ifdef SBTV_LAB
-        // the workgroup row kernel on the tiled layout: 4 rows x 4 columns = 256 contiguous bytes per access
-        if (rows_wg_rk() == 2) {
-            if (L == 11) launch_rows<11, 2, true>(ctx, pl, p);
-            else launch_rows<10, 2, true>(ctx, pl, p);
-        } else if (L == 11) launch_rows<11, 4, true>(ctx, pl, p);
-        else launch_rows<10, 4, true>(ctx, pl, p);
-        SBTV_HIP(ctx, hipGetLastError());
-        return 0;
-#endif
-    }
-#ifdef SBTV_LAB
     if (pl.wave) {
-        // values per thread: 16 (radix-16 stages) at N = 2048, 8 at N = 1024 (measured: profiles/r02_fft_lab.md)
-        const int V = rows_v(L == 11 ? 16 : 8);
-        if (L == 11) {
-            if (V == 8) launch_rows_wave<11, 8>(ctx, pl, p);
-            else launch_rows_wave<11, 16>(ctx, pl, p);
-        } else {
-            if (V == 8) launch_rows_wave<10, 8>(ctx, pl, p);
-            else launch_rows_wave<10, 16>(ctx, pl, p);
-        }
+        // software-pipelined row pass (two row pairs per workgroup, loads in flight across the arithmetic)
+        if (L == 11) launch_rows_pipe<11>(ctx, pl, p);
+        else launch_rows_pipe<10>(ctx, pl, p);
         SBTV_HIP(ctx, hipGetLastError());
         return 0;
     }
-#endif
     if (pl.N >= 512) {
         switch (L) {
             case 9:
@@ -1415,13 +1237,7 @@ int fft_rows(sbtv_ctx *ctx, const FftPlan &pl, const double2 *Sin, double2 *Sout
                 else launch_rows<9, 4>(ctx, pl, p);
                 break;
             case 10: launch_rows<10, 4>(ctx, pl, p); break;
-            case 11:
-#ifdef SBTV_LAB
-                if (rows_rk(pl) == 2) launch_rows<11, 2>(ctx, pl, p);
-                else
-#endif
-                    launch_rows<11, 4>(ctx, pl, p);
-                break;
+            case 11: launch_rows<11, 4>(ctx, pl, p); break;
             case 12: launch_rows<12, 2>(ctx, pl, p); break;
             default: break;
         }
@@ -1449,7 +1265,7 @@ int spec_unpack(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double2 *U) 
     }
     if (pl.wave) {
         hipLaunchKernelGGL(spec_unpack_tiled_kernel, dim3((pl.N + 63) / 64, pl.n1 + 1, pl.batch), dim3(64), 0,
-                           ctx->stream, S, U, pl.n1, pl.N, pl.u_ld, pl.u_tiled);
+                           ctx->stream, S, U, pl.n1, pl.N, pl.u_tiled);
         SBTV_HIP(ctx, hipGetLastError());
         return 0;
     }
@@ -1460,7 +1276,7 @@ int spec_unpack(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double2 *U) 
     return 0;
 }
 
-// spectra of `nsets` (<= 3) tap sets of the same size: one launch on the default layouts, else one call per set
+// spectra of `nsets` (<= 3) tap sets of the same size: one launch (the arbitrary-size path: one call per set)
 int psf_spectrum_sets(sbtv_ctx *ctx, const FftPlan &pl, const double *const *taps_dev, int taille, double2 *const *U, int nsets) {
     const int thr = 64;
     if (taille > PSF_TMAX) return fail(ctx, SBTV_ERR_PSF, "PSF larger than 15 x 15");
@@ -1472,26 +1288,13 @@ int psf_spectrum_sets(sbtv_ctx *ctx, const FftPlan &pl, const double *const *tap
     const size_t elems = (size_t)(pl.n1 + 1) * pl.N * pl.batch;
     int lch = (int)(elems >> 19);                       // 512^2, 1024^2: 1;  2048^2: 4;  8 x 1024^2: 8
     lch = lch < 1 ? 1 : (lch > 16 ? 16 : lch);
-    if (pl.u_ld || pl.u_tiled == 2) {
-        const dim3 gridw((pl.N + thr - 1) / thr, (pl.n1 + 1 + lch - 1) / lch, pl.batch);
-        for (int q = 0; q < nsets; ++q) {
-            if (taille == 7)
-                hipLaunchKernelGGL(psf_spectrum_rowmajor_kernel<7>, gridw, dim3(thr), 0, ctx->stream, taps_dev[q], taille, U[q],
-                                   pl.n1, pl.M, pl.N, pl.tw_M, pl.tw_N, lch, pl.u_ld ? pl.u_ld : pl.N, pl.u_tiled == 2);
-            else
-                hipLaunchKernelGGL(psf_spectrum_rowmajor_kernel<0>, gridw, dim3(thr), 0, ctx->stream, taps_dev[q], taille, U[q],
-                                   pl.n1, pl.M, pl.N, pl.tw_M, pl.tw_N, lch, pl.u_ld ? pl.u_ld : pl.N, pl.u_tiled == 2);
-        }
-        SBTV_HIP(ctx, hipGetLastError());
-        return 0;
-    }
     PsfSets ps{};
     for (int q = 0; q < 3; ++q) {
         ps.taps[q] = taps_dev[q < nsets ? q : 0];
         ps.U[q] = U[q < nsets ? q : 0];
     }
-    const dim3 grid = (pl.u_tiled == 1) ? dim3(((pl.n1 + 1) * 4 + thr - 1) / thr, ((pl.N >> 2) + lch - 1) / lch, pl.batch * nsets)
-                                        : dim3((pl.n1 + 1 + thr - 1) / thr, (pl.N + lch - 1) / lch, pl.batch * nsets);
+    const dim3 grid = pl.u_tiled ? dim3(((pl.n1 + 1) * 4 + thr - 1) / thr, ((pl.N >> 2) + lch - 1) / lch, pl.batch * nsets)
+                                 : dim3((pl.n1 + 1 + thr - 1) / thr, (pl.N + lch - 1) / lch, pl.batch * nsets);
     if (taille == 7)
         hipLaunchKernelGGL(psf_spectrum_kernel<7>, grid, dim3(thr), 0, ctx->stream, ps, taille, pl.batch, pl.n1, pl.M, pl.N,
                            pl.tw_M, pl.tw_N, lch, pl.u_tiled);

@@ -7,17 +7,16 @@
 //   columns : ONE WAVE per column (n1 = M/2 complex points = 64 lanes x V values, V = 16 or 8).  All inter-stage
 //             exchanges are wave-local LDS round trips (no workgroup barrier); four waves share a workgroup only to
 //             transpose their results through LDS into the tiled spectrum layout (one barrier).
-//   rows    : one row per T = N/16 threads (two waves at N = 2048, one at N = 1024), radix-16 stages with 16 values per
-//             thread (3 stages instead of 4 at N = 2048), two adjacent rows per workgroup so that global accesses are
-//             whole 128-byte lines; the H / Y spectra can be fetched before the forward transform (one memory phase).
+//   rows    : a software-pipelined workgroup of 2 rows x N/8 threads that owns two row pairs and keeps their loads in
+//             flight across its arithmetic (rows_pipe_kernel, below).
 // Spectrum layout in this mode ("tiled"): S[(l / 4)][k][l % 4] - 64-byte pieces that both the column side (4 columns
 // of one k) and the row side (2 rows x 4 values = one 128-byte line) move whole.  Operator spectra (H, Y, D1, D2) are
-// row-major U[k][l], k = 0..M/2, so the row pass streams them.
+// tiled the same way, U[(l / 4)][k][l % 4], k = 0..M/2.
 //
 // The 1-D engine is the same mixed-radix Stockham autosort scheme as in fft.hip, generalised to V values per thread
 // and a radix-16 butterfly (two radix-4 layers with the W16 twiddles as constants).
 
-// (TWS, TW and s_tiled() are defined in fft.hip: the workgroup row kernel addresses the tiled layout too)
+// (TWS, TW, s_tiled() and u_tiled() are defined in fft.hip)
 
 // ---- synchronisation policies of the LDS exchanges
 // Wave-local: LDS operations of one wave execute in issue order, so a wave that exchanges data among its own lanes
@@ -505,135 +504,6 @@ __global__ __launch_bounds__(64 * TW, 2) void cols_inv_wave_kernel(const double2
 }
 
 // ---------------------------------------------------------------------------
-// row pass on the tiled layout: forward FFT, spectral operator, inverse FFT.  T = N/V threads per row (V = 16: radix-16
-// stages, 2 waves per row at N = 2048, up to 256 registers; V = 8: radix-8 stages, 4 waves per row, 128 registers),
-// 2 rows per workgroup.  The operator spectra are streamed in chunks of CH values per thread, the loads of chunk c+1
-// in flight while chunk c is applied (requesting all of them up front costs more registers than a wave has).
-// ---------------------------------------------------------------------------
-template <int LOG2N, int V, int OP>
-__global__ __launch_bounds__(2 * ((1 << LOG2N) / V), V == 16 ? 2 : 4) void rows_wave_kernel(RowsParams p) {
-    constexpr int N = 1 << LOG2N, T = N / V, RK = 2, NT = RK * T;
-    constexpr int REG = xseq_elems(N);
-    constexpr bool needY = (OP == OP_SALSA || OP == OP_RESID || OP == OP_GRAD || OP == OP_GRADF);
-    constexpr bool needD = (OP == OP_GRAD);
-    typedef typename std::conditional<(T > 64), SyncBlock, SyncWave>::type SYNC;
-    __shared__ __attribute__((aligned(16))) double2 lds[RK * REG];
-    __shared__ double red[3 * 8];
-    const int b = blockIdx.y;
-    if (p.frozen && p.frozen[b]) return;
-    // row index within the workgroup: wave-uniform (T is a multiple of 64), kept in an SGPR
-    const int r = __builtin_amdgcn_readfirstlane(threadIdx.x / T), t = threadIdx.x - r * T;
-    int kb;
-    {
-        const int nt = gridDim.x, bid = blockIdx.x;
-        const int q8 = nt >> 3, r8 = nt & 7, xx = bid & 7, o = bid >> 3;
-        kb = (xx < r8 ? xx * (q8 + 1) : r8 * (q8 + 1) + (xx - r8) * q8) + o;
-    }
-    const int k = kb * RK + r;
-    const int n1 = p.n1;
-    const size_t ibase = (size_t)b * n1 * N;
-    const double2 *__restrict__ in = p.Sin + ibase;
-    XSeq<SYNC> X{lds + r * REG};
-    double2 v[V];
-#pragma unroll
-    for (int s = 0; s < V; ++s) v[s] = in[s_tiled(k, t + s * T, n1)];
-    if (p.fwd) stages_v<V, LOG2N, 0, false>(v, t, p.tw, X);
-
-    double acc[3] = {0.0, 0.0, 0.0};
-    if constexpr (OP != OP_NONE) {
-        const double mu = p.mu ? p.mu[b] : 0.0;
-        const double2 z = make_double2(0.0, 0.0);
-        const size_t hbase = p.shared_spec ? 0 : (size_t)b * p.u_img;
-        const int uld = p.u_ld;
-        if (kb == 0) {
-            // This workgroup owns the packed row 0 = X[0,:] + i X[M/2,:] (its second row is an ordinary one): un-mix
-            // with the mirrored element, apply the operator rows 0 and M/2, re-mix.  The mirrored partner of every
-            // value is read from LDS one at a time (an array of V more values in registers would set the register
-            // budget of the whole kernel for the sake of this one row).
-            if (r == 0) {
-#pragma unroll
-                for (int s = 0; s < V; ++s) X.buf[XSeq<SYNC>::idx(t + s * T)] = v[s];
-            }
-        }
-        if (kb == 0) {
-            SYNC::sync();
-            if (r == 0) {
-#pragma unroll
-                for (int s = 0; s < V; ++s) {
-                    const int l = t + s * T;
-                    const size_t h0 = hbase + l, hn = hbase + (size_t)n1 * uld + l;
-                    const double2 P = v[s], Q = cconj(X.buf[XSeq<SYNC>::idx((N - l) & (N - 1))]);
-                    const double2 A = cscale(cadd(P, Q), 0.5);
-                    const double2 dB = csub(P, Q);
-                    const double2 B = make_double2(0.5 * dB.y, -0.5 * dB.x);   // (P-Q)/(2i)
-                    const double2 A2 = spec_apply<OP>(A, p.H[h0], needY ? p.Y[h0] : z, needD ? p.D1[h0] : z,
-                                                      needD ? p.D2[h0] : z, mu, 1.0, acc);
-                    const double2 B2 = spec_apply<OP>(B, p.H[hn], needY ? p.Y[hn] : z, needD ? p.D1[hn] : z,
-                                                      needD ? p.D2[hn] : z, mu, 1.0, acc);
-                    v[s] = make_double2(A2.x - B2.y, A2.y + B2.x);             // A' + i B'
-                    if ((s & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            SYNC::sync();        // the inverse transform re-uses the buffer
-        }
-        if (kb != 0 || r != 0) {
-            constexpr int CH = needD ? 2 : 4, NCH = V / CH;
-            const size_t hrow = hbase + (size_t)k * uld + t;
-            double2 hb[2][CH], yb[2][CH], d1b[2][CH], d2b[2][CH];
-            auto fetch = [&](int c, int slot) {
-#pragma unroll
-                for (int q = 0; q < CH; ++q) {
-                    const size_t hi = hrow + (size_t)(c * CH + q) * T;
-                    hb[slot][q] = p.H[hi];
-                    if constexpr (needY) yb[slot][q] = p.Y[hi];
-                    if constexpr (needD) {
-                        d1b[slot][q] = p.D1[hi];
-                        d2b[slot][q] = p.D2[hi];
-                    }
-                }
-            };
-            fetch(0, 0);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                if (c + 1 < NCH) fetch(c + 1, (c + 1) & 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < CH; ++q) {
-                    const int s = c * CH + q;
-                    v[s] = spec_apply<OP>(v[s], hb[c & 1][q], needY ? yb[c & 1][q] : z, needD ? d1b[c & 1][q] : z,
-                                          needD ? d2b[c & 1][q] : z, mu, 2.0, acc);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if constexpr (needY) {
-            // deterministic workgroup reduction of the accumulators (NT / 64 waves)
-            const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-            constexpr int NW = NT / 64;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double a = acc[c];
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-                if (lane == 0) red[c * 8 + w] = a;
-            }
-            __syncthreads();
-            if (threadIdx.x < 3) {
-                double a = 0.0;
-                for (int ww = 0; ww < NW; ++ww) a += red[threadIdx.x * 8 + ww];
-                p.acc[((size_t)b * 3 + threadIdx.x) * gridDim.x + kb] = a;
-            }
-        }
-    }
-    if (p.inv) stages_v<V, LOG2N, 0, true>(v, t, p.tw, X);
-    if (p.Sout) {
-        double2 *__restrict__ out = p.Sout + ibase;
-#pragma unroll
-        for (int s = 0; s < V; ++s) out[s_tiled(k, t + s * T, n1)] = v[s];
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Row pass, software-pipelined (tiled S, column-major operator spectra U[l][k] as in the workgroup row kernel).
 // In the loop a row pass runs as ONE round of workgroups from cold HBM, and a workgroup that loads its rows, transforms,
 // THEN loads H / Y, applies the operator, transforms back and stores pays four memory latencies and two transfer times
@@ -860,15 +730,14 @@ __global__ void s_relayout_kernel(const double2 *__restrict__ in, double2 *__res
     }
 }
 
-// packed tiled S -> operator-spectrum layout of the plan (tiled / row-major U[k][l] / column-major U[l][k]), k = 0..n1
-__global__ void spec_unpack_tiled_kernel(const double2 *__restrict__ S, double2 *__restrict__ U, int n1, int N, int uld,
-                                         int utiled) {
+// packed tiled S -> operator-spectrum layout of the plan (tiled / column-major U[l][k]), k = 0..n1
+__global__ void spec_unpack_tiled_kernel(const double2 *__restrict__ S, double2 *__restrict__ U, int n1, int N, int utiled) {
     const int b = blockIdx.z;
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = blockIdx.y;       // 0..n1
     if (l >= N) return;
     const double2 *s = S + (size_t)b * n1 * N;
-    double2 *u = U + (size_t)b * (n1 + 1) * (uld ? uld : N);
+    double2 *u = U + (size_t)b * (n1 + 1) * N;
     double2 r;
     if (k == 0 || k == n1) {
         const double2 P = s[s_tiled(0, l, n1)];
@@ -882,51 +751,6 @@ __global__ void spec_unpack_tiled_kernel(const double2 *__restrict__ S, double2 
     } else {
         r = s[s_tiled(k, l, n1)];
     }
-    if (utiled == 2) u[((size_t)k * 4 + (l & 3)) * (N >> 2) + (l >> 2)] = r;   // sub-row-major (rows_sub_kernel)
-    else if (utiled) u[u_tiled(k, l, n1)] = r;      // tiled like S (workgroup / pipelined row kernels)
-    else if (uld) u[(size_t)k * uld + l] = r;  // row-major (wave-granular row kernel)
+    if (utiled) u[u_tiled(k, l, n1)] = r;      // tiled like S (pipelined row kernel)
     else u[(size_t)l * (n1 + 1) + k] = r;      // column-major (workgroup row kernel)
-}
-
-// direct DFT of the zero-padded taps into the row-major layout: a thread owns one l, forms its taille row sums
-// d_m(l) = sum_n h[m,n] wN^(l n) once and walks `kch` values of k (same operation count as psf_spectrum_kernel)
-template <int TT>
-__global__ __launch_bounds__(64) void psf_spectrum_rowmajor_kernel(const double *__restrict__ taps, int taille,
-                                                                   double2 *__restrict__ U, int n1, int M, int N,
-                                                                   const double2 *__restrict__ tw_M,
-                                                                   const double2 *__restrict__ tw_N, int kch, int uld,
-                                                                   int subrow) {
-    constexpr int TN = TT ? TT : PSF_TMAX;
-    const int b = blockIdx.z;
-    // subrow: the thread's POSITION in the row is (l % 4) N/4 + l / 4 (sub-row-major layout of rows_sub_kernel)
-    const int pos = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pos >= N) return;
-    const int l = subrow ? 4 * (pos & ((N >> 2) - 1)) + pos / (N >> 2) : pos;
-    const double *h = taps + (size_t)b * taille * taille;
-    double2 d[TN];
-#pragma unroll
-    for (int m = 0; m < TN; ++m) {
-        double2 cc = make_double2(0.0, 0.0);
-        if (TT || m < taille) {
-#pragma unroll
-            for (int nn = 0; nn < TN; ++nn) {
-                if (TT || nn < taille) {
-                    const double2 w = tw_N[(l * nn) & (N - 1)];
-                    const double hv = h[nn * taille + m];
-                    cc.x += hv * w.x;
-                    cc.y += hv * w.y;
-                }
-            }
-        }
-        d[m] = cc;
-    }
-    double2 *out = U + (size_t)b * (n1 + 1) * uld + pos;
-    const int k0 = blockIdx.y * kch, k1 = min(k0 + kch, n1 + 1);
-    for (int k = k0; k < k1; ++k) {
-        double2 acc = make_double2(0.0, 0.0);
-#pragma unroll
-        for (int m = 0; m < TN; ++m)
-            if (TT || m < taille) acc = cadd(acc, cmul(d[m], tw_M[(k * m) & (M - 1)]));
-        out[(size_t)k * uld] = acc;
-    }
 }

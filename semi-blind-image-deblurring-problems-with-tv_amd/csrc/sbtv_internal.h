@@ -385,7 +385,6 @@ struct ProxPlan {
     int tiles_i, tiles_j, nblk;   // blocks per image (one-iteration kernels)
     int ftiles_i, ftiles_j, fnblk; // blocks per image (temporally fused kernel)
     int cj, nw, minw, rpl;        // fused-kernel variant of this plan (columns per wave, waves, waves/SIMD, rows per lane)
-    int pipe, nbands, nseg, seglen;   // pipe = 1: streaming pipeline kernel (tv_pipe.inc): bands x column segments
     ProxCtrl *ctrl;               // [batch]
     double *pbuf;                 // [pairs][2 (px,py)][batch][M*N]; pairs = 2 (ping-pong) unless prox_reserve_pairs() asked for more
     int pairs;
@@ -394,9 +393,6 @@ struct ProxPlan {
     size_t part_stride;           // doubles per set
     unsigned *counters;           // [batch] arrival tickets (in-kernel stop-rule path)
     const int *order;             // [fnblk] workgroup -> tile of the 128-row tile kernel (null: the arithmetic XCD-chunk order)
-    // mixed tiling (mix_nfull > 0): tile ids below mix_nfull are 128-row tiles on a grid of mix_nfi tile rows, the others
-    // 64-row one-row-per-lane tiles on mix_nhi tile rows starting at image row mix_row0; dispatched last (tv.hip)
-    int mix_nfull, mix_nfi, mix_nhi, mix_row0;
     // optimistic launches (prox_iterate spec == 1) sum their error terms over a subset of the pixels (a lower bound of the
     // step sums: enough to PROVE that the stop rule cannot have fired, tv_fused.inc ESUB).  A solver loop sets this to 1 once
     // the step sums it reads come within ESUB_MARGIN of tol^2: from then on its launches sum every pixel again, so that a
@@ -483,9 +479,7 @@ struct FftPlan {
     int M, N, batch;
     int n1;                 // M/2  (column transform length, complex)
     int wave;               // 1: wave-granular kernels + tiled spectrum layout (fft_wave.inc), chosen by the image size
-    int u_tiled;            // wave mode, workgroup / pipelined row kernels: operator spectra tiled like S, U[(l/4)][k][l%4], k = 0..M/2
-    int u_ld;               // wave mode: leading dimension of the row-major operator spectra U[k][l] (N + pad: a
-                            // power-of-two row stride would put every workgroup's row on the same memory channels)
+    int u_tiled;            // = wave: operator spectra tiled like S, U[(l/4)][k][l%4], k = 0..M/2 (else column-major U[l][k])
     size_t u_img;           // complex elements of ONE operator spectrum (H, Y, D1, D2) per image
     size_t s_img;           // complex elements of the spectrum S of one image (M/2 x N packed; M x N in generic mode)
     int generic;            // 1: arbitrary-size path (fft_any.inc): full complex spectra, n1 = M

@@ -232,10 +232,10 @@ constexpr int F1RI = 64;                 // region rows
 constexpr int F1HT = FHJ + 1;            // halo above the core (the f epilogue needs px(i-1) of the final iterate)
 constexpr int F1HB = FHJ;                // halo below
 constexpr int F1CI = F1RI - F1HT - F1HB; // core rows (53)
-// mixed launch of the 128-row kernel: its last workgroups work on 64-row tiles (see prox_plan)
-struct FusedMix {
-    int nfull, nhi, row0;                // 128-row tiles (ids below nfull), tile rows of the 64-row part, its first image row
-    int stagger;                         // half-microseconds the second workgroup of every CU waits at the start of a launch
+// argument of the 128-row kernel: half-microseconds the second workgroup of every CU waits at the start of a launch
+// (16-byte aligned like the launch argument it was carved from: the kernel's prologue then keeps its measured schedule)
+struct alignas(16) FusedStagger {
+    int stagger;
 };
 // Stagger (round 4, profiles/r04_chambolle_stagger.md): the 512 workgroups of the first round start together, so the two
 // workgroups of a CU wait for their regions at the same time and then share the vector units at the same time.  Holding
@@ -408,11 +408,6 @@ __device__ __forceinline__ void fused_tlw(int slot) {
 #endif
 #include "tv_fused.inc"
 #include "tv_fused1.inc"
-#ifdef SBTV_LAB
-#include "tv_pipe.inc"      // streaming pipeline kernel: measured and lost (profiles/r02_chambolle_variants.md); lab build only
-#else
-constexpr int PK = 10;      // (the pipeline kernel's iterations per launch; the plan code below keeps its arithmetic)
-#endif
 
 // Stop rule after a fused launch of `steps_arg` iterations (see the kernel header).
 __global__ __launch_bounds__(64 * FSMAX) void chambolle_fused_ctrl_kernel(ProxCtrl *__restrict__ ctrl,
@@ -712,17 +707,9 @@ int prox_plan(sbtv_ctx *ctx, int M, int N, int batch, ProxPlan *pl, const char *
         std::call_once(env_once, [] {
             if (const char *e = getenv("SBTV_FUSED_VARIANT")) {   // tuning hook: "cj,nw,minw[,rows_per_lane]"
                 int cj = 0, nw = 0, mw = 0, rpl = 2;
-#ifdef SBTV_LAB
-                static const int known[][4] = {{8, 4, 2, 2}, {8, 8, 2, 2}, {8, 8, 1, 2}, {8, 4, 3, 2}, {6, 8, 3, 2}, {12, 4, 2, 2}, {16, 4, 1, 2},
-                                               {4, 8, 2, 2}, {4, 16, 2, 2}, {8, 6, 2, 2}, {4, 8, 3, 2}, {4, 8, 4, 2},
-                                               {6, 8, 4, 2}, {6, 8, 2, 2}, {5, 8, 4, 2},
-                                               {4, 8, 6, 1}, {4, 8, 5, 1}, {4, 8, 4, 1}, {8, 4, 6, 1}, {8, 8, 4, 1},
-                                               {8, 4, 4, 1}, {6, 8, 6, 1}, {6, 8, 4, 1}};
-#else
-                // the default build carries the two geometries the plans choose themselves (128-row tiles, and 64-row
-                // tiles for small grids); the others lost on MI355X and live in the lab build (make lab)
+                // the library carries the two geometries the plans choose themselves (128-row tiles, and 64-row tiles
+                // for small grids); the others lost on MI355X (profiles/r02_chambolle_variants.md)
                 static const int known[][4] = {{4, 8, 4, 2}, {4, 8, 4, 1}};
-#endif
                 bool ok = false;
                 if (sscanf(e, "%d,%d,%d,%d", &cj, &nw, &mw, &rpl) >= 3)
                     for (auto &k4 : known) ok = ok || (k4[0] == cj && k4[1] == nw && k4[2] == mw && k4[3] == rpl);
@@ -756,83 +743,7 @@ int prox_plan(sbtv_ctx *ctx, int M, int N, int batch, ProxPlan *pl, const char *
         geometry(4, 8, 1);
         pl->minw = 4;
     }
-    // Mixed tiling of ONE large image on the shipped geometry (lab build, SBTV_TAIL_HALF=1).  A launch of T 128-row tiles runs
-    // as T / S rounds of S = 2 workgroups x CUs, and in its last ~11 us (one workgroup life) the slots run empty one by one.
-    // The idea: as many 128-row tile rows as fill whole rounds and the rest of the image in 64-row tiles (half the work per
-    // workgroup, dispatched last through the order table), so that the slots run empty over half that time.  Same pixels,
-    // same arithmetic per pixel; only the grouping of the error partials changes.  Measured: 63-65 us per launch against 60
-    // with 196, 392 or 588 half tiles (profiles/r03_chambolle_tail.md): the one-row-per-lane body costs more per pixel
-    // than the shorter tail gives back.  Kept in the lab build as the measured alternative.
-    pl->mix_nfull = pl->mix_nfi = pl->mix_nhi = pl->mix_row0 = 0;
     pl->esub_off = 0;
-#ifdef SBTV_LAB
-    {
-        static const bool env_on = [] {
-            const char *e = getenv("SBTV_TAIL_HALF");
-            return e && e[0] == '1';
-        }();
-        static const bool order_off = [] {
-            const char *e = getenv("SBTV_TILE_ORDER");
-            return e && e[0] == '0';
-        }();
-        const int slots = 2 * ctx->cu_count;
-        if (env_on && !order_off && !g_fused_forced && batch == 1 && pl->rpl == 2 && pl->cj == 4 && pl->nw == 8 && pl->minw == 4 &&
-            (M % 2 == 0) && slots > 0 && pl->fnblk > 2 * 256) {
-            const int tj_n = pl->ftiles_j;
-            int nfi = ((pl->fnblk / slots) * slots) / tj_n;           // tile rows that fit the complete rounds
-            if (nfi > pl->ftiles_i - 1) nfi = pl->ftiles_i - 1;
-            static const int env_rows = [] {                          // SBTV_TAIL_ROWS=r: the last r 128-row tile rows instead
-                const char *e = getenv("SBTV_TAIL_ROWS");
-                return e ? atoi(e) : 0;
-            }();
-            if (env_rows > 0) nfi = pl->ftiles_i - env_rows;
-            const int row0 = nfi * FCI;
-            if (nfi >= 1 && row0 < M) {
-                const int nhi = (M - row0 + F1CI - 1) / F1CI;
-                pl->mix_nfi = nfi;
-                pl->mix_nhi = nhi;
-                pl->mix_row0 = row0;
-                pl->mix_nfull = nfi * tj_n;
-                pl->fnblk = pl->mix_nfull + nhi * tj_n;
-            }
-        }
-    }
-#endif
-    // Streaming pipeline kernel (tv_pipe.inc): bands of PCI core rows x column segments, one workgroup per CU.
-    // OPT-IN (SBTV_PROX_PIPE=1, any even M): on MI355X it does 1.34 x instead of 1.68 x the arithmetic and a third of
-    // the memory traffic, but one barrier per column step with ~100 instructions of work per wave in between leaves
-    // the vector units idle half of the time: 21.1 vs 14.7 us per Chambolle iteration at 2048^2
-    // (profiles/r02_chambolle_variants.md).  Kept as the measured alternative, exercised by the parity suite.
-    pl->pipe = 0;
-    {
-        static const int env_pipe = [] {
-            const char *e = getenv("SBTV_PROX_PIPE");
-            return e ? atoi(e) : -1;
-        }();
-#ifdef SBTV_LAB
-        const int nbands = (M + PCI - 1) / PCI;
-#else
-        const int nbands = (M + 105) / 106;
-#endif
-        int nseg = 256 / (nbands * batch);
-        if (nseg < 1) nseg = 1;
-        if (nseg > N / 80) nseg = N / 80;
-        if (nseg < 1) nseg = 1;
-        const int seglen = (N + nseg - 1) / nseg;
-        nseg = (N + seglen - 1) / seglen;
-#ifndef SBTV_LAB
-        (void)env_pipe;
-        if (false) {
-#else
-        if (env_pipe == 1 && (M % 2 == 0) && !g_fused_forced) {
-#endif
-            pl->pipe = 1;
-            pl->nbands = nbands;
-            pl->nseg = nseg;
-            pl->seglen = seglen;
-            pl->fnblk = nbands * nseg;
-        }
-    }
     const size_t P = (size_t)M * N;
     size_t npart = (size_t)batch * pl->nblk;
     if ((size_t)batch * FSTRIDE * pl->fnblk > npart) npart = (size_t)batch * FSTRIDE * pl->fnblk;
@@ -856,27 +767,21 @@ int prox_plan(sbtv_ctx *ctx, int M, int N, int batch, ProxPlan *pl, const char *
             return e && e[0] == '0';
         }();
         const int nt = pl->fnblk;
-        if (!env_off && !pl->pipe && pl->rpl == 2 && nt > 2 * 256) {
+        if (!env_off && pl->rpl == 2 && nt > 2 * 256) {
             int *od = nullptr;
             // one table per shape, built once per context (the name carries the shape)
             const std::string name = "prox.order." + std::to_string(M) + "x" + std::to_string(N) + "." + std::to_string(pl->cj) +
-                                     "." + std::to_string(pl->nw) + (pl->mix_nfull ? ".mix" + std::to_string(pl->mix_nfi) : std::string());
+                                     "." + std::to_string(pl->nw);
             const bool built = ctx->ws.find(name) != ctx->ws.end();
             SBTV_TRY(ws_get_t(ctx, name.c_str(), (size_t)nt, &od));
             if (!built) {
                 std::vector<int> h(nt);
-                const int q8 = nt >> 3, r8 = nt & 7, tj_n = pl->ftiles_j;
-                // 128-row tiles: ids 0 .. nf-1 on ti_n tile rows; mixed tiling: 64-row tiles nf .. nt-1 on mix_nhi tile rows
-                const int nf = pl->mix_nfull ? pl->mix_nfull : nt, ti_n = pl->mix_nfull ? pl->mix_nfi : pl->ftiles_i;
-                const int fq8 = nf >> 3, fr8 = nf & 7;
-                int half_next = nf;
+                const int q8 = nt >> 3, r8 = nt & 7, ti_n = pl->ftiles_i, tj_n = pl->ftiles_j;
                 for (int x = 0; x < 8; ++x) {
-                    // this XCD's workgroup ids are o * 8 + x, o = 0 .. cnt-1: first its contiguous chunk of the 128-row tiles
-                    // (border tiles before interior ones), then a contiguous run of 64-row tiles (roughly the same columns)
-                    const int cnt = q8 + (x < r8 ? 1 : 0);
-                    const int c0 = (x < fr8 ? x * (fq8 + 1) : fr8 * (fq8 + 1) + (x - fr8) * fq8);
-                    int len = fq8 + (x < fr8 ? 1 : 0);
-                    if (len > cnt) len = cnt;
+                    // this XCD's workgroup ids are o * 8 + x, o = 0 .. len-1: its contiguous chunk of the tiles (border tiles
+                    // before interior ones)
+                    const int c0 = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8);
+                    const int len = q8 + (x < r8 ? 1 : 0);
                     int o = 0;
                     // experiment (SBTV_TILE_ORDER=2 / 3): inside a chunk walk the tiles ROW by row (horizontal neighbours, which
                     // share 11 of their 32 region columns, become consecutive workgroups of the XCD; by default vertical
@@ -892,10 +797,9 @@ int prox_plan(sbtv_ctx *ctx, int M, int N, int batch, ProxPlan *pl, const char *
                     for (int pass = 0; pass < 2; ++pass)
                         for (int t2 : chunk) {
                             const int ti = t2 % ti_n, tj = t2 / ti_n;
-                            const bool border = (ti == 0 || (!pl->mix_nfull && ti == ti_n - 1) || tj == 0 || tj == tj_n - 1);
+                            const bool border = (ti == 0 || ti == ti_n - 1 || tj == 0 || tj == tj_n - 1);
                             if (env_mode == 3 ? (pass == 0) : (border == (pass == 0))) h[(size_t)(o++) * 8 + x] = t2;      // workgroup id = o * 8 + x
                         }
-                    while (o < cnt) h[(size_t)(o++) * 8 + x] = half_next++;
                 }
                 SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 SBTV_HIP(ctx, hipMemcpy(od, h.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
@@ -954,21 +858,20 @@ int g_force_single_step = 0;   // test hook (SBTV_SINGLE_STEP=1): one-iteration 
 int prox_finish(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, double *f);
 
 // Can prox_iterate run optimistically (spec_cur != nullptr) for this plan and these buffers?  Needs the tile kernels
-// (even M, aligned buffers, not the single-step / pipeline variants) and all steps in the partials' FSTRIDE slots.
+// (even M, aligned buffers, not the single-step variant) and all steps in the partials' FSTRIDE slots.
 bool prox_spec_ok(const ProxPlan &pl, const double *g, const double *f_out, int maxiter) {
     static const bool env_single = (getenv("SBTV_SINGLE_STEP") != nullptr);
     static const bool env_off = [] {
         const char *e = getenv("SBTV_PROX_SPEC");
         return e && e[0] == '0';
     }();
-    return !env_off && !env_single && !g_force_single_step && !pl.pipe && maxiter <= FSTRIDE && vec_ok(g, pl.M) &&
+    return !env_off && !env_single && !g_force_single_step && maxiter <= FSTRIDE && vec_ok(g, pl.M) &&
            vec_ok(pl.pbuf, pl.M) && (!f_out || vec_ok(f_out, pl.M));
 }
 
 // number of fused launches prox_iterate makes for `maxiter` iterations (without the redo pass)
 int prox_launches(const ProxPlan &pl, int maxiter) {
-    const int per_launch = pl.pipe ? PK : FHJ;
-    return (maxiter + per_launch - 1) / per_launch;
+    return (maxiter + FHJ - 1) / FHJ;
 }
 
 // spec: optimistic mode for solver loops (see the kernels, bit 2 of their flag word): the launches run all `maxiter`
@@ -996,8 +899,7 @@ int prox_iterate(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, int maxiter
         // temporally fused path: ceil(K/FH) launches of (nearly) equal step counts + the redo pair
         dim3 fgrid(pl.fnblk, 1, pl.batch);         // linear tile list, remapped per XCD inside the kernel
         const SideJob no_side{};
-        const int per_launch = pl.pipe ? PK : FHJ;
-        const int nl = (maxiter + per_launch - 1) / per_launch;
+        const int nl = prox_launches(pl, maxiter);
         const int base = maxiter / nl, extra = maxiter % nl;
         // In-kernel stop rule: the last workgroup of a normal launch applies the rule itself instead of a separate
         // control kernel.  On large grids the gain is marginal (+0.6 % SALSA it/s at 2048^2), so there it needs
@@ -1027,30 +929,17 @@ int prox_iterate(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, int maxiter
                     spec_off += steps;
                 }
             }
-#ifdef SBTV_LAB
-            if (pl.pipe) {
-                launched = true;
-                if (g_fused.fast)
-                    hipLaunchKernelGGL(chambolle_pipe_kernel<true>, fgrid, dim3(64 * PNW), 0, ctx->stream, g, pl.pbuf,
-                                       pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.nbands, pl.nseg, pl.seglen, pl.fnblk,
-                                       steps, redo, f_out, write_f, pl.counters, kflags);
-                else
-                    hipLaunchKernelGGL(chambolle_pipe_kernel<false>, fgrid, dim3(64 * PNW), 0, ctx->stream, g, pl.pbuf,
-                                       pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.nbands, pl.nseg, pl.seglen, pl.fnblk,
-                                       steps, redo, f_out, write_f, pl.counters, kflags);
-            }
-#endif
 #define SBTV_FUSED_CASE(CJ_, NW_, MW_)                                                                               \
-    if (!pl.pipe && pl.rpl == 2 && pl.cj == CJ_ && pl.nw == NW_ && pl.minw == MW_) {             \
+    if (pl.rpl == 2 && pl.cj == CJ_ && pl.nw == NW_ && pl.minw == MW_) {                         \
         launched = true;                                                                                             \
         if (g_fused.fast)                                                                                            \
             hipLaunchKernelGGL((chambolle_fused_kernel<CJ_, NW_, MW_, true>), fgrid, dim3(64 * NW_), 0, ctx->stream, \
                                g, pl.pbuf, pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.ftiles_i, pl.fnblk, steps, \
-                               redo, f_out, write_f, pl.counters, kflags, sj, pl.order, FusedMix{0, 0, 0, fused_stagger(pl.fnblk)});  \
+                               redo, f_out, write_f, pl.counters, kflags, sj, pl.order, FusedStagger{fused_stagger(pl.fnblk)});  \
         else                                                                                                         \
             hipLaunchKernelGGL((chambolle_fused_kernel<CJ_, NW_, MW_, false>), fgrid, dim3(64 * NW_), 0,             \
                                ctx->stream, g, pl.pbuf, pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.ftiles_i,     \
-                               pl.fnblk, steps, redo, f_out, write_f, pl.counters, kflags, sj, pl.order, FusedMix{0, 0, 0, fused_stagger(pl.fnblk)}); \
+                               pl.fnblk, steps, redo, f_out, write_f, pl.counters, kflags, sj, pl.order, FusedStagger{fused_stagger(pl.fnblk)}); \
     }
             // optimistic ping-pong launches of a solver loop (spec == 1: the caller only CHECKS the rule afterwards): the error
             // sums run over a quarter of the columns (tv_fused.inc, ESUB); SBTV_ERR_SUBSET=0: all columns
@@ -1058,48 +947,17 @@ int prox_iterate(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, int maxiter
                 const char *e = getenv("SBTV_ERR_SUBSET");
                 return !(e && e[0] == '0');
             }();
-            if (esub_wanted && !pl.esub_off && spec == 1 && !redo && !pl.pipe && pl.rpl == 2 && pl.cj == 4 && pl.nw == 8 && pl.minw == 4 &&
-                pl.mix_nfull == 0 && g_fused.fast) {
+            if (esub_wanted && !pl.esub_off && spec == 1 && !redo && pl.rpl == 2 && pl.cj == 4 && pl.nw == 8 && pl.minw == 4 &&
+                g_fused.fast) {
                 launched = true;
-                hipLaunchKernelGGL((chambolle_fused_kernel<4, 8, 4, true, false, true>), fgrid, dim3(64 * 8), 0, ctx->stream, g, pl.pbuf,
+                hipLaunchKernelGGL((chambolle_fused_kernel<4, 8, 4, true, true>), fgrid, dim3(64 * 8), 0, ctx->stream, g, pl.pbuf,
                                    pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.ftiles_i, pl.fnblk, steps, redo, f_out, write_f,
-                                   pl.counters, kflags, sj, pl.order, FusedMix{0, 0, 0, fused_stagger(pl.fnblk)});
+                                   pl.counters, kflags, sj, pl.order, FusedStagger{fused_stagger(pl.fnblk)});
             } else
-#ifdef SBTV_LAB
-            if (!pl.pipe && pl.rpl == 2 && pl.mix_nfull > 0) {
-                // mixed tiling (shipped geometry only, see prox_plan): the 128-row grid has mix_nfi tile rows
-                launched = true;
-                const FusedMix mix{pl.mix_nfull, pl.mix_nhi, pl.mix_row0, 0};
-                if (g_fused.fast)
-                    hipLaunchKernelGGL((chambolle_fused_kernel<4, 8, 4, true, true>), fgrid, dim3(64 * 8), 0, ctx->stream, g, pl.pbuf,
-                                       pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.mix_nfi, pl.fnblk, steps, redo, f_out, write_f,
-                                       pl.counters, kflags, sj, pl.order, mix);
-                else
-                    hipLaunchKernelGGL((chambolle_fused_kernel<4, 8, 4, false, true>), fgrid, dim3(64 * 8), 0, ctx->stream, g, pl.pbuf,
-                                       pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.mix_nfi, pl.fnblk, steps, redo, f_out, write_f,
-                                       pl.counters, kflags, sj, pl.order, mix);
-            } else
-#endif
             SBTV_FUSED_CASE(4, 8, 4)
-#ifdef SBTV_LAB
-            SBTV_FUSED_CASE(8, 4, 2)
-            SBTV_FUSED_CASE(8, 8, 2)
-            SBTV_FUSED_CASE(8, 8, 1)
-            SBTV_FUSED_CASE(8, 4, 3)
-            SBTV_FUSED_CASE(6, 8, 3)
-            SBTV_FUSED_CASE(12, 4, 2)
-            SBTV_FUSED_CASE(16, 4, 1)
-            SBTV_FUSED_CASE(4, 8, 2)
-            SBTV_FUSED_CASE(4, 16, 2)
-            SBTV_FUSED_CASE(8, 6, 2)
-            SBTV_FUSED_CASE(4, 8, 3)
-            SBTV_FUSED_CASE(6, 8, 4)
-            SBTV_FUSED_CASE(6, 8, 2)
-            SBTV_FUSED_CASE(5, 8, 4)
-#endif
 #undef SBTV_FUSED_CASE
 #define SBTV_FUSED1_CASE(CJ_, NW_, MW_)                                                                              \
-    if (!pl.pipe && pl.rpl == 1 && pl.cj == CJ_ && pl.nw == NW_ && pl.minw == MW_) {             \
+    if (pl.rpl == 1 && pl.cj == CJ_ && pl.nw == NW_ && pl.minw == MW_) {                         \
         launched = true;                                                                                             \
         if (g_fused.fast)                                                                                            \
             hipLaunchKernelGGL((chambolle_fused1_kernel<CJ_, NW_, MW_, true>), fgrid, dim3(64 * NW_), 0,             \
@@ -1110,22 +968,13 @@ int prox_iterate(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, int maxiter
                                ctx->stream, g, pl.pbuf, pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.ftiles_i,     \
                                pl.fnblk, steps, redo, f_out, write_f, pl.counters, kflags, sj);                         \
     }
-            if (esub_wanted && !pl.esub_off && spec == 1 && !redo && !pl.pipe && pl.rpl == 1 && pl.cj == 4 && pl.nw == 8 && pl.minw == 4 && g_fused.fast) {
+            if (esub_wanted && !pl.esub_off && spec == 1 && !redo && pl.rpl == 1 && pl.cj == 4 && pl.nw == 8 && pl.minw == 4 && g_fused.fast) {
                 launched = true;
                 hipLaunchKernelGGL((chambolle_fused1_kernel<4, 8, 4, true, true>), fgrid, dim3(64 * 8), 0, ctx->stream, g, pl.pbuf,
                                    pl.ctrl, pl.partials, pl.M, pl.N, pl.batch, pl.ftiles_i, pl.fnblk, steps, redo, f_out, write_f,
                                    pl.counters, kflags, sj);
             } else
             SBTV_FUSED1_CASE(4, 8, 4)
-#ifdef SBTV_LAB
-            SBTV_FUSED1_CASE(4, 8, 6)
-            SBTV_FUSED1_CASE(4, 8, 5)
-            SBTV_FUSED1_CASE(8, 4, 6)
-            SBTV_FUSED1_CASE(8, 4, 4)
-            SBTV_FUSED1_CASE(8, 8, 4)
-            SBTV_FUSED1_CASE(6, 8, 6)
-            SBTV_FUSED1_CASE(6, 8, 4)
-#endif
 #undef SBTV_FUSED1_CASE
             // a plan whose geometry matches no compiled variant must not pass silently (nothing was enqueued)
             if (!launched)
@@ -1282,7 +1131,7 @@ int sbtv_diag_prox_variant(sbtv_ctx *ctx, int M, int N, int batch, int out[6]) {
     out[2] = pl.minw;
     out[3] = pl.rpl;
     out[4] = pl.fnblk;
-    out[5] = (M % 2 == 0 && !env_single && !g_force_single_step) ? (pl.pipe ? 2 : 1) : 0;
+    out[5] = (M % 2 == 0 && !env_single && !g_force_single_step) ? 1 : 0;
     return 0;
 }
 

@@ -405,18 +405,7 @@ __device__ __forceinline__ void fused_body(const double *__restrict__ gg, const 
     SBTV_TL(3);
 }
 
-// (tv_fused1.inc, included after this file: the one-row-per-lane body, which a MIX launch runs on its last tiles)
-template <int FCJ, int FNW, bool FAST, bool INTERIOR, bool ESUB>
-__device__ __forceinline__ void fused1_body(const double *__restrict__ gg, const double *__restrict__ pxi,
-                                            const double *__restrict__ pyi, double *__restrict__ pxo,
-                                            double *__restrict__ pyo, double *__restrict__ partial_out, int nblk,
-                                            int M, int N, int ti, int tj, int nsteps, double lambda, double tau,
-                                            double *__restrict__ lds_base, double *__restrict__ f_out, int row0);
-
-// MIX: the tile list is mix.nfull 128-row tiles on `tiles_i` tile rows followed by 64-row tiles (one row per lane) on mix.nhi
-// tile rows that start at image row mix.row0.  Half the work per workgroup: dispatched last (order table), they halve the
-// tail of the launch in which the slots run empty one by one (profiles/r03_chambolle_tail.md).
-template <int FCJ, int FNW, int MINW, bool FAST, bool MIX = false, bool ESUB = false>
+template <int FCJ, int FNW, int MINW, bool FAST, bool ESUB = false>
 __global__ __launch_bounds__(64 * FNW, MINW) void chambolle_fused_kernel(const double *__restrict__ g,
                                                                           double *__restrict__ pbuf,
                                                                           ProxCtrl *__restrict__ ctrl,
@@ -426,7 +415,7 @@ __global__ __launch_bounds__(64 * FNW, MINW) void chambolle_fused_kernel(const d
                                                                           double *__restrict__ f_all, int write_f,
                                                                           unsigned *__restrict__ counters,
                                                                           int inline_ctrl, SideJob side,
-                                                                          const int *__restrict__ order, FusedMix mix) {
+                                                                          const int *__restrict__ order, FusedStagger stg) {
     // write_f: this launch also stores f = g - lambda div p (the last planned launch and the
     // redo launch).  The redo launch doubles as the finish-only pass (0 steps) when no launch has
     // produced a valid f yet (early stop before the last planned launch).
@@ -491,36 +480,17 @@ __global__ __launch_bounds__(64 * FNW, MINW) void chambolle_fused_kernel(const d
         if (order) tile = order[bid];
     }
     double *fo = (write_f && f_all) ? f_all + (size_t)b * P : nullptr;
-    if (mix.stagger > 0) {
+    const int stagger = stg.stagger;
+    if (stagger > 0) {
         // workgroups 256..511 are the SECOND workgroup of their CU in the first round (blocks are dealt round-robin over the
         // XCDs and then over an XCD's 32 CUs): hold them back so that the two workgroups of a CU alternate between the memory
         // phase and the arithmetic phase instead of sharing both (tv.hip fused_stagger)
         const int bid = blockIdx.x - nside;
         if (bid >= 256 && bid < 512 && b == 0)
-            for (int q = 0; q < mix.stagger; ++q) __builtin_amdgcn_s_sleep(18);      // ~0.5 us per round
-    }
-    if constexpr (MIX) {
-        if (tile >= mix.nfull) {
-            const int th = tile - mix.nfull;
-            const int ti = th % mix.nhi, tj = th / mix.nhi;
-            double *pout = partials + ((size_t)b * FSTRIDE + (spec ? ((inline_ctrl >> 12) & 31) : 0)) * nblk + tile;
-            const int i0 = mix.row0 + ti * F1CI - F1HT, j0 = tj * (FRJ - FHL - FHJ) - FHL;
-            const bool interior = (i0 >= 1) && (i0 + F1RI <= M - 1) && (j0 >= 1) && (j0 + FRJ <= N - 1);
-            if (interior)
-                fused1_body<FCJ, FNW, FAST, true, ESUB>(gg, pxi, pyi, pxo, pyo, pout, nblk, M, N, ti, tj, nsteps, c.lambda, c.tau, lds,
-                                                  fo, mix.row0);
-            else
-                fused1_body<FCJ, FNW, FAST, false, ESUB>(gg, pxi, pyi, pxo, pyo, pout, nblk, M, N, ti, tj, nsteps, c.lambda, c.tau,
-                                                   lds, fo, mix.row0);
-            if (!spec && ((inline_ctrl & 1) || redo_mode))
-                fused_inline_ctrl(&ctrl[b], partials + (size_t)b * FSTRIDE * nblk, nblk, nsteps, write_f, counters + b, redo_mode);
-            return;
-        }
+            for (int q = 0; q < stagger; ++q) __builtin_amdgcn_s_sleep(18);      // ~0.5 us per round
     }
     const int ti = tile % tiles_i, tj = tile / tiles_i;
-    // (MIX: every tile files its partials under its tile id; the 128-row grid then has only `tiles_i` of the image's tile rows)
-    double *pout = partials + ((size_t)b * FSTRIDE + (spec ? ((inline_ctrl >> 12) & 31) : 0)) * nblk +
-                   (MIX ? (size_t)tile : (size_t)tj * tiles_i + ti);
+    double *pout = partials + ((size_t)b * FSTRIDE + (spec ? ((inline_ctrl >> 12) & 31) : 0)) * nblk + (size_t)tj * tiles_i + ti;
     // region strictly inside the image (one pixel of margin for the i-1 / j-1 / i+1 / j+1 rules)?
     const int i0 = ti * FCI - FH, j0 = tj * (FRJ - FHL - FHJ) - FHL;
     const bool interior = (i0 >= 1) && (i0 + FRI <= M - 1) && (j0 >= 1) && (j0 + FRJ <= N - 1);

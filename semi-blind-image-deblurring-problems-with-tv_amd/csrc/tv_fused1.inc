@@ -7,14 +7,14 @@
 // the other two keep the fp64 pipes busy.  Loads are 8 bytes per lane (no alignment requirement,
 // so odd M works as well).
 
-// (F1RI, F1HT, F1HB, F1CI are defined in tv.hip: the 128-row kernel calls this body for the tiles of its last round)
+// (F1RI, F1HT, F1HB, F1CI are defined in tv.hip)
 
 template <int FCJ, int FNW, bool FAST, bool INTERIOR, bool ESUB>
 __device__ __forceinline__ void fused1_body(const double *__restrict__ gg, const double *__restrict__ pxi,
                                             const double *__restrict__ pyi, double *__restrict__ pxo,
                                             double *__restrict__ pyo, double *__restrict__ partial_out, int nblk,
                                             int M, int N, int ti, int tj, int nsteps, double lambda, double tau,
-                                            double *__restrict__ lds_base, double *__restrict__ f_out, int row0) {
+                                            double *__restrict__ lds_base, double *__restrict__ f_out) {
     constexpr int FRJ = FCJ * FNW;
     SBTV_TL(0);
     double(*gl_lds)[F1RI] = reinterpret_cast<double(*)[F1RI]>(lds_base);                       // [FRJ][64]
@@ -24,7 +24,7 @@ __device__ __forceinline__ void fused1_body(const double *__restrict__ gg, const
     double(*esl)[64 * FNW] = reinterpret_cast<double(*)[64 * FNW]>(lds_base + (FRJ + 2 * FNW) * F1RI);   // [FH][64 FNW]
 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int gi = row0 + ti * F1CI - F1HT + lane;                // global row of this lane
+    const int gi = ti * F1CI - F1HT + lane;                       // global row of this lane
     const int jw = tj * (FRJ - FHL - FHJ) - FHL + w * FCJ;        // global column of this wave's first column
     const bool rin = INTERIOR || ((gi >= 0) && (gi < M));
     const bool rcore = (lane >= F1HT) && (lane < F1RI - F1HB);
@@ -237,10 +237,10 @@ __global__ __launch_bounds__(64 * FNW, MINW) void chambolle_fused1_kernel(const 
     double *fo = (write_f && f_all) ? f_all + (size_t)b * P : nullptr;
     if (interior)
         fused1_body<FCJ, FNW, FAST, true, ESUB>(gg, pxi, pyi, pxo, pyo, pout, nblk, M, N, ti, tj, nsteps, c.lambda, c.tau,
-                                                lds, fo, 0);
+                                                lds, fo);
     else
         fused1_body<FCJ, FNW, FAST, false, ESUB>(gg, pxi, pyi, pxo, pyo, pout, nblk, M, N, ti, tj, nsteps, c.lambda, c.tau,
-                                                 lds, fo, 0);
+                                                 lds, fo);
     if (!spec && ((inline_ctrl & 1) || redo_mode))
         fused_inline_ctrl(&ctrl[b], partials + (size_t)b * FSTRIDE * nblk, nblk, nsteps, write_f, counters + b, redo_mode);
 }

@@ -10,10 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from conftest import LAB_LIB
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAB = {"SBTV_LIBRARY": LAB_LIB}      # variants only the lab build carries
 
 CHILD = r"""
 import json, os, sys
@@ -42,15 +39,11 @@ def _run(tmp_path, name, env):
     return np.load(out)
 
 
-def test_exact_fast_single_step_and_tile_variants_agree(tmp_path):
+def test_exact_fast_single_step_and_default_tile_variants_agree(tmp_path):
     ref = _run(tmp_path, "default", {})
     variants = {
         "exact": {"SBTV_EXACT": "1"},                       # IEEE div/sqrt, no FMA contraction
         "single": {"SBTV_SINGLE_STEP": "1"},                # one-iteration kernels (the fallback path)
-        "tile_8_4": dict(LAB, SBTV_FUSED_VARIANT="8,4,2"),  # other tile geometries of the fused kernel (lab build)
-        "tile_16_4": dict(LAB, SBTV_FUSED_VARIANT="16,4,1"),
-        "nospec": dict(LAB, SBTV_FUSED_VARIANT="4,8,2"),
-        "lab_default": dict(LAB),                           # the lab build without any switch = the default kernels
         "rows1": {"SBTV_FUSED_VARIANT": "4,8,4,1"},         # one row per lane (64-row tiles; the default on small grids)
         "rows2": {"SBTV_FUSED_VARIANT": "4,8,4"},           # the 128-row tiles large images get, forced on these small ones
         "inline": {"SBTV_INLINE_CTRL": "1"},                # stop rule applied by the last workgroup of a launch
@@ -181,79 +174,3 @@ def test_loop_hooks_agree_with_the_default_loops(tmp_path):
             np.testing.assert_allclose(got[key], ref[key], rtol=1e-11, atol=1e-11, err_msg=key)
         else:
             np.testing.assert_array_equal(got[key], ref[key], err_msg=key)
-
-
-ROWS_CHILD = r"""
-import os, sys
-import numpy as np
-sys.path.insert(0, os.path.join(%(root)r, "semi-blind-image-deblurring-problems-with-tv_amd"))
-sys.path.insert(0, os.path.join(%(root)r, "tests"))
-import sbtv
-from conftest import synth_image
-res = {}
-for tag, (M, N) in (("a", (2048, 1024)), ("b", (1024, 2048))):
-    x = synth_image(M, N, 9)
-    st = sbtv.demo_setup("gaussian", x, np.random.default_rng(3).standard_normal(x.shape), evMax=1.0)
-    A = sbtv.BlurOperator(sbtv.Gaussian_psf(7, 0.4, 0.3))
-    mu = 0.003
-    res[tag + "_Ax"], res[tag + "_ATx"], res[tag + "_LSx"] = A(x), A.T(x), A.LS(mu)(x)
-    out = sbtv.SALSA_v2(st["y"], A, 0.03 * st["sigma"] ** 2, "MU", mu, "AT", A.T, "LS", A.LS(mu), "True_x", x,
-                        "ToleranceA", 1e-9, "MAXITERA", 8, "TVINITIALIZATION", 1, "TViters", 10)
-    res[tag + "_x"], res[tag + "_obj"] = out[0], out[3]
-    got = sbtv.csalsa(st["y"], A, 0.5, 0.5, st["sigma"], "AT", A.T, "LS", A.invLS, "TVINITIALIZATION", 1, "TVITERS", 5,
-                      "STOPCRITERION", 3, "TOLERANCEA", 1e-9, "MAXITERA", 8, "TRUE_X", x, "VERBOSE", 0)
-    res[tag + "_cx"], res[tag + "_cobj"], res[tag + "_ccrit"] = got[0], got[3], got[6]
-np.savez(sys.argv[1], **res)
-"""
-
-
-def test_lab_row_pass_variants_agree_at_the_wave_granular_sizes(tmp_path):
-    """The row passes the lab build keeps for M, N in {1024, 2048} against the default library's pipelined kernel: four
-    wave-local sub-transforms per row on sub-row-major operator spectra (SBTV_ROWS_SUB=1, round 3) and the workgroup kernel
-    on the tiled layout (SBTV_ROWS_PIPE=0); plain operator applications, SALSA (OP_SALSA) and C-SALSA (OP_CSALSA)."""
-    def run(name, env):
-        out = str(tmp_path / (name + ".npz"))
-        e = dict(os.environ)
-        e.update(env)
-        subprocess.run([sys.executable, "-c", ROWS_CHILD % {"root": ROOT}, out], check=True, env=e, timeout=900)
-        return np.load(out)
-    ref = run("default", {})
-    for name, env in (("rows_sub", dict(LAB, SBTV_ROWS_SUB="1")), ("rows_wg", dict(LAB, SBTV_ROWS_PIPE="0"))):
-        got = run(name, env)
-        for key in ref.files:
-            scale = float(np.max(np.abs(ref[key])))
-            assert np.max(np.abs(got[key] - ref[key])) <= 1e-10 * scale, (name, key)
-
-
-TAIL_CHILD = r"""
-import os, sys
-import numpy as np
-sys.path.insert(0, os.path.join(%(root)r, "semi-blind-image-deblurring-problems-with-tv_amd"))
-sys.path.insert(0, os.path.join(%(root)r, "tests"))
-import sbtv
-from conftest import synth_image
-g = synth_image(2048, 2048, 13) + np.random.default_rng(5).standard_normal((2048, 2048))
-f, px, py, k, err = sbtv.chambolle_prox_TV_stop(g, "lambda", 7.0, "maxiter", 25, return_info=True)
-f2, px2, py2, k2, err2 = sbtv.chambolle_prox_TV_stop(g, "lambda", 7.0, "maxiter", 10, "dualvars", np.hstack([px, py]), return_info=True)
-np.savez(sys.argv[1], f=f, px=px, py=py, k=k, err=err, f2=f2, px2=px2, k2=k2, err2=err2)
-"""
-
-
-def test_lab_mixed_tiling_agrees_with_the_128_row_tiles(tmp_path):
-    """SBTV_TAIL_HALF=1 (lab build): the last workgroups of a launch work on 64-row tiles (one row per lane) below the
-    128-row ones, three splits of the tile rows; cold prox of 25 iterations and a warm-started one of 10 at 2048 x 2048."""
-    def run(name, env):
-        out = str(tmp_path / (name + ".npz"))
-        e = dict(os.environ)
-        e.update(env)
-        subprocess.run([sys.executable, "-c", TAIL_CHILD % {"root": ROOT}, out], check=True, env=e, timeout=900)
-        return np.load(out)
-    ref = run("default", {})
-    for name, env in (("auto", dict(LAB, SBTV_TAIL_HALF="1")), ("rows1", dict(LAB, SBTV_TAIL_HALF="1", SBTV_TAIL_ROWS="1")),
-                      ("rows2", dict(LAB, SBTV_TAIL_HALF="1", SBTV_TAIL_ROWS="2"))):
-        got = run(name, env)
-        assert int(got["k"][0]) == int(ref["k"][0]) == 25 and int(got["k2"][0]) == int(ref["k2"][0]) == 10
-        for key in ("err", "err2"):
-            assert float(got[key][0]) == pytest.approx(float(ref[key][0]), rel=1e-12), (name, key)
-        for key in ("f", "px", "py", "f2", "px2"):
-            np.testing.assert_allclose(got[key], ref[key], rtol=1e-12, atol=1e-12, err_msg=name + " " + key)

@@ -40,12 +40,11 @@ def _find(rep, *parts):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_fused_chambolle_kernel_keeps_four_waves_per_simd_without_scratch():
+def test_default_fused_chambolle_kernels_keep_four_waves_per_simd_without_scratch():
     rep = _report("tv.hip")
-    # template <FCJ, FNW, MINW, FAST, MIX, ESUB>: ...Lb1ELb0ELb0E sums the error of every pixel (exact launches, SAPG),
-    # ...Lb1ELb0ELb1E of a subset (the optimistic launches of the SALSA / FISTA / ADMM loops: what bench.py times);
-    # MIX = true (mixed launch whose last workgroups run the one-row-per-lane body) exists in the lab build only
-    for name in ("chambolle_fused_kernelILi4ELi8ELi4ELb1ELb0ELb0E", "chambolle_fused_kernelILi4ELi8ELi4ELb1ELb0ELb1E"):
+    # template <FCJ, FNW, MINW, FAST, ESUB>: ...Lb1ELb0EE sums the error of every pixel (exact launches, SAPG),
+    # ...Lb1ELb1EE of a subset (the optimistic launches of the SALSA / FISTA / ADMM loops: what bench.py times)
+    for name in ("chambolle_fused_kernelILi4ELi8ELi4ELb1ELb0EE", "chambolle_fused_kernelILi4ELi8ELi4ELb1ELb1EE"):
         k = _find(rep, name)
         assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0, (name, k)
         assert k["VGPRs"] <= 128 and k["Occupancy"] == 4, (name, k)

@@ -40,8 +40,7 @@ print("LABJSON" + json.dumps(out))
 
 VARIANTS = {
     "legacy (workgroup kernels)": {"SBTV_FFT_WAVE": "0"},
-    "wave, rows V=16": {"SBTV_FFT_WAVE": "1", "SBTV_ROWS_V": "16"},
-    "wave, rows V=8": {"SBTV_FFT_WAVE": "1", "SBTV_ROWS_V": "8"},
+    "wave (tiled layout, pipelined rows)": {"SBTV_FFT_WAVE": "1"},
 }
 
 
@@ -73,7 +72,7 @@ def main():
     res = {}
     for name in a.variants:
         env = dict(os.environ)
-        for k in ("SBTV_FFT_WAVE", "SBTV_ROWS_V", "SBTV_FUSED_VARIANT", "SBTV_INLINE_CTRL"):
+        for k in ("SBTV_FFT_WAVE", "SBTV_FUSED_VARIANT", "SBTV_INLINE_CTRL"):
             env.pop(k, None)
         env.update(VARIANTS[name])
         code = CHILD % dict(root=ROOT, sizes=a.size, batches=a.batch, passes=a.passes, reps=a.reps, check=a.check)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # In-situ kernel times of the bench loop under several environment settings, same box (run on the GPU box):
-#   bash tools/prof_env.sh "base:SBTV_U_TILED=0 SBTV_ROWS_PIPE=0" "pipe:SBTV_ROWS_PIPE=1"
+#   bash tools/prof_env.sh "legacy:SBTV_FFT_WAVE=0" "wave:SBTV_FFT_WAVE=1"
 # -> gpurun_out/prof_env_<label>_kernel_stats.csv and the top kernels on stdout
 set -eo pipefail
 export TMPDIR=/tmp
