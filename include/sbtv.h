@@ -51,7 +51,7 @@ extern "C" {
 /* sbtv_fista_tv only: */
 #define SBTV_FISTA_EXACT_PROX 2 /* stop-rule kernel after every Chambolle launch (default: the launches of a prox run all
                                  * prox_iters iterations, the host applies the rule of chambolle_prox_TV_stop.m:131 over the
-                                 * steps afterwards and repeats the call with this flag if it stopped early) */
+                                 * steps afterwards and repeats the solve with exact launches if it stopped early) */
 
 /* status codes */
 #define SBTV_OK                   0
@@ -476,9 +476,9 @@ int sbtv_CoRAL_v2_sharded(sbtv_group *g, const double *y, int M, int N, int n_it
  *   prox of 10 iterations incl. f (one SALSA outer iteration's share); 8 cold TV prox of 25 iterations incl. f;
  *   11..15 ONE fused Chambolle launch of 1..5 warm-started iterations without f and without control kernels (separates
  *   the fixed cost of a launch from the cost of an iteration).
- * sbtv_last_host_stats: how the HOST side of the most recent sbtv_SALSA_v2 call waited for the device (the loop keeps one
- *   iteration queued ahead and polls completion tags in pinned memory): out = {waits, waits that found the scalars at
- *   the first look, waits that went past the spin window and slept, nanosleep calls, stream queries (the 50 ms
+ * sbtv_last_host_stats: how the HOST side of the most recent sbtv_SALSA_v2 or sbtv_fista_tv call waited for the device
+ *   (the loop keeps one iteration queued ahead and polls completion tags in pinned memory): out = {waits, waits that found
+ *   the scalars at the first look, waits that went past the spin window and slept, nanosleep calls, stream queries (the 50 ms
  *   fallback), seconds inside the waits, longest wait, seconds spent enqueueing, longest enqueue of one iteration,
  *   the outer iteration the longest wait was for, and what the operating system did to the calling thread during the
  *   loop (getrusage(RUSAGE_THREAD) deltas): voluntary / involuntary context switches, minor / major page faults}.

@@ -6,9 +6,9 @@
 // loop since round 3 is its stream discipline: the Chambolle launches of an outer iteration are OPTIMISTIC (all TViters
 // iterations back to back, no stop-rule kernels, no redo pass; the host applies chambolle_prox_TV_stop.m:131 to the step
 // sums it reads with the iteration's scalars and, should the rule ever fire before the last step, repeats the solve with
-// exact launches: SBTV_ADMM_EXACT=1 forces those), and the host evaluates the outer stop rule one iteration late while
-// the next iteration already runs (x is double-buffered, so the result of the stopping iteration is intact).  The
-// images of a batch are solved one after another.
+// exact launches), and the host evaluates the outer stop rule one iteration late while the next iteration already runs
+// (x is double-buffered, so the result of the stopping iteration is intact).  The images of a batch are solved one after
+// another.
 #include <chrono>
 #include <cmath>
 
@@ -347,16 +347,6 @@ int check_common(sbtv_ctx *ctx, const char *who, const double *y, const double *
     return 0;
 }
 
-constexpr int ADMM_RESTART_EXACT = 12345;      // internal status: the optimistic prox met its stop rule early
-
-inline bool admm_exact_forced() {
-    static const bool on = [] {
-        const char *e = getenv("SBTV_ADMM_EXACT");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
 // C-SALSA: the constraint split (v, bv) as ONE spectrum and a scalar (default) or as images (SBTV_CSALSA_SPECTRAL=0)
 inline bool csalsa_spectral_wanted() {
     static const bool on = [] {
@@ -377,18 +367,6 @@ inline int admm_prox(sbtv_ctx *ctx, const ProxPlan &pp, const double *g, int K, 
     SBTV_TRY(prox_iterate(ctx, pp, g, K, f, false, 1, (int)(*nlaunch & 1), nullptr));
     *nlaunch += prox_launches(pp, K);
     return reduce_partials(ctx, pp.partials, K, pp.fnblk, stepsums);
-}
-// cont = (k < MaxIter) & (err > tol) over the K step sums: did the rule stop before the last step?
-inline bool admm_fired_early(const double *stepsums, int K, double tol) {
-    for (int k = 1; k < K; ++k)
-        if (!(sqrt(stepsums[k - 1]) > tol * SPEC_TOL_GUARD)) return true;
-    return false;
-}
-// the step sums of launches that sum a subset of the pixels are lower bounds (ProxPlan::esub_off): are they still far from tol^2?
-inline bool admm_sums_near_tol(const double *stepsums, int K, double tol) {
-    for (int k = 1; k <= K; ++k)
-        if (!(stepsums[k - 1] > ESUB_MARGIN * tol * tol)) return true;
-    return false;
 }
 
 // Per-iteration scalars travel through two pinned slots; an event per slot tells the host (which runs one iteration
@@ -412,7 +390,7 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         SBTV_TRY(fft_plan(ctx, M, N, 1, &chk));
         // spectral form of the constraint split (see `enqueue_spectral` below): needs fixed mu1 / mu2, an even M (pairs of
         // one column per lane) and the row kernels that carry OP_CSALSA
-        const bool sp = delta == 1.0 && !admm_exact_forced() && csalsa_spectral_wanted() && fft_rows_csalsa_ok(chk) && !(M & 1) &&
+        const bool sp = delta == 1.0 && csalsa_spectral_wanted() && fft_rows_csalsa_ok(chk) && !(M & 1) &&
                         (size_t)M * N < ((size_t)1 << 31);
         SBTV_TRY(admm_common(ctx, M, N, taps, taille, sp ? yd : nullptr, &c));
         c.spectral = sp;
@@ -502,7 +480,7 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
     SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     // optimistic prox launches need a fixed threshold (the control block is armed once) and the tile kernels
     const int K = opts->TViters;
-    const bool spec = spec_wanted && delta == 1.0 && !(opts->speculate & 2) && !admm_exact_forced() && prox_spec_ok(pp, g, u, K);
+    const bool spec = spec_wanted && delta == 1.0 && prox_spec_ok(pp, g, u, K);
     const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
     long long nlaunch = 0, prox_iters = 0;
     AdmmSlots slots;
@@ -628,20 +606,13 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
         return 0;
     };
-    bool stop = false, fired = false;
+    bool stop = false;
     // host side of iteration `outer`: traces (:494-501) and the stop rule (:517-541)
     auto process = [&](int outer) -> int {
         const int k = outer - 1;
         const double *hsl = hslot[outer & 1];
         SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
-        if (spec && admm_fired_early(hsl + 16, K, opts->chambolle_tol)) {
-            fired = true;
-            return 0;
-        }
-        if (spec && !pp.esub_off && admm_sums_near_tol(hsl + 16, K, opts->chambolle_tol)) {
-            pp.esub_off = 1;
-            ctx->solve_stats[1] += 1;
-        }
+        if (spec) SBTV_TRY(spec_stop_rule(ctx, pp, hsl + 16, K, opts->chambolle_tol));
         prox_iters += spec ? K : *reinterpret_cast<const int *>(hsl + 8);
         h_numAt += 1;
         h_numA += 1;
@@ -670,26 +641,11 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         stop = (sc < opts->tolA && crit <= epsilon);                     // :529,535,541
         return 0;
     };
-    int last = 1, enq = 1, done = 1;
-    while (!stop && done < maxiter) {
-        while (enq < maxiter && enq - done <= lag) SBTV_TRY(enqueue(++enq));
-        SBTV_TRY(process(++done));
-        if (fired) {
-            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            return ADMM_RESTART_EXACT;
-        }
-        last = done;
-    }
+    int last = 1;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
     SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    {
-        float ms = 0.f;
-        SBTV_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->timing[0] = ms;
-        ctx->timing[1] = 0.0;
-        ctx->timing[2] = (double)prox_iters;
-        ctx->timing[3] = 40.0 * (double)P * (double)prox_iters;
-    }
+    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
     SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[(last - 1) & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (numA) *numA = h_numA;
@@ -796,7 +752,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
     const auto t0 = std::chrono::steady_clock::now();
     SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     const int K1 = opts->TViters, K2 = TViters2;
-    const bool spec = spec_wanted && !(opts->speculate & 2) && !admm_exact_forced() && prox_spec_ok(pu, g1, u, K1) &&
+    const bool spec = spec_wanted && prox_spec_ok(pu, g1, u, K1) &&
                       (batched || prox_spec_ok(pv, g2, v, K2));
     const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
     long long nl_u = 0, nl_v = 0, prox_iters = 0;
@@ -870,17 +826,15 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
         SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
         return 0;
     };
-    bool stop = false, fired = false;
+    bool stop = false;
     auto process = [&](int outer) -> int {
         const double *hsl = hslot[outer & 1];
         const bool sp = spec && outer >= 2;
         SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
-        if (sp && (admm_fired_early(hsl + 16, K1, opts->chambolle_tol) || admm_fired_early(hsl + 48, K2, opts->chambolle_tol))) {
-            fired = true;
-            return 0;
+        if (sp) {     // per plan: batched, the step sums of v are those of the plan's second image (sums + 48)
+            SBTV_TRY(spec_stop_rule(ctx, pu, hsl + 16, K1, opts->chambolle_tol));
+            if (!batched) SBTV_TRY(spec_stop_rule(ctx, pv, hsl + 48, K2, opts->chambolle_tol));
         }
-        if (sp && (admm_sums_near_tol(hsl + 16, K1, opts->chambolle_tol) || admm_sums_near_tol(hsl + 48, K2, opts->chambolle_tol)))
-            pu.esub_off = pv.esub_off = 1;
         prox_iters += sp ? (long long)(K1 + K2)
                          : (long long)(*reinterpret_cast<const int *>(hsl + 12) + *reinterpret_cast<const int *>(hsl + 13));
         h_numA += 1;
@@ -906,26 +860,11 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
         obj_prev = f;
         return 0;
     };
-    int last = 0, enq = 0, done = 0;
-    while (!stop && done < maxiter) {
-        while (enq < maxiter && enq - done <= lag) SBTV_TRY(enqueue(++enq));
-        SBTV_TRY(process(++done));
-        if (fired) {
-            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            return ADMM_RESTART_EXACT;
-        }
-        last = done;
-    }
+    int last = 0;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
     SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    {
-        float ms = 0.f;
-        SBTV_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->timing[0] = ms;
-        ctx->timing[1] = 0.0;
-        ctx->timing[2] = (double)prox_iters;
-        ctx->timing[3] = 40.0 * (double)P * (double)prox_iters;
-    }
+    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
     SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (numA) *numA = h_numA;
@@ -970,23 +909,15 @@ int sbtv_CSALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, cons
     const int mi = opts->maxiter;
     for (int b = 0; b < batch; ++b) {
         const size_t o = (size_t)b * P, r = (size_t)b * mi;
-        const long long calls0 = ctx->calls;
-        for (int attempt = 0; attempt < 2; ++attempt) {       // optimistic prox launches first; exact ones if the rule fired early
-            const int rc = csalsa_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, mu1[b], mu2[b], sigma[b],
-                                      epsilon ? epsilon[b] : 0.0, continuationfactor, opts, td ? td + o : nullptr,
-                                      xi ? xi + o : nullptr, xo + o, objective ? objective + r : nullptr,
-                                      distance1 ? distance1 + r : nullptr, distance2 ? distance2 + r : nullptr,
-                                      criterion ? criterion + r : nullptr, times ? times + r : nullptr,
-                                      mses ? mses + r : nullptr, numA ? numA + b : nullptr, numAt ? numAt + b : nullptr,
-                                      n_outer ? n_outer + b : nullptr, attempt == 0);
-            if (rc == ADMM_RESTART_EXACT && attempt == 0) {
-                ctx->calls = calls0;
-                ctx->solve_stats[0] += 1;
-                continue;
-            }
-            SBTV_TRY(rc);
-            break;
-        }
+        // optimistic prox launches first (unless bit 1 of `speculate` asks for exact ones); exact ones if the rule fired early
+        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
+            return csalsa_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, mu1[b], mu2[b], sigma[b],
+                              epsilon ? epsilon[b] : 0.0, continuationfactor, opts, td ? td + o : nullptr,
+                              xi ? xi + o : nullptr, xo + o, objective ? objective + r : nullptr,
+                              distance1 ? distance1 + r : nullptr, distance2 ? distance2 + r : nullptr,
+                              criterion ? criterion + r : nullptr, times ? times + r : nullptr, mses ? mses + r : nullptr,
+                              numA ? numA + b : nullptr, numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
+        }));
     }
     SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1022,23 +953,14 @@ int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     const int mi = opts->maxiter;
     for (int b = 0; b < batch; ++b) {
         const size_t o = (size_t)b * P;
-        const long long calls0 = ctx->calls;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            const int rc = coral_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, tau1[b], tau2[b], mu1[b],
-                                     mu2[b], mu_ls ? mu_ls[b] : mu1[b] + mu2[b], TViters2, opts, td ? td + o : nullptr,
-                                     xi ? xi + o : nullptr, xo + o, objective ? objective + (size_t)b * (mi + 1) : nullptr,
-                                     distance ? distance + (size_t)b * mi * 2 : nullptr,
-                                     times ? times + (size_t)b * (mi + 1) : nullptr,
-                                     mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
-                                     numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, attempt == 0);
-            if (rc == ADMM_RESTART_EXACT && attempt == 0) {
-                ctx->calls = calls0;
-                ctx->solve_stats[0] += 1;
-                continue;
-            }
-            SBTV_TRY(rc);
-            break;
-        }
+        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
+            return coral_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, tau1[b], tau2[b], mu1[b], mu2[b],
+                             mu_ls ? mu_ls[b] : mu1[b] + mu2[b], TViters2, opts, td ? td + o : nullptr, xi ? xi + o : nullptr,
+                             xo + o, objective ? objective + (size_t)b * (mi + 1) : nullptr,
+                             distance ? distance + (size_t)b * mi * 2 : nullptr, times ? times + (size_t)b * (mi + 1) : nullptr,
+                             mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
+                             numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
+        }));
     }
     SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));

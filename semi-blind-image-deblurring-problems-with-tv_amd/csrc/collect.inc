@@ -1,4 +1,23 @@
-// The SALSA collector (included inside namespace sbtv by sbtv_internal.h users that launch or host it).
+// The collectors' shared parts (included inside namespace sbtv by sbtv_internal.h users that launch or host them).
+// This thread's part of the total of one Chambolle step's error partials pp[0..n) (written by optimistic prox launches):
+// the first 256 threads load, in a fixed order; the caller adds the parts up (xor tree, then red[0..3] in pairs).
+__device__ __forceinline__ double step_sum_part(const double *pp, int n) {
+    double s = 0.0;
+    constexpr int NB = 8;
+    for (int base = 0; threadIdx.x < 256 && base < n; base += 256 * NB) {
+        double v[NB];
+#pragma unroll
+        for (int r = 0; r < NB; ++r) {
+            const int q = base + r * 256 + (int)threadIdx.x;
+            v[r] = (q < n) ? __hip_atomic_load(pp + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < NB; ++r) s += v[r];
+    }
+    return s;
+}
+
+// The SALSA collector.
 // Block qn of image b reduces ONE quantity of SalsaScal in a fixed order (deterministic):
 //   qn 0      rows-kernel partials [batch][3][nrb]                          -> resid2 (+ scalar 7: prox iterations booked)
 //   qn 1      tvnorm partials (initial objective) or post slot 5             -> tv_u
@@ -17,19 +36,7 @@ __device__ __forceinline__ void salsa_collect_block(const Collect &c, ProxCtrl *
     const bool act = threadIdx.x < 256;
     double s = 0.0;
     if (qn >= 7) {
-        const int st = qn - 7;
-        const double *pp = c.ppart + ((size_t)b * FSTRIDE + st) * c.pnblk;
-        constexpr int NB = 8;
-        for (int base = 0; act && base < c.pnblk; base += 256 * NB) {
-            double v[NB];
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                const int q = base + r * 256 + (int)threadIdx.x;
-                v[r] = (q < c.pnblk) ? __hip_atomic_load(pp + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            }
-#pragma unroll
-            for (int r = 0; r < NB; ++r) s += v[r];
-        }
+        s = step_sum_part(c.ppart + ((size_t)b * FSTRIDE + (qn - 7)) * c.pnblk, c.pnblk);
     } else {
         const double *p = nullptr;
         int n = 0;

@@ -358,87 +358,6 @@ int stage_out_copy(sbtv_ctx *ctx, double *host, const double *dev, size_t count,
     return 0;
 }
 
-// ---- host waits inside the solver loops -----------------------------------------------------------------
-// One outer iteration of a small image takes tens of microseconds; a host thread that blocks in
-// hipEventSynchronize / hipStreamSynchronize is woken much later than that and the GPU queue runs dry.  These
-// helpers can poll (hipEventQuery / hipStreamQuery) for up to 2 ms before they fall back to the blocking call.
-// Opt-in (SBTV_SPIN=1): measured on MI355X it helps at 512^2 (8 500 vs 6 500 SALSA iterations/s) and hurts at 256^2
-// and 1024^2 (profiles/r02_small_sizes.md) - the polling calls compete with the launches of the same thread.
-static inline bool spin_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("SBTV_SPIN");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-template <class Q>
-static inline hipError_t poll_2ms(Q query) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int it = 0;; ++it) {
-        const hipError_t e = query();
-        if (e != hipErrorNotReady) return e;
-        if ((it & 63) == 63 &&
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2e-3)
-            return hipErrorNotReady;
-    }
-}
-int wait_event(sbtv_ctx *ctx, hipEvent_t ev) {
-    if (spin_enabled()) {
-        const hipError_t e = poll_2ms([&] { return hipEventQuery(ev); });
-        if (e == hipSuccess) return 0;
-        if (e != hipErrorNotReady) return fail_hip(ctx, e, "hipEventQuery", __FILE__, __LINE__);
-    }
-    SBTV_HIP(ctx, hipEventSynchronize(ev));
-    return 0;
-}
-int wait_stream(sbtv_ctx *ctx) {
-    if (spin_enabled()) {
-        const hipError_t e = poll_2ms([&] { return hipStreamQuery(ctx->stream); });
-        if (e == hipSuccess) return 0;
-        if (e != hipErrorNotReady) return fail_hip(ctx, e, "hipStreamQuery", __FILE__, __LINE__);
-    }
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// ---- hipGraph replay of launch-bound iteration bodies -------------------------------------------
-// Small images make the solver loops latency-bound (20-odd dependent kernels of a few microseconds per
-// iteration).  With SBTV_GRAPH=1 the iteration body is captured once from the stream and replayed with one
-// hipGraphLaunch: the host thread then issues one call per iteration instead of ~25.  Measured on MI355X
-// (512^2 demo): 0.168 vs 0.172 ms per SAPG iteration - the loop is bound by the dependent-kernel latency on
-// the GPU, not by host launch cost - so replay is opt-in (it mainly frees the host core when 8 ranks share
-// a node).  Results are bit-identical either way (tests/test_gpu_modes.py).
-bool graph_wanted(size_t total_px) {
-    static const char *e = getenv("SBTV_GRAPH");
-    (void)total_px;
-    return e && e[0] == '1';
-}
-
-int graph_begin(sbtv_ctx *ctx) {
-    SBTV_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    return 0;
-}
-
-// Ends the capture started by graph_begin (always, so the stream leaves capture mode even when the body
-// failed) and instantiates the graph.  body_rc is the status of the captured enqueue code.
-int graph_end(sbtv_ctx *ctx, int body_rc, hipGraphExec_t *exec) {
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-    *exec = nullptr;
-    if (body_rc != 0) {
-        if (g) (void)hipGraphDestroy(g);
-        return body_rc;
-    }
-    if (e != hipSuccess || !g) return fail_hip(ctx, e, "hipStreamEndCapture", __FILE__, __LINE__);
-    const hipError_t ei = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) {
-        *exec = nullptr;
-        return fail_hip(ctx, ei, "hipGraphInstantiate", __FILE__, __LINE__);
-    }
-    return 0;
-}
-
 }  // namespace sbtv
 
 using namespace sbtv;
@@ -639,7 +558,7 @@ int sbtv_diag_switches(char *buf, size_t cap) {
     static const char *const names[] = {
         "SBTV_CANARY", "SBTV_COLLECT_RIDE", "SBTV_EXACT", "SBTV_FFT_WAVE", "SBTV_FISTA_FUSED_STEP", "SBTV_FISTA_LAG",
         "SBTV_FUSED_VARIANT", "SBTV_GRAPH", "SBTV_INLINE_CTRL", "SBTV_PROX_SPEC", "SBTV_SAPG_DEFER",
-        "SBTV_SAPG_FUSED_MYULA", "SBTV_SAPG_HOST", "SBTV_SINGLE_STEP", "SBTV_SPIN", "SBTV_TAG_SPIN_US", "SBTV_TILE_ORDER", "SBTV_ADMM_EXACT", "SBTV_SALSA_NOX", "SBTV_CSALSA_SPECTRAL",
+        "SBTV_SAPG_FUSED_MYULA", "SBTV_SAPG_HOST", "SBTV_SINGLE_STEP", "SBTV_SPIN", "SBTV_TAG_SPIN_US", "SBTV_TILE_ORDER", "SBTV_SALSA_NOX", "SBTV_CSALSA_SPECTRAL",
         "SBTV_CORAL_BATCH", "SBTV_ROWS_FOLD", "SBTV_ERR_SUBSET", "SBTV_LANES", "SBTV_LANE_COUNT", "SBTV_STAGE_THREADS", "SBTV_TEST_FAIL_SAPG", "SBTV_FUSED_STAGGER"};
     if (!buf || cap == 0) return SBTV_ERR_BADARG;
     std::string s;

@@ -17,18 +17,11 @@
 #include <chrono>
 #include <cmath>
 
-#include <sys/resource.h>
 #include <time.h>
 
 #include "sbtv_internal.h"
 
 namespace sbtv {
-
-// images the host has frozen: their prox control block is parked (done = 1)
-__global__ void prox_park_kernel(ProxCtrl *__restrict__ ctrl, const int *__restrict__ frozen, int batch) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch && frozen[b]) ctrl[b].done = 1;
-}
 
 // start of a call: per-image parameters from the pinned staging block into device memory, frozen flags cleared
 __global__ void salsa_setup_kernel(const double *__restrict__ src, double *__restrict__ par, int npar, int *__restrict__ frozen,
@@ -76,48 +69,22 @@ void sbtv_salsa_opts_default(sbtv_salsa_opts *o) {
     o->chambolle_tau = 0.249;  // chambolle_prox_TV_stop.m:77
 }
 
-int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
-                  const double *tau, const double *mu, const sbtv_salsa_opts *opts, const double *true_x,
-                  const double *x_init, double *x_out, double *objective, double *distance, double *times,
-                  double *mses, int *numA, int *numAt, int *n_outer, int flags) {
-    if (!ctx) return SBTV_ERR_BADARG;
-    if (!y || !tau || !mu || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SALSA_v2: missing required argument");
-    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
-    if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
-        return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
-    if (opts->initialization == 33333 && !x_init) return fail(ctx, SBTV_ERR_INIT, "Initialization = array but x_init is NULL");
-    if (opts->TViters <= 0) return fail(ctx, SBTV_ERR_MAXITER, "SALSA_v2: TViters must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
-    for (int b = 0; b < batch; ++b)
-        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_MISSING_LS, "(A^T A + mu I)^(-1) must be specified: mu must be > 0");
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    // a batch: the images are independent (each stops by its own rule) -> two lanes of this context, group.hip
-    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {
-        LaneCall lc(ctx, lg);
-        return lc.done(salsa_sharded(lg, y, M, N, batch, taps, taille, tau, mu, opts, true_x, x_init, x_out, objective,
-                                     distance, times, mses, numA, numAt, n_outer, flags), batch);
-    }
+}  // extern "C"
+
+// One solve on the staged inputs (device pointers yd, td, xi); spec_wanted: optimistic prox launches
+static int salsa_solve(sbtv_ctx *ctx, const double *yd, int M, int N, int batch, const double *taps, int taille,
+                       const double *tau, const double *mu, const sbtv_salsa_opts *opts, const double *td, const double *xi,
+                       double *x_out, double *objective, double *distance, double *times, double *mses, int *numA,
+                       int *numAt, int *n_outer, int flags, bool spec_wanted) {
     FftPlan fp;
     SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
     ProxPlan pp;
     SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
     const size_t P = (size_t)M * N, cnt = P * batch;
     const int maxiter = opts->maxiter;
-    const bool want_mse = (true_x != nullptr);
+    const bool want_mse = (td != nullptr);
     const bool crit2 = (opts->stopcriterion == 2);
     const int lag = (opts->speculate & 1) ? 1 : 0;
-    const long long calls_at_entry = ctx->calls;
-
-    // start of the device-side clock of the call (sbtv_last_timing[0]): recorded while the stream is still idle - an event
-    // record between two kernels would cost the stream 5-6 us
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-
-    // ---- stage inputs
-    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "salsa.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "salsa.true", true_x, cnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "salsa.xinit", x_init, cnt, flags, &xi));
     double *xbuf[2] = {nullptr, nullptr}, *u = nullptr, *bu = nullptr, *g = nullptr;
     SBTV_TRY(ws_get_t(ctx, "salsa.x0", cnt, &xbuf[0]));
     SBTV_TRY(ws_get_t(ctx, "salsa.x1", cnt, &xbuf[1]));
@@ -125,9 +92,8 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     // runs to MAXITERA then ends without the copy out of the double buffer (images that stop earlier are copied as
     // before, after that write).  Not when x_out overlaps an input (an optimistic solve that has to be repeated reads
     // them again) and not with captured iterations (their arguments are frozen).
-    auto overlaps_out = [&](const double *p) { return p && x_out && (p < x_out + cnt) && (x_out < p + cnt); };
-    const bool direct_last_ok = x_out && (flags & SBTV_DEVICE_PTRS) && !graph_wanted(cnt) && !overlaps_out(yd) &&
-                                !overlaps_out(td) && !overlaps_out(xi);
+    const bool direct_last_ok = x_out && (flags & SBTV_DEVICE_PTRS) && !graph_wanted(cnt) && !overlaps(yd, x_out, cnt) &&
+                                !overlaps(td, x_out, cnt) && !overlaps(xi, x_out, cnt);
     SBTV_TRY(ws_get_t(ctx, "salsa.u", cnt, &u));
     SBTV_TRY(ws_get_t(ctx, "salsa.bu", cnt, &bu));
     SBTV_TRY(ws_get_t(ctx, "salsa.g", cnt, &g));
@@ -168,18 +134,10 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     SBTV_TRY(ws_get_t(ctx, "salsa.scal", 2 * (size_t)batch, &scal_d));
     SalsaScal *scal_h = nullptr;       // pinned [2][batch] + frozen staging
     SalsaScal *scal_hd = nullptr;      // the same pinned block as seen from the device
-    int *frozen_h = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(SalsaScal) * 3 * batch + sizeof(double) * batch * (2 * FSTRIDE + 3 * SALSA_TAGS) + sizeof(int) * batch +
-                                     sizeof(double) * npar, &pz));
-        scal_h = static_cast<SalsaScal *>(pz);
-        void *dp = nullptr;
-        SBTV_HIP(ctx, hipHostGetDevicePointer(&dp, pz, 0));
-        scal_hd = static_cast<SalsaScal *>(dp);
-        frozen_h = reinterpret_cast<int *>(reinterpret_cast<double *>(scal_h + 3 * (size_t)batch) + (size_t)batch * (2 * FSTRIDE + 3 * SALSA_TAGS) + npar);
-        for (int b = 0; b < batch; ++b) frozen_h[b] = 0;
-    }
+    SBTV_TRY(pinned_get(ctx, sizeof(SalsaScal) * 3 * batch + sizeof(double) * batch * (2 * FSTRIDE + 3 * SALSA_TAGS) + sizeof(int) * batch +
+                                 sizeof(double) * npar, &scal_h, &scal_hd));
+    int *frozen_h = reinterpret_cast<int *>(reinterpret_cast<double *>(scal_h + 3 * (size_t)batch) + (size_t)batch * (2 * FSTRIDE + 3 * SALSA_TAGS) + npar);
+    for (int b = 0; b < batch; ++b) frozen_h[b] = 0;
     // completion tags [2][batch][8] behind the scalars (same pinned block): tag q of slot s = outer iteration whose
     // scalar q is in scal_h[s]
     // behind them: the prox step sums [2][batch][FSTRIDE] of the optimistic launches
@@ -334,18 +292,12 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     long long prox_iters_run = 0;
     // captured graphs of this call: released on EVERY return path.  The six events of the loop belong to the context
     // (created on first use: creating and destroying them cost every call ~20 us of host time before its first launch)
-    struct LoopResources {
-        hipGraphExec_t gexec[2] = {nullptr, nullptr};
-        ~LoopResources() {
-            for (int s = 0; s < 2; ++s)
-                if (gexec[s]) (void)hipGraphExecDestroy(gexec[s]);
-        }
-    } res;
+    GraphExecs res;
     for (auto &e : ctx->loop_ev)
         if (!e) SBTV_HIP(ctx, hipEventCreate(&e));
     hipEvent_t ev_done[2] = {ctx->loop_ev[0], ctx->loop_ev[1]}, ev_p0[2] = {ctx->loop_ev[2], ctx->loop_ev[3]},
                ev_p1[2] = {ctx->loop_ev[4], ctx->loop_ev[5]};
-    hipGraphExec_t(&gexec)[2] = res.gexec;
+    hipGraphExec_t(&gexec)[2] = res.g;
     const auto t0 = std::chrono::steady_clock::now();
 
     // enqueue the kernels of outer iteration `outer` (reads x = xbuf[(outer-1)&1] through g, writes
@@ -357,12 +309,11 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     // (SURVEY.md section 8 a-1); if one does, the solve is repeated from the start with exact launches (bit 1 of
     // `speculate`), so the result is always that of the exact rule.
     // The first outer iteration always runs exactly: from the zero start its prox input is flat and the rule stops at k = 1.
-    const bool spec_ok = !(opts->speculate & 2) && !graph_wanted(cnt) && prox_spec_ok(pp, g, u, opts->TViters);
+    const bool spec_ok = spec_wanted && !graph_wanted(cnt) && prox_spec_ok(pp, g, u, opts->TViters);
     static const bool piggyback = [] {
         const char *e = getenv("SBTV_COLLECT_RIDE");
         return !(e && e[0] == '0');
     }();
-    bool fired_early = false;
     bool slot_tagged[2] = {false, false}, slot_spec[2] = {false, false};
     long long prox_iters_timed = 0;
     // The collector of an optimistic iteration does not get a launch of its own when another iteration follows: its
@@ -498,75 +449,15 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
         SBTV_TRY(enqueue_body(outer, true));
         return 0;
     };
-    // wait until the collector of iteration `outer` has delivered all eight scalars of every image: poll the tags (the
-    // host is normally one iteration ahead), yielding the core between polls.  No HIP call in the normal case: a
-    // stream query makes the runtime append a marker packet, which costs the stream 5-6 us before the next kernel.
-    // Only after 50 ms without the tags is the stream asked, so that a failed launch cannot leave the host waiting.
-    // The wait has three phases: (1) spin on the tags for up to `spin_us` microseconds (default 150; SBTV_TAG_SPIN_US):
-    // an outer iteration of a small image takes 50 us and only ONE more iteration is queued behind it, while a
-    // nanosleep of 5 us returns after 55-60 us (the kernel's default timer slack is 50 us) or much later when the core
-    // went into a deep idle state - a host that sleeps there lets the queue run dry and a 512^2 solve then runs at a
-    // third of its speed (the "slow mode" of round 2, `sbtv_last_host_stats`); (2) sleep between polls - a 2048^2
-    // iteration takes 240 us, the spin would burn a core for nothing; (3) after 50 ms ask the stream.
-    static const double spin_us = [] {
-        const char *e = getenv("SBTV_TAG_SPIN_US");
-        return e ? atof(e) : 150.0;
-    }();
-    ctx->hstat = HostStats{};
-    struct rusage ru0 {};
-    (void)getrusage(RUSAGE_THREAD, &ru0);
-    auto wait_tags = [&](int slot, int outer) -> int {
-        volatile const double *tg = tags_h + (size_t)slot * batch * SALSA_TAGS;
-        const double want = (double)outer;
-        const int ntag = 8 + (slot_spec[slot] ? opts->TViters : 0);
-        const auto t_begin = std::chrono::steady_clock::now();
-        auto t_query = t_begin;
-        bool slept = false;
-        HostStats &hs = ctx->hstat;
-        hs.waits += 1;
-        for (unsigned spin = 0;; ++spin) {
-            bool ready = true;
-            for (int b = 0; b < batch && ready; ++b)
-                for (int i = 0; i < ntag && ready; ++i) ready = (tg[(size_t)b * SALSA_TAGS + i] == want);
-            if (ready) {
-                if (spin == 0) hs.ready_at_once += 1;
-                break;
-            }
-            __builtin_ia32_pause();
-            if ((spin & 15) != 15) continue;                       // look at the clock every 16th poll only
-            const auto now = std::chrono::steady_clock::now();
-            if (std::chrono::duration<double, std::micro>(now - t_begin).count() < spin_us) continue;
-            struct timespec ts = {0, 5000};
-            nanosleep(&ts, nullptr);
-            hs.sleeps += 1;
-            slept = true;
-            if (now - t_query > std::chrono::milliseconds(50)) {
-                hs.stream_queries += 1;
-                const hipError_t e = hipStreamQuery(ctx->stream);
-                if (e == hipSuccess) {
-                    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));     // everything has run: the scalars are there
-                    break;
-                }
-                if (e != hipErrorNotReady) return fail_hip(ctx, e, "hipStreamQuery", __FILE__, __LINE__);
-                t_query = std::chrono::steady_clock::now();
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        const double w = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        hs.wait_s += w;
-        if (w > hs.wait_max_s) {
-            hs.wait_max_s = w;
-            hs.wait_max_outer = (double)outer;
-        }
-        if (slept) hs.waits_slept += 1;
-        return 0;
-    };
     // host side of outer iteration `outer`: traces + stopping rule (:444-482)
     auto process = [&](int outer) -> int {
         const int slot = outer & 1;
         SBTV_TRY(read_initial());                                            // objective(1), mses(1): long there by now
         if (pend.valid && pend.outer == outer) SBTV_TRY(flush_pending());     // no later iteration took it along
-        if (slot_tagged[slot]) SBTV_TRY(wait_tags(slot, outer));
+        // until the collector of iteration `outer` has delivered all eight scalars (and the step sums) of every image
+        if (slot_tagged[slot])
+            SBTV_TRY(wait_tags(ctx, tags_h + (size_t)slot * batch * SALSA_TAGS, batch, SALSA_TAGS, 8,
+                               slot_spec[slot] ? opts->TViters : 0, (double)outer));
         else SBTV_TRY(wait_event(ctx, ev_done[slot]));
         if (prox_timed[slot]) {
             float ms = 0.f;
@@ -577,6 +468,10 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
                 if (!frozen[b]) prox_iters_timed += slot_spec[slot] ? (long long)opts->TViters : (long long)scal_h[(size_t)slot * batch + b].pad;
             prox_timed[slot] = false;
         }
+        // optimistic launches: the rule stopped a prox before its last step -> start over, exactly
+        if (slot_spec[slot])
+            SBTV_TRY(spec_stop_rule(ctx, pp, psum_h + (size_t)slot * batch * FSTRIDE, opts->TViters, opts->chambolle_tol,
+                                    frozen.data()));
         const double tnow = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         bool changed = false;
         for (int b = 0; b < batch; ++b) {
@@ -586,24 +481,7 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
             h_nouter[b] = outer;
             double prox_k = s.pad;                   // exact launches: iterations booked by the stop-rule kernels
             if (zero_start && outer == 1) prox_k = 1.0;   // the prox of a zero image: one iteration, not launched
-            if (slot_spec[slot]) {
-                // optimistic launches: cont = (k < MaxIter) & (err > tol)  (chambolle_prox_TV_stop.m:131) over the steps
-                const double *ps = psum_h + ((size_t)slot * batch + b) * FSTRIDE;
-                prox_k = (double)opts->TViters;
-                for (int k = 1; k < opts->TViters; ++k)
-                    if (!(sqrt(ps[k - 1]) > opts->chambolle_tol * SPEC_TOL_GUARD)) {
-                        fired_early = true;          // the rule stopped before the last step: start over, exactly
-                        break;
-                    }
-                if (fired_early) break;
-                // the sums of launches that sum a subset of the pixels are lower bounds: long before they can come near
-                // tol^2 the launches of this solve go back to the full sums (ProxPlan::esub_off)
-                for (int k = 1; k <= opts->TViters && !pp.esub_off; ++k)
-                    if (!(ps[k - 1] > ESUB_MARGIN * opts->chambolle_tol * opts->chambolle_tol)) {
-                        pp.esub_off = 1;
-                        ctx->solve_stats[1] += 1;
-                    }
-            }
+            if (slot_spec[slot]) prox_k = (double)opts->TViters;    // optimistic launches: all steps ran
             prox_iters_run += (long long)prox_k;
             ctx->calls += 2;   // invLS + A (callcounter)
             const double f = 0.5 * (s.resid2 * parseval) + tau[b] * s.tv_u;                  // :444
@@ -630,52 +508,14 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
                 changed = true;
             }
         }
-        if (fired_early) return 0;
-        if (changed && active > 0) {
-            SBTV_HIP(ctx, hipMemcpyAsync(frozen_d, frozen_h, sizeof(int) * batch, hipMemcpyHostToDevice, ctx->stream));
-            // park the frozen images' prox as well (optimistic launches do not re-arm the control blocks)
-            hipLaunchKernelGGL(prox_park_kernel, dim3((batch + 63) / 64), dim3(64), 0, ctx->stream, pp.ctrl, (const int *)frozen_d, batch);
-            SBTV_HIP(ctx, hipGetLastError());
-        }
+        // park the frozen images' prox as well (optimistic launches do not re-arm the control blocks)
+        if (changed && active > 0) SBTV_TRY(upload_frozen(ctx, frozen_h, frozen_d, batch, pp.ctrl));
         return 0;
     };
 
-    int rc = 0, enq = 0, done = 0;
-    while (active > 0 && done < maxiter) {
-        // keep up to 1 + lag iterations in flight
-        while (rc == 0 && enq < maxiter && enq - done <= lag && active > 0) {
-            const auto te = std::chrono::steady_clock::now();
-            rc = enqueue(++enq);
-            const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - te).count();
-            ctx->hstat.enqueue_s += d;
-            if (d > ctx->hstat.enqueue_max_s) ctx->hstat.enqueue_max_s = d;
-        }
-        if (rc != 0) break;
-        rc = process(++done);
-        if (rc != 0 || fired_early) break;
-    }
-    if (rc != 0) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if (fired_early) {
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->calls = calls_at_entry;
-        ctx->solve_stats[0] += 1;
-        sbtv_salsa_opts exact = *opts;
-        exact.speculate = (opts->speculate & 1) | 2;
-        return sbtv_SALSA_v2(ctx, y, M, N, batch, taps, taille, tau, mu, &exact, true_x, x_init, x_out, objective, distance,
-                             times, mses, numA, numAt, n_outer, flags);
-    }
+    int done = 0;
+    SBTV_TRY(pipelined_loop(ctx, &done, maxiter, lag, true, enqueue, process, [&] { return active > 0; }));
     SBTV_TRY(read_initial());
-    {
-        struct rusage ru1 {};
-        (void)getrusage(RUSAGE_THREAD, &ru1);
-        ctx->hstat.nvcsw = (double)(ru1.ru_nvcsw - ru0.ru_nvcsw);
-        ctx->hstat.nivcsw = (double)(ru1.ru_nivcsw - ru0.ru_nivcsw);
-        ctx->hstat.minflt = (double)(ru1.ru_minflt - ru0.ru_minflt);
-        ctx->hstat.majflt = (double)(ru1.ru_majflt - ru0.ru_majflt);
-    }
     SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     if (x_out && nox) {
         // image b's result is g + bu of ITS last processed iteration (x itself was never stored)
@@ -708,21 +548,50 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
         }
     }
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the one synchronisation of the call
-    {
-        float ms = 0.f;
-        SBTV_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        ctx->timing[0] = ms;
-        // time inside the Chambolle launches: measured on the sampled iterations, scaled to all of them
-        ctx->timing[1] = prox_iters_timed > 0 ? ms_prox * ((double)prox_iters_run / (double)prox_iters_timed) : 0.0;
-        ctx->timing[2] = (double)prox_iters_run / batch;      // Chambolle iterations (image-averaged)
-        ctx->timing[3] = 40.0 * (double)P * (double)prox_iters_run;
-    }
+    // time inside the Chambolle launches: measured on the sampled iterations, scaled to all of them
+    SBTV_TRY(loop_timing(ctx, prox_iters_timed > 0 ? ms_prox * ((double)prox_iters_run / (double)prox_iters_timed) : 0.0,
+                         prox_iters_run, batch, P));
     for (int b = 0; b < batch; ++b) {
         if (numA) numA[b] = h_numA[b];
         if (numAt) numAt[b] = h_numAt[b];
         if (n_outer) n_outer[b] = h_nouter[b];
     }
-    return canary_epilogue(ctx, 0);
+    return 0;
 }
 
-}  // extern "C"
+int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                  const double *tau, const double *mu, const sbtv_salsa_opts *opts, const double *true_x,
+                  const double *x_init, double *x_out, double *objective, double *distance, double *times,
+                  double *mses, int *numA, int *numAt, int *n_outer, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!y || !tau || !mu || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SALSA_v2: missing required argument");
+    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
+    if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
+    if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
+        return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
+    if (opts->initialization == 33333 && !x_init) return fail(ctx, SBTV_ERR_INIT, "Initialization = array but x_init is NULL");
+    if (opts->TViters <= 0) return fail(ctx, SBTV_ERR_MAXITER, "SALSA_v2: TViters must be positive");
+    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    for (int b = 0; b < batch; ++b)
+        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_MISSING_LS, "(A^T A + mu I)^(-1) must be specified: mu must be > 0");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    // a batch: the images are independent (each stops by its own rule) -> two lanes of this context, group.hip
+    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {
+        LaneCall lc(ctx, lg);
+        return lc.done(salsa_sharded(lg, y, M, N, batch, taps, taille, tau, mu, opts, true_x, x_init, x_out, objective,
+                                     distance, times, mses, numA, numAt, n_outer, flags), batch);
+    }
+    // start of the device-side clock of the call (sbtv_last_timing[0]): recorded while the stream is still idle - an event
+    // record between two kernels would cost the stream 5-6 us
+    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    const size_t cnt = (size_t)M * N * batch;
+    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "salsa.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "salsa.true", true_x, cnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "salsa.xinit", x_init, cnt, flags, &xi));
+    // optimistic prox launches first, unless bit 1 of `speculate` asks for exact ones; repeated exactly if the rule fired
+    return canary_epilogue(ctx, solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
+        return salsa_solve(ctx, yd, M, N, batch, taps, taille, tau, mu, opts, td, xi, x_out, objective, distance, times, mses,
+                           numA, numAt, n_outer, flags, spec);
+    }));
+}

@@ -54,12 +54,6 @@ __global__ __launch_bounds__(256) void sapg_collect_kernel(const double *__restr
     if (threadIdx.x == 0) out[(q < 3) ? (size_t)b * 3 + q : 3 * (size_t)batch + b] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// images the host has frozen: their prox control block is parked (done = 1)
-__global__ void fista_park_kernel(ProxCtrl *__restrict__ ctrl, const int *__restrict__ frozen, int batch) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch && frozen[b]) ctrl[b].done = 1;
-}
-
 // FISTA scalars of one iteration in one launch: block (q, b): q < 3 rows-kernel accumulators [batch][3][nrb] ->
 // out[b*3+q]; q = 3..5 momentum-kernel sums [batch][3][npb] (may be null) -> out[3*batch + b*3 + (q-3)];
 // q = 6 periodic-TV partials [batch][ntv] -> out[6*batch + b].  `out` is the device view of pinned host memory.
@@ -74,39 +68,18 @@ __global__ __launch_bounds__(256) void fista_collect_kernel(const double *__rest
     double *__restrict__ tags = reinterpret_cast<double *>(tags_addr);
     __shared__ double red[4];
     const int q = blockIdx.x, b = blockIdx.y;
+    const double *p = nullptr;
+    int n = 0;
+    size_t o, t = (size_t)b * (8 + FSTRIDE) + q;
+    double s = 0.0;
     if (q >= 7) {
         // optimistic prox launches (prox_iterate, spec): block 7 + s totals the error partials of Chambolle step s into
         // out[8*batch + b*FSTRIDE + s]; the host applies the stop rule of chambolle_prox_TV_stop.m:131 over the steps
         const int st = q - 7;
-        const double *pp = ppart + ((size_t)b * FSTRIDE + st) * pnblk;
-        double a = 0.0;
-        constexpr int NB = 8;
-        for (int base = 0; base < pnblk; base += 256 * NB) {
-            double v[NB];
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                const int i = base + r * 256 + (int)threadIdx.x;
-                v[r] = (i < pnblk) ? __hip_atomic_load(pp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            }
-#pragma unroll
-            for (int r = 0; r < NB; ++r) a += v[r];
-        }
-        for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            out[8 * (size_t)batch + (size_t)b * FSTRIDE + st] = (red[0] + red[1]) + (red[2] + red[3]);
-            if (tags) {
-                __threadfence_system();
-                __hip_atomic_store(&tags[(size_t)b * (8 + FSTRIDE) + 8 + st], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        return;
-    }
-    const double *p;
-    int n;
-    size_t o;
-    if (q < 3) {
+        s = step_sum_part(ppart + ((size_t)b * FSTRIDE + st) * pnblk, pnblk);
+        o = 8 * (size_t)batch + (size_t)b * FSTRIDE + st;
+        t = (size_t)b * (8 + FSTRIDE) + 8 + st;
+    } else if (q < 3) {
         p = acc + ((size_t)b * 3 + q) * nrb;
         n = nrb;
         o = (size_t)b * 3 + q;
@@ -119,7 +92,6 @@ __global__ __launch_bounds__(256) void fista_collect_kernel(const double *__rest
         n = ntv;
         o = 6 * (size_t)batch + b;
     }
-    double s = 0.0;
     if (p)
         for (int i = threadIdx.x; i < n; i += 256) s += p[i];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
@@ -129,7 +101,7 @@ __global__ __launch_bounds__(256) void fista_collect_kernel(const double *__rest
         out[o] = (red[0] + red[1]) + (red[2] + red[3]);
         if (tags) {
             __threadfence_system();
-            __hip_atomic_store(&tags[(size_t)b * (8 + FSTRIDE) + q], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&tags[t], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
@@ -418,35 +390,21 @@ int sbtv_max_eigenval(sbtv_ctx *ctx, const double *taps, int taille, const doubl
     return canary_epilogue(ctx, 0);
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------
 // a-8: FISTA with Psi = cold-start Chambolle, Phi = periodic TVnorm
 // ---------------------------------------------------------------------------
-int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, const double *taps, int taille,
-                  const double *tau, double L, int prox_iters, int stopcriterion, double tolerance, int maxiters,
-                  int zero_start, const double *true_x, double *x_out, double *objective, double *mses, int *n_iter,
-                  int flags) {
-    if (!ctx) return SBTV_ERR_BADARG;
-    if (!bimg || !taps || !tau || !true_x || batch < 1 || maxiters < 1 || !(L > 0.0))
-        return fail(ctx, SBTV_ERR_BADARG, "fista_tv: bad arguments (b, taps, tau, true are required)");
-    if (stopcriterion < 1 || stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Invalid stopping criterion!");
-    if (prox_iters <= 0) return fail(ctx, SBTV_ERR_MAXITER, "fista_tv: prox_iters must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
-    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
-        LaneCall lc(ctx, lg);
-        return lc.done(fista_sharded(lg, bimg, M, N, batch, taps, taille, tau, L, prox_iters, stopcriterion, tolerance, maxiters,
-                                     zero_start, true_x, x_out, objective, mses, n_iter, flags), batch);
-    }
+// one solve on the staged inputs (device pointers bd, td); spec_wanted: optimistic prox launches
+static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch, const double *taps, int taille,
+                       const double *tau, double L, int prox_iters, int stopcriterion, double tolerance, int maxiters,
+                       int zero_start, const double *td, double *x_out, double *objective, double *mses, int *n_iter,
+                       int flags, bool spec_wanted) {
     FftPlan fp;
     SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
     ProxPlan pp;
     SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
     const size_t P = (size_t)M * N, cnt = P * batch;
-    const double *bd = nullptr, *td = nullptr;
-    SBTV_TRY(stage_in(ctx, "fista.b", bimg, cnt, flags, &bd));
-    SBTV_TRY(stage_in(ctx, "fista.true", true_x, cnt, flags, &td));
     // x is double-buffered by iteration parity: the host evaluates the stopping rule one iteration late while the next
     // iteration already runs, and the iterate of a stopping iteration must still be intact then
     double *xb[2] = {nullptr, nullptr}, *y = nullptr, *grad = nullptr, *xfinal = nullptr;
@@ -484,17 +442,10 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
     constexpr int FT = 8 + FSTRIDE;
     const size_t slot_n = (size_t)FT * batch;
     double *scal_base_h = nullptr, *scal_base_hd = nullptr;
-    int *frozen_h = nullptr;
-    {
-        void *pz = nullptr, *dp = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 4 * slot_n + sizeof(int) * batch, &pz));
-        scal_base_h = static_cast<double *>(pz);
-        SBTV_HIP(ctx, hipHostGetDevicePointer(&dp, pz, 0));
-        scal_base_hd = static_cast<double *>(dp);
-        for (size_t i = 0; i < 2 * slot_n; ++i) scal_base_h[2 * slot_n + i] = 0.0;      // tags: no iteration yet
-        frozen_h = reinterpret_cast<int *>(scal_base_h + 4 * slot_n);
-        for (int b = 0; b < batch; ++b) frozen_h[b] = 0;
-    }
+    SBTV_TRY(pinned_get(ctx, sizeof(double) * 4 * slot_n + sizeof(int) * batch, &scal_base_h, &scal_base_hd));
+    for (size_t i = 0; i < 2 * slot_n; ++i) scal_base_h[2 * slot_n + i] = 0.0;      // tags: no iteration yet
+    int *frozen_h = reinterpret_cast<int *>(scal_base_h + 4 * slot_n);
+    for (int b = 0; b < batch; ++b) frozen_h[b] = 0;
     double *tags_base_h = scal_base_h + 2 * slot_n, *tags_base_hd = scal_base_hd + 2 * slot_n;
     const double inv_scale = 1.0 / ((double)fp.n1 * N), parseval = 1.0 / ((double)M * N);
     SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
@@ -525,12 +476,11 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
     // momentum-kernel sums when given) straight into pinned host memory
     // Optimistic prox launches (no stop-rule kernels, no redo pass: 6 launches less per iteration); the host applies the
     // rule over the prox_iters step sums when it reads the iteration's scalars and, should it have stopped early, repeats
-    // the whole call with exact launches (flag SBTV_FISTA_EXACT_PROX), so the result is always that of the exact rule.
+    // the whole solve with exact launches, so the result is always that of the exact rule.
     // (not when a device-resident x_out overlaps an input: frozen images are copied into x_out while the loop runs, and a
-    // repeated call would then start from damaged inputs - such a call takes the exact launches from the start)
-    auto overlaps_out = [&](const double *p) { return p && x_out && (p < x_out + cnt) && (x_out < p + cnt); };
-    const bool out_aliases_input = (flags & SBTV_DEVICE_PTRS) && (overlaps_out(bimg) || overlaps_out(true_x));
-    const bool prox_spec = !(flags & SBTV_FISTA_EXACT_PROX) && !out_aliases_input && prox_spec_ok(pp, y, x, prox_iters);
+    // repeated solve would then start from damaged inputs - such a call takes the exact launches from the start)
+    const bool out_aliases_input = (flags & SBTV_DEVICE_PTRS) && (overlaps(bd, x_out, cnt) || overlaps(td, x_out, cnt));
+    const bool prox_spec = spec_wanted && !out_aliases_input && prox_spec_ok(pp, y, x, prox_iters);
     bool prox_was_spec = false;
     // objective / sums of iterate `xk` of iteration k -> pinned slot k & 1, tagged with k
     auto objective_of_x = [&](const double *xk, int k, const int *frozen, const double *mom_partials) -> int {
@@ -557,38 +507,6 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
                            batch, (const double *)pp.partials, pp.fnblk,
                            (unsigned long long)(uintptr_t)(tags_base_hd + slot * slot_n), (double)k);
         SBTV_HIP(ctx, hipGetLastError());
-        return 0;
-    };
-    // wait until the collector of iteration k has delivered every scalar: poll the tags in pinned memory (no HIP call in
-    // the normal case: a stream query would cost the stream a marker packet); ask the stream only after 50 ms
-    auto wait_tags = [&](int k, bool spec) -> int {
-        volatile const double *tg = tags_base_h + (size_t)(k & 1) * slot_n;
-        const double want = (double)k;
-        auto t_begin = std::chrono::steady_clock::now();
-        for (unsigned spin = 0;; ++spin) {
-            bool ready = true;
-            for (int b = 0; b < batch && ready; ++b) {
-                for (int i = 0; i < 7 && ready; ++i) ready = (tg[(size_t)b * FT + i] == want);
-                for (int i = 0; spec && i < prox_iters && ready; ++i) ready = (tg[(size_t)b * FT + 8 + i] == want);
-            }
-            if (ready) break;
-            if (spin < 200) {
-                __builtin_ia32_pause();
-                continue;
-            }
-            struct timespec ts = {0, 5000};
-            nanosleep(&ts, nullptr);
-            if ((spin & 255) == 0 && std::chrono::steady_clock::now() - t_begin > std::chrono::milliseconds(50)) {
-                const hipError_t e = hipStreamQuery(ctx->stream);
-                if (e == hipSuccess) {
-                    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    break;
-                }
-                if (e != hipErrorNotReady) return fail_hip(ctx, e, "hipStreamQuery", __FILE__, __LINE__);
-                t_begin = std::chrono::steady_clock::now();
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
         return 0;
     };
     std::vector<double> obj_prev(batch, 0.0);
@@ -624,7 +542,7 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
         return !(e && e[0] == '0');
     }();
     const bool fused_step = fused_wanted && prox_spec && fft_cols_inv_step_ok(fp);
-    if (fused_step) SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, prox_iters, 1e-3, 0.249, false, frozen_d));
+    if (fused_step) SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, prox_iters, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, frozen_d));
     auto enqueue = [&](int k) -> int {
         const double t_old = t_enq;
         double *xk = xb[k & 1];
@@ -647,12 +565,12 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
             } else {
                 SBTV_TRY(fft_cols_inv_f(ctx, fp, S, grad, inv_scale, frozen_d));
                 // the gradient-step kernel also re-arms the control blocks of the cold-start prox that follows
-                const ProxArm arm{pp.ctrl, lam_d, prox_iters, 1e-3, 0.249, frozen_d};
+                const ProxArm arm{pp.ctrl, lam_d, prox_iters, CHAMBOLLE_TOL, CHAMBOLLE_TAU, frozen_d};
                 if (batch <= 256) {
                     SBTV_TRY(axpy(ctx, y, grad, 1.0 / L, cnt, &arm, batch));
                 } else {
                     SBTV_TRY(axpy(ctx, y, grad, 1.0 / L, cnt));
-                    SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, prox_iters, 1e-3, 0.249, false, frozen_d));
+                    SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, prox_iters, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, frozen_d));
                 }
             }
         }
@@ -665,25 +583,14 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
         SBTV_TRY(objective_of_x(xk, k, frozen_d, momp));
         return 0;
     };
-    bool fired = false;
     auto process = [&](int k) -> int {
-        SBTV_TRY(wait_tags(k, slot_spec[k & 1]));
+        // until the collector of iteration k has delivered every scalar (and the step sums) of every image
+        SBTV_TRY(wait_tags(ctx, tags_base_h + (size_t)(k & 1) * slot_n, batch, FT, 7, slot_spec[k & 1] ? prox_iters : 0,
+                           (double)k));
         const double *sc = scal_base_h + (size_t)(k & 1) * slot_n;
-        if (slot_spec[k & 1]) {
-            // cont = (k < MaxIter) & (err > tol)  (chambolle_prox_TV_stop.m:131; tol 1e-3 as armed above)
-            for (int b = 0; b < batch && !fired; ++b) {
-                if (frozen[b]) continue;
-                const double *ps = sc + 8 * (size_t)batch + (size_t)b * FSTRIDE;
-                for (int kk = 1; kk < prox_iters && !fired; ++kk) fired = !(sqrt(ps[kk - 1]) > 1e-3 * SPEC_TOL_GUARD);
-                // (lower-bound sums of the subset launches: back to the full sums long before they can reach tol^2)
-                for (int kk = 1; kk <= prox_iters && !pp.esub_off; ++kk)
-                    if (!(ps[kk - 1] > ESUB_MARGIN * 1e-6)) {
-                        pp.esub_off = 1;
-                        ctx->solve_stats[1] += 1;
-                    }
-            }
-            if (fired) return 0;
-        }
+        // the stop rule of the optimistic prox with the tolerance armed above: fired before the last step -> start over
+        if (slot_spec[k & 1])
+            SBTV_TRY(spec_stop_rule(ctx, pp, sc + 8 * (size_t)batch, prox_iters, CHAMBOLLE_TOL, frozen.data()));
         bool changed = false;
         for (int b = 0; b < batch; ++b) {
             if (frozen[b]) continue;
@@ -709,35 +616,12 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
                                              hipMemcpyDeviceToDevice, ctx->stream));
             }
         }
-        if (changed && active > 0) {
-            SBTV_HIP(ctx, hipMemcpyAsync(frozen_d, frozen_h, sizeof(int) * batch, hipMemcpyHostToDevice, ctx->stream));
-            if (fused_step) {      // nothing re-arms the control blocks per iteration: park the frozen images' prox
-                hipLaunchKernelGGL(fista_park_kernel, dim3((batch + 63) / 64), dim3(64), 0, ctx->stream, pp.ctrl,
-                                   (const int *)frozen_d, batch);
-                SBTV_HIP(ctx, hipGetLastError());
-            }
-        }
+        // with the fused step nothing re-arms the control blocks per iteration: park the frozen images' prox
+        if (changed && active > 0) SBTV_TRY(upload_frozen(ctx, frozen_h, frozen_d, batch, fused_step ? pp.ctrl : nullptr));
         return 0;
     };
-    {
-        int rc = 0, enq = 1, done = 1;
-        while (active > 0 && done < maxiters) {
-            while (rc == 0 && enq < maxiters && enq - done <= lag && active > 0) rc = enqueue(++enq);
-            if (rc != 0) break;
-            rc = process(++done);
-            if (rc != 0 || fired) break;
-        }
-        if (rc != 0) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return rc;
-        }
-        if (fired) {
-            // the stop rule fired inside an optimistic prox: repeat the whole call with exact launches
-            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            return sbtv_fista_tv(ctx, bimg, M, N, batch, taps, taille, tau, L, prox_iters, stopcriterion, tolerance, maxiters,
-                                 zero_start, true_x, x_out, objective, mses, n_iter, flags | SBTV_FISTA_EXACT_PROX);
-        }
-    }
+    int done = 1;
+    SBTV_TRY(pipelined_loop(ctx, &done, maxiters, lag, true, enqueue, process, [&] { return active > 0; }));
     for (int b = 0; b < batch; ++b)
         if (!frozen[b])
             SBTV_HIP(ctx, hipMemcpyAsync(xfinal + (size_t)b * P, xb[h_niter[b] & 1] + (size_t)b * P, sizeof(double) * P,
@@ -746,14 +630,41 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n_iter)
         for (int b = 0; b < batch; ++b) n_iter[b] = h_niter[b];
-    return canary_epilogue(ctx, 0);
+    return 0;
+}
+
+int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, const double *taps, int taille,
+                  const double *tau, double L, int prox_iters, int stopcriterion, double tolerance, int maxiters,
+                  int zero_start, const double *true_x, double *x_out, double *objective, double *mses, int *n_iter,
+                  int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!bimg || !taps || !tau || !true_x || batch < 1 || maxiters < 1 || !(L > 0.0))
+        return fail(ctx, SBTV_ERR_BADARG, "fista_tv: bad arguments (b, taps, tau, true are required)");
+    if (stopcriterion < 1 || stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Invalid stopping criterion!");
+    if (prox_iters <= 0) return fail(ctx, SBTV_ERR_MAXITER, "fista_tv: prox_iters must be positive");
+    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    if (((size_t)M * N) & 1)
+        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
+        LaneCall lc(ctx, lg);
+        return lc.done(fista_sharded(lg, bimg, M, N, batch, taps, taille, tau, L, prox_iters, stopcriterion, tolerance, maxiters,
+                                     zero_start, true_x, x_out, objective, mses, n_iter, flags), batch);
+    }
+    const size_t cnt = (size_t)M * N * batch;
+    const double *bd = nullptr, *td = nullptr;
+    SBTV_TRY(stage_in(ctx, "fista.b", bimg, cnt, flags, &bd));
+    SBTV_TRY(stage_in(ctx, "fista.true", true_x, cnt, flags, &td));
+    // optimistic prox launches first, unless SBTV_FISTA_EXACT_PROX asks for exact ones; repeated exactly if the rule fired
+    return canary_epilogue(ctx, solve_with_exact_repeat(ctx, !(flags & SBTV_FISTA_EXACT_PROX), [&](bool spec) {
+        return fista_solve(ctx, bd, M, N, batch, taps, taille, tau, L, prox_iters, stopcriterion, tolerance, maxiters,
+                           zero_start, td, x_out, objective, mses, n_iter, flags, spec);
+    }));
 }
 
 // ---------------------------------------------------------------------------
 // a-6: plain MYULA chain at fixed parameters (SALSA/myula.m:1-22)
 // ---------------------------------------------------------------------------
-}  // extern "C"
-
 namespace sbtv {
 // iterations of the accumulator: first, first + thin, ... <= last; 0 when iteration ii is not one of them
 static inline int mom_sample_of(const MomReq *mr, int ii) {
@@ -830,8 +741,8 @@ static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     SBTV_HIP(ctx, hipMemcpyAsync(X, yd, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));   // x = op.y  (:3,11)
     if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));            // iteration 1 = y
     const double inv_scale = 1.0 / ((double)fp.n1 * N);
-    SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, 1e-3, 0.249, false, nullptr));
-    const ProxArm arm{pp.ctrl, lam_d, chambolleit, 1e-3, 0.249, nullptr};
+    SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, nullptr));
+    const ProxArm arm{pp.ctrl, lam_d, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, nullptr};
     for (int ii = 2; ii <= samples - 1; ++ii) {             // :13
         const size_t step = (size_t)(ii - 2);
         SBTV_TRY(prox_iterate(ctx, pp, X, chambolleit, prox, true));                         // :15
@@ -1029,18 +940,8 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     const int nrb = fft_rows_blocks(fp);
     double *acc = nullptr;
     SBTV_TRY(ws_get_t(ctx, "sapg.acc", (size_t)batch * 3 * nrb, &acc));
-    double *scal_h = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * (4 * batch + 3 * t2 * nspec + 2 * batch + 1), &pz));
-        scal_h = static_cast<double *>(pz);
-    }
-    double *scal_hd = nullptr;                        // the same pinned scalars as the device sees them
-    {
-        void *dp = nullptr;
-        SBTV_HIP(ctx, hipHostGetDevicePointer(&dp, scal_h, 0));
-        scal_hd = static_cast<double *>(dp);
-    }
+    double *scal_h = nullptr, *scal_hd = nullptr;      // pinned scalars, as the host and as the device see them
+    SBTV_TRY(pinned_get(ctx, sizeof(double) * (4 * batch + 3 * t2 * nspec + 2 * batch + 1), &scal_h, &scal_hd));
     double *par_h = scal_h + 4 * (size_t)batch;       // pinned staging for the per-iteration parameter upload
     const double inv_scale = 1.0 / ((double)fp.n1 * N), parseval = 1.0 / ((double)M * N);
     const double lamb = op->lambda, gam = op->gamma;
@@ -1182,7 +1083,7 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     // X <- |X + gam (prox - X)/lamb - gam gradF + sqrt(2 gam) Z|  (:80-81,160-161).  With the device generator the
     // normals are drawn inside the step kernel (no Z array is written or read); injected noise goes through Z.
     // The step kernel also re-arms the prox control blocks for the cold-start prox that always follows it.
-    const ProxArm arm{pp.ctrl, lam_d, op->chambolleit, 1e-3, 0.249, nullptr};
+    const ProxArm arm{pp.ctrl, lam_d, op->chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, nullptr};
     // Posterior moments: the step of SAPG iteration main_ii (0 in the warm-up) also updates the running mean / M2 when
     // the iteration is selected; a captured iteration (in_graph) decides that on the device from u.it[0] == ii.
     int main_ii = 0;
@@ -1224,7 +1125,7 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     }();
     const bool defer_rule = prox_mb && defer_wanted;
     auto do_prox = [&](bool armed) -> int {
-        if (!armed) SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, op->chambolleit, 1e-3, 0.249, false, nullptr));
+        if (!armed) SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, op->chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, nullptr));
         SBTV_TRY(prox_iterate(ctx, pp, X, op->chambolleit, prox, true, (armed && prox_mb) ? (defer_rule ? 3 : 2) : 0));
         return 0;
     };
@@ -1236,14 +1137,8 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     const bool params_move = !(op->fix_p[0] && (npar < 2 || op->fix_p[1]));
     // (the host-side loop has no device iteration counter to select the moments' samples from: it launches eagerly then)
     bool use_graph = (noise == nullptr) && graph_wanted(cnt) && !(mom && !dev_loop);
-    hipGraphExec_t g_warm = nullptr, g_main = nullptr;
-    struct GraphGuard {
-        hipGraphExec_t *a, *b;
-        ~GraphGuard() {
-            if (*a) (void)hipGraphExecDestroy(*a);
-            if (*b) (void)hipGraphExecDestroy(*b);
-        }
-    } graph_guard{&g_warm, &g_main};
+    GraphExecs graphs;
+    hipGraphExec_t &g_warm = graphs.g[0], &g_main = graphs.g[1];
     auto graph_body = [&](bool main_loop) -> int {
         SBTV_HIP(ctx, hipMemcpyAsync(par, par_h, sizeof(double) * npar_all, hipMemcpyHostToDevice, ctx->stream));
         if (main_loop && params_move) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <map>
 #include <string>
 #include <vector>
@@ -191,6 +192,18 @@ inline int ws_get_t(sbtv_ctx *ctx, const char *name, size_t count, T **out) {
     return rc;
 }
 int pinned_get(sbtv_ctx *ctx, size_t bytes, void **out);
+// the same pinned block as the host and as the device see it
+template <typename T>
+inline int pinned_get(sbtv_ctx *ctx, size_t bytes, T **host, T **dev) {
+    void *h = nullptr, *d = nullptr;
+    SBTV_TRY(pinned_get(ctx, bytes, &h));
+    SBTV_HIP(ctx, hipHostGetDevicePointer(&d, h, 0));
+    *host = static_cast<T *>(h);
+    *dev = static_cast<T *>(d);
+    return 0;
+}
+// do the arrays [a, a + n) and [b, b + n) overlap (null: no)
+inline bool overlaps(const double *a, const double *b, size_t n) { return a && b && a < b + n && b < a + n; }
 // end of a C-ABI call: with SBTV_CANARY=1 verify every guard band (one tiny kernel + a sync), else return rc
 int canary_epilogue(sbtv_ctx *ctx, int rc);
 int canary_verify(sbtv_ctx *ctx, int *nbuf, int *nbad, std::string *first_bad);
@@ -370,14 +383,62 @@ int coral_sharded(::sbtv_group *g, const double *y, int M, int N, int n_items, c
                   double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer,
                   int flags);
 
-// low-latency host waits of the solver loops (poll, then block; ctx.hip)
+// ----------------------------- host side of the solver loops (loop.hip) -----
+// low-latency host waits of the solver loops (poll, then block)
 int wait_event(sbtv_ctx *ctx, hipEvent_t ev);
 int wait_stream(sbtv_ctx *ctx);
+// waits until the completion tags [batch][stride] in pinned memory hold `seq`: scalar tags 0..nscal-1 and step-sum tags
+// 8..8+nstep-1 of every image (sbtv_last_host_stats records the wait)
+int wait_tags(sbtv_ctx *ctx, const double *tags, int batch, int stride, int nscal, int nstep, double seq);
 
-// hipGraph replay of launch-bound iteration bodies (ctx.hip)
+// hipGraph replay of launch-bound iteration bodies
 bool graph_wanted(size_t total_px);
 int graph_begin(sbtv_ctx *ctx);
 int graph_end(sbtv_ctx *ctx, int body_rc, hipGraphExec_t *exec);
+// the captured graph execs of one call: destroyed on every return path
+struct GraphExecs {
+    hipGraphExec_t g[2] = {nullptr, nullptr};
+    ~GraphExecs() {
+        for (auto e : g)
+            if (e) (void)hipGraphExecDestroy(e);
+    }
+};
+
+// sbtv_last_timing of a solver loop: the device time between ctx->ev[0] and ctx->ev[1] (both complete), the time inside the
+// Chambolle launches, the Chambolle iterations per image and what they move (40 bytes per pixel and iteration)
+int loop_timing(sbtv_ctx *ctx, double prox_ms, long long prox_iters, int batch, size_t P);
+// sbtv_last_host_stats of a solver loop: begin clears ctx->hstat, end books what the operating system did to the thread
+void host_stats_begin(sbtv_ctx *ctx);
+void host_stats_end(sbtv_ctx *ctx);
+
+// The pipelined host loop of the solvers: iterations *done + 1 .. maxiter, at most 1 + lag of them enqueued, processed in
+// order.  It stops after maxiter, when active() turns false, or when enqueue / process return non-zero (an error, or
+// SOLVE_RESTART_EXACT from spec_stop_rule); the stream is then drained.  *done: the last iteration processed.  stats: the
+// loop keeps sbtv_last_host_stats (enqueue times here, waits in wait_tags).
+template <class Enqueue, class Process, class Active>
+int pipelined_loop(sbtv_ctx *ctx, int *done, int maxiter, int lag, bool stats, Enqueue &&enqueue, Process &&process,
+                   Active &&active) {
+    if (stats) host_stats_begin(ctx);
+    int rc = 0, enq = *done;
+    while (rc == 0 && active() && *done < maxiter) {
+        while (rc == 0 && enq < maxiter && enq - *done <= lag) {
+            const auto te = std::chrono::steady_clock::now();
+            rc = enqueue(++enq);
+            const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - te).count();
+            if (stats) {
+                ctx->hstat.enqueue_s += d;
+                if (d > ctx->hstat.enqueue_max_s) ctx->hstat.enqueue_max_s = d;
+            }
+        }
+        if (rc == 0) rc = process(++*done);
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    if (stats) host_stats_end(ctx);
+    return 0;
+}
 
 // ----------------------------- TV kernels (tv.hip) --------------------------
 struct ProxPlan {
@@ -453,6 +514,32 @@ int prox_iterate(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, int maxiter
 int prox_reserve_pairs(sbtv_ctx *ctx, ProxPlan *pl, int pairs);
 int prox_launches(const ProxPlan &pl, int maxiter);
 bool prox_spec_ok(const ProxPlan &pl, const double *g, const double *f_out, int maxiter);
+// defaults of chambolle_prox_TV_stop.m:77-78, which FISTA, MYULA and SAPG call without options
+constexpr double CHAMBOLLE_TOL = 1e-3, CHAMBOLLE_TAU = 0.249;
+
+// ---- optimistic prox launches in the solver loops (loop.hip)
+// internal status: the Chambolle stop rule fired inside an optimistic prox, the solve has to be repeated exactly
+constexpr int SOLVE_RESTART_EXACT = 12345;
+// cont = (k < MaxIter) & (err > tol)  (chambolle_prox_TV_stop.m:131) over the K step sums [pp.batch][FSTRIDE] of an
+// optimistic prox on plan pp (images with frozen[b] set are skipped): SOLVE_RESTART_EXACT when it stopped an image before
+// the last step.  Otherwise the plan's launches go back to the full error sums once the (lower-bound) subset sums come
+// within ESUB_MARGIN of tol^2 (ProxPlan::esub_off, counted in solve_stats[1]).
+int spec_stop_rule(sbtv_ctx *ctx, ProxPlan &pp, const double *stepsums, int K, double tol, const int *frozen = nullptr);
+// Runs body(spec) - optimistic prox launches when spec - and, should it return SOLVE_RESTART_EXACT, rewinds the call
+// counter, counts the repeat (solve_stats[0]) and runs body(false) with exact launches: the result is always that of the
+// exact rule.
+template <class Body>
+int solve_with_exact_repeat(sbtv_ctx *ctx, bool spec, Body &&body) {
+    const long long calls0 = ctx->calls;
+    const int rc = body(spec);
+    if (rc != SOLVE_RESTART_EXACT) return rc;
+    ctx->calls = calls0;
+    ctx->solve_stats[0] += 1;
+    return body(false);
+}
+// images the host has frozen: their flags go up from (pinned) frozen_h to frozen_d, then the prox control blocks of
+// park_ctrl (null: none) are parked (done = 1)
+int upload_frozen(sbtv_ctx *ctx, const int *frozen_h, int *frozen_d, int batch, ProxCtrl *park_ctrl);
 // f = g - lambda * div(p)
 int prox_finish(sbtv_ctx *ctx, const ProxPlan &pl, const double *g, double *f);
 // periodic TV norm of x -> out_dev[batch] (device)

@@ -13,10 +13,10 @@ from .operators import BlurOperator, _Adjoint, _InvLS
 from .tv import _parse_varargin
 
 _CSALSA_OPTIONS = {"P", "PT", "PSI", "PHI", "TVINITIALIZATION", "TVITERS", "STOPCRITERION", "TOLERANCEA", "MAXITERA",
-                   "INITIALIZATION", "TRUE_X", "AT", "LS", "VERBOSE", "CONTINUATIONFACTOR", "EPSILON", "SEED"}
+                   "INITIALIZATION", "TRUE_X", "AT", "LS", "VERBOSE", "CONTINUATIONFACTOR", "EPSILON", "SEED", "SPECULATE"}
 _CORAL_OPTIONS = {"W", "WT", "P1", "P1T", "P2", "P2T", "PSI1", "PHI1", "TVINITIALIZATION1", "TVITERS1", "PSI2", "PHI2",
                   "TVINITIALIZATION2", "TVITERS2", "MU1", "MU2", "STOPCRITERION", "TOLERANCEA", "INNERITERS",
-                  "MAXITERA", "INITIALIZATION", "TRUE_X", "AT", "VERBOSE", "LS", "SEED"}
+                  "MAXITERA", "INITIALIZATION", "TRUE_X", "AT", "VERBOSE", "LS", "SEED", "SPECULATE"}
 
 _vp = L.vptr
 
@@ -34,6 +34,8 @@ def _common(y, A, opts, ctx, default_stop):
         raise L.SbtvError(-6, "Unknown stopping criterion")
     so.maxiter = int(opts.get("MAXITERA", 10000))
     so.tolA = float(opts.get("TOLERANCEA", 0.001))
+    # extension (no counterpart in the reference): sbtv_salsa_opts.speculate, bit 0 host-side lag, bit 1 exact prox launches
+    so.speculate = int(opts.get("SPECULATE", so.speculate))
     yi = L.Images(y)
     init = opts.get("INITIALIZATION", 0)
     xinit = None

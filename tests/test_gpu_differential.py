@@ -103,6 +103,40 @@ def test_salsa_small_lambda_rule_fires_inside_the_prox(ctx):
     assert fired >= 4, "the configurations are meant to make the rule fire inside a prox (it did in %d of 10)" % fired
 
 
+@pytest.mark.parametrize("solver", ["fista", "csalsa", "coral", "coral_separate"])
+def test_rule_firing_inside_the_prox_restarts_once_with_the_exact_bits(ctx, solver):
+    """A nearly flat observation (as in test_gpu_salsa.py): the Chambolle rule stops every prox at k = 1, so the first
+    optimistic iteration reports it, the solve is repeated once with exact launches (counted in exact_restarts) and its
+    result is, bit for bit, that of a call that used exact launches from the start."""
+    import sbtv
+    M = N = 64
+    y = np.full((M, N), 120.0)
+    y[10:20, 30:40] += 1e-9
+    A = sbtv.BlurOperator(sbtv.psf_family("gaussian", 7, (0.4, 0.3))[0])
+
+    def solve(exact):
+        if solver == "fista":
+            return sbtv.my_fista(y, A, A.T, 0.3, 1.0, sbtv.TVnorm, sbtv.Psi_TV(10), 1, 1e-30, 6, y, ctx=ctx, exact_prox=exact)
+        spec = 3 if exact else 1
+        if solver == "csalsa":
+            return sbtv.csalsa(y, A, 0.5, 0.5, 1.0, "AT", A.T, "LS", A.invLS, "TVINITIALIZATION", 1, "TVITERS", 10,
+                               "STOPCRITERION", 1, "TOLERANCEA", 1e-30, "MAXITERA", 6, "TRUE_X", y, "SPECULATE", spec, ctx=ctx)
+        mu1, mu2 = 0.003, 0.002
+        return sbtv.CoRAL(y, A, 0.2, 0.1, "MU1", mu1, "MU2", mu2, "AT", A.T, "LS", A.LS(mu1 + mu2), "TVINITIALIZATION1", 1,
+                          "TVITERS1", 10, "TVINITIALIZATION2", 1, "TVITERS2", 10 if solver == "coral" else 7,
+                          "STOPCRITERION", 1, "TOLERANCEA", 1e-30, "MAXITERA", 6, "TRUE_X", y, "SPECULATE", spec, ctx=ctx)
+
+    s0 = ctx.solve_stats()["exact_restarts"]
+    got = solve(False)
+    assert ctx.solve_stats()["exact_restarts"] == s0 + 1
+    ref = solve(True)
+    assert ctx.solve_stats()["exact_restarts"] == s0 + 1
+    times = {"fista": 2, "csalsa": 7, "coral": 5, "coral_separate": 5}[solver]
+    for i, (g, r) in enumerate(zip(got, ref)):
+        if i != times:                                     # wall-clock traces
+            np.testing.assert_array_equal(np.asarray(g), np.asarray(r), err_msg="output %d" % i)
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_fista_optimistic_and_exact_prox_give_the_same_bits(ctx, seed):
     import sbtv

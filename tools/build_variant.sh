@@ -11,7 +11,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 cd "$C"
 $HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fno-gpu-rdc $FLAGS -c $UNIT.hip -o $UNIT.$NAME.o
 OBJS=""
-for u in ctx tv fft elementwise salsa sapg admm group; do
+for u in ctx loop tv fft elementwise salsa sapg admm group; do
   if [ "$u" = "$UNIT" ]; then OBJS="$OBJS $UNIT.$NAME.o"; else OBJS="$OBJS $u.o"; fi
 done
 $HIPCC -shared -fPIC --offload-arch=gfx950 -o ../lib/libsbtv_$NAME.so $OBJS -lpthread
