@@ -246,6 +246,41 @@ int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                   double *x_out, double *objective, double *distance, double *times, double *mses,
                   int *numA, int *numAt, int *n_outer, int flags);
 
+/* ---- masked-observation SALSA: unknown boundaries and missing pixels ------------------------------------------------
+ * The SALSA toolbox knows a mask OR a blur ('MASK', 1: SALSA/SALSA.m:103-104,308-312,463-464 and
+ * SALSA/csalsa.m:112-113,349-352,510-511 solve with 1 ./ (mu + mask)); a mask OF a blur has no counterpart in the
+ * reference.  This entry is the ADMM of Almeida & Figueiredo ("Deconvolving images with unknown boundaries using the
+ * alternating direction method of multipliers", IEEE TIP 2013) on the kernels of sbtv_SALSA_v2:
+ *     minimise over x   0.5 * sum( m .* (B x - y).^2 ) + tau * TV(x)
+ * B: circular blur of `taps` (top-left embedding, utils/resize.m), m = mask: M*N*batch non-negative weights like y (0 = not
+ * observed, 1 = observed, other values weigh a pixel); y enters only as m .* y, its values under m = 0 must be finite.
+ * With the splits u = x, v = B x and scaled multipliers bu, bv in SALSA_v2's sign convention (SALSA/SALSA_v2.m:429-440)
+ * one outer iteration is
+ *     u  = chambolle_prox_TV_stop(x - bu, 'lambda', tau/mu1, 'maxiter', TViters, 'dualvars', [pux puy])
+ *     v  = (m .* y + mu2 * (Bx - bv)) ./ (m + mu2)
+ *     X  = (mu1 * fft2(u + bu) + mu2 * conj(H) .* fft2(v + bv)) ./ (mu1 + mu2 * abs(H).^2)
+ *     x  = real(ifft2(X));    Bx = real(ifft2(H .* X))
+ *     bu = bu + (u - x);      bv = bv + (v - Bx)
+ *     objective(outer+1) = 0.5 * sum(m .* (Bx - y).^2) + tau * TVnorm(u)
+ * Start: x by opts->initialization (0 zeros, 2 B'(m .* y), 33333 x_init), Bx = B x, u = x, v = Bx, bu = bv = 0, zero duals;
+ * objective(1) from that state.  Stop rules 1, 2, 3 as SALSA/SALSA_v2.m:453-482 (from the second outer iteration on).
+ * objective / times / mses: [batch*(maxiter+1)] (mses against true_x over all M*N pixels, SALSA_v2.m:446-449);
+ * distance: [batch*maxiter*2], entry (outer-1)*2 + {0,1} = ||x-u|| / sqrt(||x||^2+||u||^2), ||Bx-v|| / sqrt(||Bx||^2+||v||^2);
+ * numA / numAt count the applications of B / B' as the iteration is written: numA = 1 (the start's B x) + one per outer
+ * iteration (H .* X), numAt = one per outer iteration (conj(H) .* fft2(v + bv)) + 1 when initialization = 2.
+ * mu2 decides the speed, not the answer; 0.1 is the Python mirror's default (measured on one problem with pixel values
+ * in 0..255).  `speculate` as for sbtv_SALSA_v2; images of a batch are solved one after another, image k bit for bit as alone.
+ * Errors before any GPU work: mask == NULL, mu1[b] <= 0, mu2[b] <= 0 -> SBTV_ERR_BADARG; odd pixel count -> SBTV_ERR_SIZE;
+ * stop criterion and initialization as sbtv_SALSA_v2.  With SBTV_HOST_PTRS a mask with a negative or non-finite entry is
+ * rejected (SBTV_ERR_BADARG); a device-resident mask (it lives where y lives) is the caller's responsibility.
+ * Out of scope: the SAPG / MYULA samplers keep the circular, fully observed likelihood (their gradients and parameter
+ * sums live in the spectral domain by Parseval, which a mask breaks). */
+int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch,
+                      const double *taps, int taille, const double *tau, const double *mu1, const double *mu2,
+                      const sbtv_salsa_opts *opts, const double *true_x, const double *x_init,
+                      double *x_out, double *objective, double *distance, double *times, double *mses,
+                      int *numA, int *numAt, int *n_outer, int flags);
+
 /* ---- a-8: FISTA with the TV prox ----------------------------------------
  * Replaces my_fista(b,A,AT,tau,L,Phi,Psi,stopcriterion,tolerance,maxiters,true,verbose)
  * (SALSA/my_fista.m:5-56) with Psi = cold-start Chambolle(prox_iters) and Phi = TVnorm
@@ -452,6 +487,12 @@ int sbtv_CoRAL_v2_sharded(sbtv_group *g, const double *y, int M, int N, int n_it
                           const sbtv_salsa_opts *opts, const double *true_x, const double *x_init,
                           double *x_out, double *objective, double *distance, double *times, double *mses,
                           int *numA, int *numAt, int *n_outer);
+/* independent images, no exchange; arguments as for sbtv_SALSA_masked, image k bit for bit as by that entry */
+int sbtv_SALSA_masked_sharded(sbtv_group *g, const double *y, const double *mask, int M, int N, int n_items,
+                              const double *taps, int taille, const double *tau, const double *mu1, const double *mu2,
+                              const sbtv_salsa_opts *opts, const double *true_x, const double *x_init,
+                              double *x_out, double *objective, double *distance, double *times, double *mses,
+                              int *numA, int *numAt, int *n_outer);
 
 /* ---- diagnostics (no counterpart in the reference; SURVEY.md §5 sanitizer / tracing rows) ----
  * sbtv_diag_canary: with SBTV_CANARY=1 in the environment when the context was created, every device workspace of

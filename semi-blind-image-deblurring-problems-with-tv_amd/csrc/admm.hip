@@ -2,6 +2,8 @@
 // the same device kernels as SALSA_v2:
 //   C-SALSA  (SALSA/CSALSA_v2.m:160-561)  min TV(x)  s.t. ||Ax - y|| <= epsilon
 //   CoRAL    (SALSA/CoRAL_v2.m:2-476)     min 0.5||Ax-y||^2 + tau1 TV(x) + tau2 TV(x)   (two split copies)
+// and the masked-observation SALSA (no counterpart in the reference: SALSA/SALSA.m:103-104,308-312,463-464 takes a mask OR a
+// blur), min 0.5 sum(m .* (Bx - y).^2) + tau TV(x) with the splits u = x and v = Bx (masked_one below).
 // Neither is called by the reference's demos, so they are not fused to the last pass; what they share with the SALSA
 // loop since round 3 is its stream discipline: the Chambolle launches of an outer iteration are OPTIMISTIC (all TViters
 // iterations back to back, no stop-rule kernels, no redo pass; the host applies chambolle_prox_TV_stop.m:131 to the step
@@ -267,6 +269,79 @@ __global__ __launch_bounds__(AB) void coral_post_kernel(const double *__restrict
         }
     }
     ad_store_partials<7>(acc, partials);
+}
+
+// ---- masked-observation SALSA (masked_one) ------------------------------------------------------
+// w = m .* y: the right-hand side of the start x = B'(m .* y) ('INITIALIZATION' 2)
+__global__ __launch_bounds__(AB) void masked_my_kernel(const double *__restrict__ m, const double *__restrict__ y,
+                                                        double *__restrict__ w, size_t P) {
+    AD_LOOP(q, P) {
+        const double2 mv = AD_LD(m, q), yv = AD_LD(y, q);
+        AD_ST(w, q, make_double2(mv.x * yv.x, mv.y * yv.y));
+    }
+}
+
+// The one element-wise pass of an outer iteration, after the two inverse transforms (x, Bx) and with this iteration's u and v:
+//   bu += u - x ; bv += v - Bx ; g = x - bu (the next prox input) ; v <- (m .* y + mu2 (Bx - bv)) ./ (m + mu2) (the next v)
+//   partials [9 or 10][nb]: m (Bx-y)^2, (x-u)^2, (Bx-v)^2, x^2, u^2, Bx^2, v^2, (x-true)^2, (x-xprev)^2 and, TVS, the periodic
+//   TV norm of u (utils/TVnorm.m:2; M even, element 2q = (i, j) with i even), all with the v this iteration solved with
+template <bool TVS>
+__global__ __launch_bounds__(AB) void masked_post_kernel(const double *__restrict__ x, const double *__restrict__ xprev,
+                                                          const double *__restrict__ Bx, const double *__restrict__ u,
+                                                          const double *__restrict__ y, const double *__restrict__ m,
+                                                          double *__restrict__ bu, double *__restrict__ v,
+                                                          double *__restrict__ bv, double *__restrict__ g,
+                                                          const double *__restrict__ tru, double mu2,
+                                                          double *__restrict__ partials, unsigned M, unsigned N, size_t P) {
+    constexpr int NQ = TVS ? 10 : 9;
+    double acc[NQ];
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
+    AD_LOOP(q, P) {
+        const double2 xv = AD_LD(x, q), ax = AD_LD(Bx, q), uv = AD_LD(u, q), vv = AD_LD(v, q);
+        const double2 yv = AD_LD(y, q), mv = AD_LD(m, q);
+        double2 b1 = AD_LD(bu, q), b2 = AD_LD(bv, q);
+        b1.x = b1.x + (uv.x - xv.x);
+        b1.y = b1.y + (uv.y - xv.y);
+        b2.x = b2.x + (vv.x - ax.x);
+        b2.y = b2.y + (vv.y - ax.y);
+        AD_ST(bu, q, b1);
+        AD_ST(bv, q, b2);
+        AD_ST(g, q, make_double2(xv.x - b1.x, xv.y - b1.y));
+        AD_ST(v, q, make_double2((mv.x * yv.x + mu2 * (ax.x - b2.x)) / (mv.x + mu2),
+                                 (mv.y * yv.y + mu2 * (ax.y - b2.y)) / (mv.y + mu2)));
+        {
+            const double e0 = ax.x - yv.x, e1 = ax.y - yv.y;
+            acc[0] += mv.x * (e0 * e0) + mv.y * (e1 * e1);
+            const double d0 = xv.x - uv.x, d1 = xv.y - uv.y;
+            acc[1] += d0 * d0 + d1 * d1;
+            const double r0 = ax.x - vv.x, r1 = ax.y - vv.y;
+            acc[2] += r0 * r0 + r1 * r1;
+        }
+        acc[3] += xv.x * xv.x + xv.y * xv.y;
+        acc[4] += uv.x * uv.x + uv.y * uv.y;
+        acc[5] += ax.x * ax.x + ax.y * ax.y;
+        acc[6] += vv.x * vv.x + vv.y * vv.y;
+        if (tru) {
+            const double2 tv = AD_LD(tru, q);
+            const double m0 = xv.x - tv.x, m1 = xv.y - tv.y;
+            acc[7] += m0 * m0 + m1 * m1;
+        }
+        if (xprev) {
+            const double2 xo = AD_LD(xprev, q);
+            const double m0 = xv.x - xo.x, m1 = xv.y - xo.y;
+            acc[8] += m0 * m0 + m1 * m1;
+        }
+        if constexpr (TVS) {
+            const unsigned idx = (unsigned)(2 * q), j = idx / M, i = idx - j * M;
+            const size_t lcol = (size_t)(j > 0 ? j - 1 : N - 1) * M + i;
+            const double2 ul = *reinterpret_cast<const double2 *>(u + lcol);
+            const double uu = u[(size_t)j * M + (i > 0 ? i - 1 : M - 1)];
+            const double h0 = uv.x - ul.x, v0 = uv.x - uu, h1 = uv.y - ul.y, v1 = uv.y - uv.x;
+            acc[NQ - 1] += sqrt(h0 * h0 + v0 * v0) + sqrt(h1 * h1 + v1 * v1);
+        }
+    }
+    ad_store_partials<NQ>(acc, partials);
 }
 
 inline int ad_blocks(size_t P) {
@@ -873,6 +948,218 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Masked-observation SALSA:  min_x 0.5 sum(m .* (B x - y).^2) + tau TV(x)  with the splits u = x (TV) and v = B x (data),
+// the ADMM of Almeida & Figueiredo (IEEE TIP 2013) in SALSA_v2's sign convention (include/sbtv.h states the iteration).
+// The spectral solve with its two right-hand sides,
+//     X = (mu1 fft2(u+bu) + mu2 conj(H) fft2(v+bv)) / (mu1 + mu2 |H|^2)
+//       = (conj(H) W + r S) / (|H|^2 + r),   W = fft2(v+bv), S = fft2(u+bu), r = mu1 / mu2,
+// is the row pass OP_SALSA with the per-iteration spectrum W in the place of fft2(y) and r in the place of mu: no new
+// row kernel.  Bx needs no forward column pass either: the row pass leaves S = N colFFT(x) (the column-transformed x), so a
+// second row pass with OP_MUL_H on that S and an inverse column pass scaled by 1/N more give real(ifft2(H X)).  Per outer
+// iteration: 2 forward column passes (v+bv, u+bu), 3 row passes (+ the unpack of W), 2 inverse column passes, the prox,
+// one element-wise pass and one reduction launch.
+int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, const double *taps, int taille, double tau,
+               double mu1, double mu2, const sbtv_salsa_opts *opts, const double *td, const double *xi, double *x_out_dev,
+               double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer,
+               bool spec_wanted) {
+    AdmmCommon c;
+    SBTV_TRY(admm_common(ctx, M, N, taps, taille, nullptr, &c));
+    ProxPlan pp;
+    SBTV_TRY(prox_plan(ctx, M, N, 1, &pp));
+    const size_t P = c.P;
+    const int nb = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
+    const bool tv_in_post = !(M & 1) && P < ((size_t)1 << 31);          // TV(u) rides in the element-wise pass
+    const int nq = tv_in_post ? 10 : 9;
+    double *xbuf[2], *u, *bu, *v, *bv, *Bx, *g, *par, *partials, *sums, *acc;
+    double2 *Ws, *S2;
+    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &xbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &xbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &u));
+    SBTV_TRY(ws_get_t(ctx, "admm.bu", P, &bu));
+    SBTV_TRY(ws_get_t(ctx, "admm.v", P, &v));
+    SBTV_TRY(ws_get_t(ctx, "admm.bv", P, &bv));
+    SBTV_TRY(ws_get_t(ctx, "admm.Ax", P, &Bx));
+    SBTV_TRY(ws_get_t(ctx, "admm.g", P, &g));
+    SBTV_TRY(ws_get_t(ctx, "admm.par", (size_t)4, &par));               // mu1 / mu2, tau / mu1
+    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * nb, &partials));
+    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0..9] sums of the element-wise pass, [16..] prox step sums
+    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));         // residual sum of OP_SALSA (against W: not used)
+    SBTV_TRY(ws_get_t(ctx, "admm.W", c.fp.u_img, &Ws));
+    SBTV_TRY(ws_get_t(ctx, "admm.S2", c.fp.s_img, &S2));
+    double *hs = nullptr;
+    {
+        void *pz = nullptr;
+        SBTV_TRY(pinned_get(ctx, sizeof(double) * 192, &pz));
+        hs = static_cast<double *>(pz);
+    }
+    {
+        const double h[4] = {mu1 / mu2, tau / mu1, 0.0, 0.0};
+        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // the inverse column pass of H X takes the spectrum the row pass of X left: N times the column transform of x (the
+    // chirp-z path keeps whole 2-D spectra, its "row pass" is point-wise)
+    const double bx_scale = c.fp.generic ? c.inv_scale : c.inv_scale / (double)N;
+    auto post = [&](const double *xn, const double *xprev) {
+        if (tv_in_post)
+            hipLaunchKernelGGL(masked_post_kernel<true>, dim3(nb), dim3(AB), 0, ctx->stream, xn, xprev, (const double *)Bx,
+                               (const double *)u, yd, md, bu, v, bv, g, td, mu2, partials, (unsigned)M, (unsigned)N, P);
+        else
+            hipLaunchKernelGGL(masked_post_kernel<false>, dim3(nb), dim3(AB), 0, ctx->stream, xn, xprev, (const double *)Bx,
+                               (const double *)u, yd, md, bu, v, bv, g, td, mu2, partials, (unsigned)M, (unsigned)N, P);
+    };
+    const int maxiter = opts->maxiter;
+    int h_numA = 0, h_numAt = 0;
+    double *x = xbuf[0];
+    if (opts->initialization == 2) {                                     // x = B'(m .* y)
+        hipLaunchKernelGGL(masked_my_kernel, dim3(nb), dim3(AB), 0, ctx->stream, md, yd, g, P);
+        SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, g, x));
+        h_numAt += 1;
+        ctx->calls += 1;
+    } else {
+        SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
+    }
+    // Bx = B x ; u = x ; v = Bx ; bu = bv = 0 ; zero duals.  The element-wise pass on that state leaves bu = bv = 0, the
+    // first prox input g = x, the first v and the sums of objective(1) / mses(1)
+    SBTV_TRY(admm_apply(ctx, c, OP_MUL_H, x, Bx));
+    h_numA += 1;
+    ctx->calls += 1;
+    SBTV_HIP(ctx, hipMemcpyAsync(u, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipMemcpyAsync(v, Bx, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipMemsetAsync(bu, 0, sizeof(double) * P, ctx->stream));
+    SBTV_HIP(ctx, hipMemsetAsync(bv, 0, sizeof(double) * P, ctx->stream));
+    SBTV_TRY(prox_zero_duals(ctx, pp));
+    SBTV_TRY(prox_reset(ctx, pp, par + 1, 1.0, opts->TViters, opts->chambolle_tol, opts->chambolle_tau, false, nullptr));
+    {
+        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
+        post(x, nullptr);
+        SBTV_TRY(reduce_partials(ctx, partials, nq, nb, sums));
+        if (!tv_in_post) SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
+        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const double f0 = 0.5 * hs[0] + tau * hs[9];
+        if (objective) objective[0] = f0;
+        if (times) times[0] = 0.0;
+        if (mses && td) mses[0] = hs[7] / (double)P;
+        hs[15] = f0;
+    }
+    double obj_prev = hs[15];
+    const auto t0 = std::chrono::steady_clock::now();
+    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    const int K = opts->TViters;
+    const bool spec = spec_wanted && prox_spec_ok(pp, g, u, K);
+    const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
+    long long nlaunch = 0, prox_iters = 0;
+    AdmmSlots slots;
+    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    double *hslot[2] = {hs, hs + 96};
+    auto enqueue = [&](int outer) -> int {
+        double *xn = xbuf[outer & 1];
+        const double *xprev = xbuf[(outer & 1) ^ 1];
+        // u = prox_{(tau/mu1) TV}(x - bu), warm-started duals.  The first outer iteration always runs exactly (a zero start
+        // gives a zero prox input and the rule stops at k = 1); the control block is re-armed for the optimistic launches
+        const bool sp = spec && outer >= 2;
+        RedJobs jb;
+        if (spec && outer == 2)
+            SBTV_TRY(prox_reset(ctx, pp, par + 1, 1.0, K, opts->chambolle_tol, opts->chambolle_tau, true, nullptr));
+        if (!sp) {
+            SBTV_TRY(admm_prox(ctx, pp, g, K, u, false, &nlaunch, sums + 16, par + 1, opts->chambolle_tol, opts->chambolle_tau));
+        } else {
+            SBTV_TRY(prox_iterate(ctx, pp, g, K, u, false, 1, (int)(nlaunch & 1), nullptr));
+            nlaunch += prox_launches(pp, K);
+            jb.add(pp.partials, K, pp.fnblk, sums + 16);                 // reduced at the end of the iteration
+        }
+        // W = fft2(v + bv) (v was formed by the previous element-wise pass)
+        {
+            RowsArgs a{};
+            a.dir_fwd = 1;
+            a.op = OP_NONE;
+            SBTV_TRY(fft_cols_fwd(ctx, c.fp, v, bv, S2));
+            SBTV_TRY(fft_rows(ctx, c.fp, S2, S2, a));
+            SBTV_TRY(spec_unpack(ctx, c.fp, S2, Ws));
+        }
+        // X = (conj(H) W + r fft2(u + bu)) / (|H|^2 + r) ; x = real(ifft2(X))
+        {
+            RowsArgs a{};
+            a.dir_fwd = 1;
+            a.dir_inv = 1;
+            a.op = OP_SALSA;
+            a.H = c.Hs;
+            a.Y = Ws;
+            a.mu = par;                                                  // r = mu1 / mu2
+            a.acc = acc;
+            SBTV_TRY(fft_cols_fwd(ctx, c.fp, u, bu, c.S));
+            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
+            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xn, c.inv_scale));
+        }
+        // Bx = real(ifft2(H X)) from the column-transformed x the row pass left in S
+        {
+            RowsArgs a{};
+            a.dir_fwd = 1;
+            a.dir_inv = 1;
+            a.op = OP_MUL_H;
+            a.H = c.Hs;
+            SBTV_TRY(fft_rows(ctx, c.fp, c.S, S2, a));
+            SBTV_TRY(fft_cols_inv(ctx, c.fp, S2, Bx, bx_scale));
+        }
+        post(xn, (opts->stopcriterion == 2) ? xprev : (const double *)nullptr);
+        jb.add(partials, nq, nb, sums);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        if (!tv_in_post) SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
+        SBTV_HIP(ctx, hipGetLastError());
+        double *hsl = hslot[outer & 1];
+        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * (sp ? 16 + K : 12), hipMemcpyDeviceToHost, ctx->stream));
+        if (!sp) SBTV_HIP(ctx, hipMemcpyAsync(hsl + 12, pp.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
+        return 0;
+    };
+    bool stop = false;
+    // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
+    auto process = [&](int outer) -> int {
+        const double *hsl = hslot[outer & 1];
+        const bool sp = spec && outer >= 2;
+        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
+        if (sp) SBTV_TRY(spec_stop_rule(ctx, pp, hsl + 16, K, opts->chambolle_tol));
+        prox_iters += sp ? (long long)K : (long long)*reinterpret_cast<const int *>(hsl + 12);
+        h_numA += 1;                                                     // H .* X
+        h_numAt += 1;                                                    // conj(H) .* fft2(v + bv)
+        ctx->calls += 2;
+        const double f = 0.5 * hsl[0] + tau * hsl[9];
+        if (objective) objective[outer] = f;
+        if (mses && td) mses[outer] = hsl[7] / (double)P;
+        if (distance) {
+            distance[(size_t)(outer - 1) * 2] = sqrt(hsl[1]) / sqrt(hsl[3] + hsl[4]);
+            distance[(size_t)(outer - 1) * 2 + 1] = sqrt(hsl[2]) / sqrt(hsl[5] + hsl[6]);
+        }
+        if (times) times[outer] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (outer > 1) {                                                 // :453
+            double crit;
+            if (opts->stopcriterion == 1)
+                crit = fabs(f - obj_prev) / obj_prev;                    // :456
+            else if (opts->stopcriterion == 2)
+                crit = fabs(sqrt(hsl[8]) / sqrt(hsl[3]));                // :460
+            else
+                crit = f;                                                // :464
+            stop = crit < opts->tolA;                                    // :472
+        }
+        obj_prev = f;
+        return 0;
+    };
+    int last = 0;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
+    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
+    SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (numA) *numA = h_numA;
+    if (numAt) *numAt = h_numAt;
+    if (n_outer) *n_outer = last;
+    return 0;
+}
+
 }  // namespace
 }  // namespace sbtv
 
@@ -960,6 +1247,54 @@ int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
                              distance ? distance + (size_t)b * mi * 2 : nullptr, times ? times + (size_t)b * (mi + 1) : nullptr,
                              mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
                              numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
+        }));
+    }
+    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return canary_epilogue(ctx, 0);
+}
+
+int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch, const double *taps,
+                      int taille, const double *tau, const double *mu1, const double *mu2, const sbtv_salsa_opts *opts,
+                      const double *true_x, const double *x_init, double *x_out, double *objective, double *distance,
+                      double *times, double *mses, int *numA, int *numAt, int *n_outer, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    SBTV_TRY(check_common(ctx, "SALSA_masked", y, taps, opts, x_init, M, N, batch, taille));
+    if (!mask) return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: the mask is missing");
+    if (!tau || !mu1 || !mu2) return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: missing required argument");
+    for (int b = 0; b < batch; ++b)
+        if (!(mu1[b] > 0.0) || !(mu2[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: mu1, mu2 must be > 0");
+    if (((size_t)M * N) & 1)
+        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    const size_t P = (size_t)M * N, cnt = P * batch;
+    if (!(flags & SBTV_DEVICE_PTRS))
+        for (size_t i = 0; i < cnt; ++i)
+            if (!(mask[i] >= 0.0) || std::isinf(mask[i]))
+                return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: the mask must be finite and non-negative");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
+    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
+        LaneCall lc(ctx, lg);
+        return lc.done(masked_sharded(lg, y, mask, M, N, batch, taps, taille, tau, mu1, mu2, opts, true_x, x_init, x_out,
+                                      objective, distance, times, mses, numA, numAt, n_outer, flags), batch);
+    }
+    const double *yd = nullptr, *md = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "admm.in.mask", mask, cnt, flags, &md));
+    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
+    double *xo = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
+    const int mi = opts->maxiter;
+    for (int b = 0; b < batch; ++b) {
+        const size_t o = (size_t)b * P;
+        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
+            return masked_one(ctx, yd + o, md + o, M, N, taps + (size_t)b * taille * taille, taille, tau[b], mu1[b], mu2[b],
+                              opts, td ? td + o : nullptr, xi ? xi + o : nullptr, xo + o,
+                              objective ? objective + (size_t)b * (mi + 1) : nullptr,
+                              distance ? distance + (size_t)b * mi * 2 : nullptr, times ? times + (size_t)b * (mi + 1) : nullptr,
+                              mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
+                              numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
         }));
     }
     SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));

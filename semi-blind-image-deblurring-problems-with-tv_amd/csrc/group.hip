@@ -298,6 +298,15 @@ int sbtv_CoRAL_v2_sharded(sbtv_group *g, const double *y, int M, int N, int n_it
                          objective, distance, times, mses, numA, numAt, n_outer, SBTV_HOST_PTRS);
 }
 
+int sbtv_SALSA_masked_sharded(sbtv_group *g, const double *y, const double *mask, int M, int N, int n_items,
+                              const double *taps, int taille, const double *tau, const double *mu1, const double *mu2,
+                              const sbtv_salsa_opts *opts, const double *true_x, const double *x_init, double *x_out,
+                              double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
+                              int *n_outer) {
+    return masked_sharded(g, y, mask, M, N, n_items, taps, taille, tau, mu1, mu2, opts, true_x, x_init, x_out, objective,
+                          distance, times, mses, numA, numAt, n_outer, SBTV_HOST_PTRS);
+}
+
 // Device-resident images on several GPUs: y[r] (true_x[r], x_init[r], x_out[r]) is a DEVICE pointer on shard r's device to
 // that shard's block of images (sbtv_group_shard_of gives first / count), column-major, one after the other.
 int sbtv_SALSA_v2_sharded_dev(sbtv_group *g, const double *const *y, int M, int N, int n_items, const double *taps,
@@ -482,6 +491,27 @@ int coral_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, con
                              off(x_out, b * P), off(objective, b * (K + 1)), off(distance, b * K * 2),
                              off(times, b * (K + 1)), off(mses, b * (K + 1)), off(numA, b), off(numAt, b),
                              off(n_outer, b), flags);
+    });
+}
+
+// masked-observation SALSA over independent images: no exchange
+int masked_sharded(sbtv_group *g, const double *y, const double *mask, int M, int N, int n_items, const double *taps,
+                   int taille, const double *tau, const double *mu1, const double *mu2, const sbtv_salsa_opts *opts,
+                   const double *true_x, const double *x_init, double *x_out, double *objective, double *distance,
+                   double *times, double *mses, int *numA, int *numAt, int *n_outer, int flags) {
+    if (!g) return SBTV_ERR_BADARG;
+    if (!y || !mask || !taps || !tau || !mu1 || !mu2 || !opts || n_items < 1 || M < 2 || N < 2)
+        return gfail(g, SBTV_ERR_BADARG, "SALSA_masked_sharded: missing required argument");
+    const int ns = active_shards(g, n_items);
+    const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)(opts->maxiter > 0 ? opts->maxiter : 0);
+    return run_shards(g, ns, [&](int r) -> int {
+        int lo, hi;
+        block_of(n_items, ns, r, &lo, &hi);
+        const size_t b = (size_t)lo;
+        return sbtv_SALSA_masked(g->ctxs[r], y + b * P, mask + b * P, M, N, hi - lo, taps + b * t2, taille, tau + b, mu1 + b,
+                                 mu2 + b, opts, off(true_x, b * P), off(x_init, b * P), off(x_out, b * P),
+                                 off(objective, b * (K + 1)), off(distance, b * K * 2), off(times, b * (K + 1)),
+                                 off(mses, b * (K + 1)), off(numA, b), off(numAt, b), off(n_outer, b), flags);
     });
 }
 

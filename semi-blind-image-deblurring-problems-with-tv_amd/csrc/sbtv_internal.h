@@ -382,6 +382,10 @@ int coral_sharded(::sbtv_group *g, const double *y, int M, int N, int n_items, c
                   int TViters2, const sbtv_salsa_opts *opts, const double *true_x, const double *x_init, double *x_out,
                   double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer,
                   int flags);
+int masked_sharded(::sbtv_group *g, const double *y, const double *mask, int M, int N, int n_items, const double *taps,
+                   int taille, const double *tau, const double *mu1, const double *mu2, const sbtv_salsa_opts *opts,
+                   const double *true_x, const double *x_init, double *x_out, double *objective, double *distance,
+                   double *times, double *mses, int *numA, int *numAt, int *n_outer, int flags);
 
 // ----------------------------- host side of the solver loops (loop.hip) -----
 // low-latency host waits of the solver loops (poll, then block)

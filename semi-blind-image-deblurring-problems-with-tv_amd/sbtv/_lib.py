@@ -104,6 +104,8 @@ SIGNATURES = {
                             _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_CoRAL_v2": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
                            _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sbtv_SALSA_masked": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _I]),
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),
@@ -132,6 +134,8 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sbtv_CoRAL_v2_sharded": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, C.POINTER(sbtv_salsa_opts), _P,
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sbtv_SALSA_masked_sharded": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _P, _P]),
     "sbtv_diag_stage_stats": (_I, [_P, C.POINTER(_D)]),
     "sbtv_host_transpose": (_I, [_P, _P, _I, _I, _I]),
     "sbtv_diag_solve_stats": (_I, [_P, C.POINTER(_D)]),

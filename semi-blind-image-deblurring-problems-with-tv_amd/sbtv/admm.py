@@ -1,6 +1,8 @@
 """Host mirrors of the two other ADMM front-ends that use the TV prox:
 `csalsa` (SALSA/CSALSA_v2.m:160-561) and `CoRAL` (SALSA/CoRAL_v2.m:2-476).  The reference's demos never
-call them; they run on the same device kernels as SALSA_v2."""
+call them; they run on the same device kernels as SALSA_v2.  `SALSA_masked` (no counterpart in the reference: SALSA/SALSA.m
+knows a mask or a blur, not a mask of a blur) solves the TV problem for observations with unknown boundaries and
+missing pixels on the same kernels."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,6 +19,9 @@ _CSALSA_OPTIONS = {"P", "PT", "PSI", "PHI", "TVINITIALIZATION", "TVITERS", "STOP
 _CORAL_OPTIONS = {"W", "WT", "P1", "P1T", "P2", "P2T", "PSI1", "PHI1", "TVINITIALIZATION1", "TVITERS1", "PSI2", "PHI2",
                   "TVINITIALIZATION2", "TVITERS2", "MU1", "MU2", "STOPCRITERION", "TOLERANCEA", "INNERITERS",
                   "MAXITERA", "INITIALIZATION", "TRUE_X", "AT", "VERBOSE", "LS", "SEED", "SPECULATE"}
+
+_MASKED_OPTIONS = {"MU1", "MU2", "AT", "TVITERS", "STOPCRITERION", "TOLERANCEA", "MAXITERA", "TRUE_X", "INITIALIZATION",
+                   "VERBOSE", "SEED", "SPECULATE"}
 
 _vp = L.vptr
 
@@ -174,3 +179,91 @@ def CoRAL(y, A, tau1, tau2, *varargin, ctx=None, **kw):
 
 
 CoRAL_v2 = CoRAL
+
+
+def SALSA_masked(y, A, mask, tau, *varargin, ctx=None, **kw):
+    """[x, numA, numAt, objective, distance, times, mses] = SALSA_masked(y, A, mask, tau, 'MU1', mu1, 'MU2', mu2, 'AT', A.T, ...)
+
+    minimise 0.5 * sum(mask .* (A x - y).^2) + tau * TV(x): `mask` holds non-negative weights of the shape of y (0 = pixel not
+    observed, 1 = observed); the iteration is stated in include/sbtv.h (sbtv_SALSA_masked).  Options: 'MU1' (required, the
+    weight of the TV split, SALSA_v2's 'MU'), 'MU2' (the weight of the data split, default 0.1: it decides the speed, not the
+    answer, and the default rests on one problem with pixel values in 0..255), 'AT', 'TVITERS', 'STOPCRITERION',
+    'TOLERANCEA', 'MAXITERA', 'TRUE_X', 'INITIALIZATION' (0, 2 = AT(mask .* y), or an array), 'VERBOSE'.  distance is
+    (outer, 2): the relative distances of the two splits.  For an observation without wrapped pixels see `embed_observation`."""
+    opts = _parse_varargin(varargin, _MASKED_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    so, yi, xinit, ti = _common(y, A, opts, ctx, 1)
+    if mask is None:
+        raise L.SbtvError(-1, "SALSA_masked: the mask is missing")
+    mi = L.Images(mask)
+    if (mi.B, mi.M, mi.N) != (yi.B, yi.M, yi.N):
+        raise ValueError("the mask must have the shape of y")
+    if mi.flags != yi.flags:
+        raise ValueError("all image arguments must live in the same memory space")
+    if "MU1" not in opts:
+        raise L.SbtvError(-1, "SALSA_masked: 'MU1' is required")
+    so.TViters = int(opts.get("TVITERS", 5))
+    B, M, N = yi.B, yi.M, yi.N
+    K = so.maxiter
+    xo = L.empty_like_images(yi)
+    objective, times, mses = np.zeros((B, K + 1)), np.zeros((B, K + 1)), np.zeros((B, K + 1))
+    distance = np.zeros((B, K, 2))
+    numA, numAt, nout = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+    taps = A._cm(B)
+    keep = [L.dvec(v, B) for v in (tau, opts["MU1"], opts.get("MU2", 0.1))]
+    tv, m1, m2 = (k[1] for k in keep)
+    args = (ctx.h, yi.ptr, mi.ptr, M, N, B, _vp(taps), A.taille, tv, m1, m2, C.byref(so), ti.ptr if ti else None,
+            xinit.ptr if xinit else None, xo.ptr, _vp(objective), _vp(distance), _vp(times), _vp(mses) if ti else None,
+            numA, numAt, nout)
+    if getattr(ctx, "is_group", False):          # sbtv.Group: images dealt to the devices in contiguous blocks
+        if yi.flags != L.SBTV_HOST_PTRS:
+            raise ValueError("a sbtv.Group takes host (NumPy) images")
+        ctx.check(ctx.lib.sbtv_SALSA_masked_sharded(*args))
+    else:
+        ctx.check(ctx.lib.sbtv_SALSA_masked(*args, yi.flags), yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    x = L.images_result(xo, sq)
+    n = np.array(nout[:])
+    if sq or B == 1:
+        k = int(n[0])
+        return (x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(),
+                times[0, :k + 1].copy(), mses[0, :k + 1].copy() if ti else np.array([]))
+    return (x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
+            [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
+            [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
+
+
+def valid_mask(shape, taille):
+    """Ones where row >= taille-1 and column >= taille-1, zeros elsewhere: the pixels of the circular blur A x (PSF of
+    taille x taille taps, top-left embedding) that use no wrapped pixel of x."""
+    M, N = (int(s) for s in shape)
+    t = int(taille)
+    if t < 1 or t > M or t > N:
+        raise ValueError("the PSF does not fit inside the image")
+    m = np.zeros((M, N))
+    m[t - 1:, t - 1:] = 1.0
+    return m
+
+
+def embed_observation(y_obs, taille, shape=None):
+    """(y, mask) for `SALSA_masked` from an observation without wrapped pixels (the 'valid' part of a linear blur): y_obs sits
+    at rows / columns taille-1 ... of a domain of y_obs.shape + taille - 1 pixels (or of a larger `shape`, e.g. the next power
+    of two), zeros elsewhere in both arrays."""
+    y_obs = np.asarray(y_obs, dtype=np.float64)
+    if y_obs.ndim != 2:
+        raise ValueError("y_obs must be one (m, n) image")
+    t = int(taille)
+    m0, n0 = y_obs.shape
+    need = (m0 + t - 1, n0 + t - 1)
+    if shape is None:
+        shape = need
+    M, N = (int(s) for s in shape)
+    if t < 1 or M < need[0] or N < need[1]:
+        raise ValueError(f"shape must be at least {need}")
+    y = np.zeros((M, N))
+    mask = np.zeros((M, N))
+    y[t - 1:t - 1 + m0, t - 1:t - 1 + n0] = y_obs
+    mask[t - 1:t - 1 + m0, t - 1:t - 1 + n0] = 1.0
+    return y, mask
