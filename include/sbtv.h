@@ -509,6 +509,11 @@ int sbtv_SALSA_masked_sharded(sbtv_group *g, const double *y, const double *mask
  *   workgroup, waves per SIMD requested, rows per lane, tiles per image, 1 = temporally fused tile kernel / 0 = the
  *   one-iteration kernels (odd M, SBTV_SINGLE_STEP)} — lets a parity test assert which kernel it exercised.  (Value 2,
  *   the retired streaming pipeline kernel, is no longer returned.)
+ * sbtv_diag_prox_geometry: the tile geometry behind that choice, from the same plan: out = {region rows, core rows, halo
+ *   rows above the core, halo rows below, rows per lane, region columns, core columns, halo columns left, halo columns
+ *   right, tile rows of the image, tile columns, 1 = the plan carries a workgroup -> tile table, first-round stagger in
+ *   half-microseconds (0 = none), tile rows / tile columns of the one-iteration kernels, most iterations of one fused
+ *   launch} — lets a test derive the image sizes that sit on a tile seam from the library instead of copying constants.
  * sbtv_diag_time_pass: times ONE pass of the hot path on scratch data of the given shape with HIP events on the
  *   context stream (`reps` launches after two untimed ones) -> average ms per launch and the algorithmic bytes of one
  *   launch.  pass: 0 forward column FFT of u+bu; 1 row pass with the SALSA spectral solve (forward FFT, operator,
@@ -540,6 +545,7 @@ int sbtv_diag_workspace(sbtv_ctx *ctx, const char *name, void **dptr, size_t *by
 int sbtv_diag_switches(char *buf, size_t cap);
 int sbtv_diag_time_pass(sbtv_ctx *ctx, int pass, int M, int N, int batch, int reps, double *ms_avg, double *alg_bytes);
 int sbtv_diag_prox_variant(sbtv_ctx *ctx, int M, int N, int batch, int out[6]);
+int sbtv_diag_prox_geometry(sbtv_ctx *ctx, int M, int N, int batch, int out[16]);
 
 #ifdef __cplusplus
 }

@@ -1135,6 +1135,31 @@ int sbtv_diag_prox_variant(sbtv_ctx *ctx, int M, int N, int batch, int out[6]) {
     return 0;
 }
 
+int sbtv_diag_prox_geometry(sbtv_ctx *ctx, int M, int N, int batch, int out[16]) {
+    if (!ctx || !out || M < 2 || N < 2 || batch < 1) return SBTV_ERR_BADARG;
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    ProxPlan pl;
+    SBTV_TRY(prox_plan(ctx, M, N, batch, &pl));
+    const bool two = (pl.rpl == 2);
+    out[0] = two ? FRI : F1RI;                   // region rows
+    out[1] = two ? FCI : F1CI;                   // core rows
+    out[2] = two ? FH : F1HT;                    // halo rows above the core
+    out[3] = two ? FH : F1HB;                    // halo rows below
+    out[4] = pl.rpl;
+    out[5] = pl.cj * pl.nw;                      // region columns
+    out[6] = pl.cj * pl.nw - FHL - FHJ;          // core columns
+    out[7] = FHL;                                // halo columns left of the core
+    out[8] = FHJ;                                // halo columns right
+    out[9] = pl.ftiles_i;
+    out[10] = pl.ftiles_j;
+    out[11] = pl.order != nullptr ? 1 : 0;       // workgroup -> tile table
+    out[12] = two ? fused_stagger(pl.fnblk) : 0; // first-round stagger (half-microseconds; the 128-row kernel only)
+    out[13] = TI;                                // tile of the one-iteration kernels
+    out[14] = TJ;
+    out[15] = FHJ;                               // most iterations one fused launch makes
+    return 0;
+}
+
 int sbtv_TVnorm(sbtv_ctx *ctx, const double *x, int M, int N, int batch, double *out, int flags) {
     if (!ctx) return SBTV_ERR_BADARG;
     if (!x || !out || M < 2 || N < 2 || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "TVnorm: bad arguments");

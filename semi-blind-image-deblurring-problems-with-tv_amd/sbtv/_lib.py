@@ -141,6 +141,7 @@ SIGNATURES = {
     "sbtv_diag_solve_stats": (_I, [_P, C.POINTER(_D)]),
     "sbtv_diag_canary": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "sbtv_diag_prox_variant": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
+    "sbtv_diag_prox_geometry": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
     "sbtv_last_host_stats": (_I, [_P, C.POINTER(_D)]),
     "sbtv_diag_workspace": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "sbtv_diag_switches": (_I, [C.c_char_p, C.c_size_t]),
@@ -265,6 +266,19 @@ class Context:
         self.check(self.lib.sbtv_diag_prox_variant(self.h, int(M), int(N), int(batch), out))
         return dict(cols_per_wave=out[0], waves=out[1], waves_per_simd=out[2], rows_per_lane=out[3], tiles=out[4],
                     fused=bool(out[5]), kind={0: "single-step", 1: "tile", 2: "pipeline"}[out[5]])
+
+    GEOMETRY = ("region_rows", "core_rows", "halo_top", "halo_bottom", "rows_per_lane", "region_cols", "core_cols",
+                "halo_left", "halo_right", "tiles_i", "tiles_j", "order", "stagger", "single_ti", "single_tj", "max_steps")
+
+    def prox_geometry(self, M, N, batch=1):
+        """Tile geometry of the TV-prox plan of an M x N x batch problem (sbtv_diag_prox_geometry): region / core / halo
+        extents of the fused kernel the plan chose, its tile grid, whether it carries a tile table (`order`), the
+        first-round stagger, the tile of the one-iteration kernels and the most iterations of one fused launch."""
+        out = (_I * 16)()
+        self.check(self.lib.sbtv_diag_prox_geometry(self.h, int(M), int(N), int(batch), out))
+        g = dict(zip(self.GEOMETRY, out))
+        g["order"] = bool(g["order"])
+        return g
 
     def last_timing(self):
         out = (C.c_double * 4)()

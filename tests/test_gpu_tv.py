@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 # kernels (odd M) and SBTV_EXACT=1 use IEEE sqrt / div with contraction off.  The reduction order of err / TVnorm
 # differs from NumPy's in every build.  These sizes take the one-row-per-lane fused kernel (fewer than 256 tiles)
 # or the scalar kernel; the two-rows-per-lane kernel that large images take is covered by test_gpu_tv_large.py.
+# None of these sizes is chosen for the tile geometry: the sizes on tile seams, image edges and either side of the
+# kernels' interior test are swept by test_gpu_tv_geometry.py.
 TOL = dict(rtol=1e-12, atol=1e-12)
 
 
