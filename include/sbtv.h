@@ -514,6 +514,17 @@ int sbtv_SALSA_masked_sharded(sbtv_group *g, const double *y, const double *mask
  *   right, tile rows of the image, tile columns, 1 = the plan carries a workgroup -> tile table, first-round stagger in
  *   half-microseconds (0 = none), tile rows / tile columns of the one-iteration kernels, most iterations of one fused
  *   launch} — lets a test derive the image sizes that sit on a tile seam from the library instead of copying constants.
+ * sbtv_diag_fft_plan: which FFT kernels an (M, N, batch) problem takes, from the host functions the launches themselves
+ *   use: out = {1 = arbitrary-size (chirp-z) path, 1 = wave-granular kernels, column transform length n1, columns per
+ *   column workgroup, threads per column workgroup, column workgroups per image, rows per row workgroup (0: the row pass
+ *   is the point-wise operator), threads per row workgroup, row workgroups per image, row kernel kind (0 workgroup,
+ *   1 software-pipelined, 2 point-wise), 1 = operator spectra tiled, Bluestein length for M, for N (0 off that path),
+ *   values of l per thread of the tap-spectrum launch (`lch`), 1 = a shared-spectrum batch of this size folds into
+ *   grid.x, bits: 1 = forward TV partials, 2 = the step / sub / skip_x column epilogues, 4 = OP_CSALSA available} -
+ *   lets a test derive its sizes and assert which kernels it ran from the library instead of copied constants.
+ * sbtv_diag_spectral_pass: ONE forward-column, row, inverse-column triple of the solver loops on caller data (host
+ *   pointers, column-major images), everything observable handed back; see sbtv_diag_pass.  Every refused argument is
+ *   refused before the first launch, with the error the pass itself would give.
  * sbtv_diag_time_pass: times ONE pass of the hot path on scratch data of the given shape with HIP events on the
  *   context stream (`reps` launches after two untimed ones) -> average ms per launch and the algorithmic bytes of one
  *   launch.  pass: 0 forward column FFT of u+bu; 1 row pass with the SALSA spectral solve (forward FFT, operator,
@@ -546,6 +557,29 @@ int sbtv_diag_switches(char *buf, size_t cap);
 int sbtv_diag_time_pass(sbtv_ctx *ctx, int pass, int M, int N, int batch, int reps, double *ms_avg, double *alg_bytes);
 int sbtv_diag_prox_variant(sbtv_ctx *ctx, int M, int N, int batch, int out[6]);
 int sbtv_diag_prox_geometry(sbtv_ctx *ctx, int M, int N, int batch, int out[16]);
+int sbtv_diag_fft_plan(sbtv_ctx *ctx, int M, int N, int batch, int out[16]);
+/* op: the spectral operator of the row pass, 0 none, 1 X H, 2 X conj(H), 3 X / (|H|^2 + mu), 4 SALSA solve, 5 residual
+ * sum only, 6 gradient with both PSF-parameter sums, 7 X |H|^2, 8 gradient, 9 C-SALSA solve with its state spectrum.
+ * epilogue of the inverse column pass: 0 plain, 1 SALSA bookkeeping (bu in / out, g_out, sums; tru, xprev optional),
+ * 2 ystep <- ystep - alpha x (x not stored), 3 g_out = x - sub_b, 4 bookkeeping that reads bu_in, writes bu and does not
+ * store x; 2..4 only where the plan reports them.  shared_spec: taps / y / e0 hold ONE set for the whole batch, else one
+ * per image.  repeats: the triple runs this many times, each on the x of the one before (epilogues that store x): two
+ * passes of op 9 observe the state spectrum the first one left.  frozen (optional, per image): the image is skipped,
+ * its outputs keep what the caller put there and its sums read 0.  acc [batch][3]: the row pass's sums; sums [batch][6]:
+ * the bookkeeping sums; tv [batch] (optional): periodic TV of x from the forward column pass. */
+typedef struct sbtv_diag_pass {
+    int M, N, batch, op, epilogue, taille, shared_spec, repeats;
+    const double *x, *add;
+    const double *taps, *d1taps, *d2taps;
+    const double *y, *e0;
+    const double *mu, *cs;
+    const int *frozen;
+    const double *u, *bu_in, *tru, *xprev, *sub_b;
+    double alpha;
+    double *bu, *ystep;
+    double *x_out, *g_out, *acc, *sums, *tv;
+} sbtv_diag_pass;
+int sbtv_diag_spectral_pass(sbtv_ctx *ctx, const sbtv_diag_pass *args);
 
 #ifdef __cplusplus
 }

@@ -936,25 +936,37 @@ static inline int cols_nseq(const FftPlan &pl) {
     return nseq;
 }
 
+// launch shape of a pass: sequences (columns / rows) per workgroup, threads per workgroup, workgroups per image; what the
+// launches below use and what sbtv_diag_fft_plan reports
+struct PassDims {
+    int per_wg, threads, wgs;
+};
+static inline PassDims cols_dims(const FftPlan &pl) {
+    if (pl.generic) return {1, ANY_THREADS, pl.N};          // one line per workgroup (any_fft2)
+    if (pl.wave) return {TW, 64 * TW, pl.N / TW};           // one wave per column
+    const int nseq = cols_nseq(pl);
+    return {nseq, nseq * (pl.n1 / 8), pl.N / nseq};
+}
+
 template <int L>
 static void launch_cols_fwd(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const double *add, double2 *S,
                             const int *frozen, double *tvp) {
-    const int nseq = cols_nseq(pl);
-    hipLaunchKernelGGL(fft_cols_fwd_kernel<L>, dim3(pl.N / nseq, pl.batch), dim3(nseq * (pl.n1 / 8)), 0, ctx->stream,
+    const PassDims cd = cols_dims(pl);
+    hipLaunchKernelGGL(fft_cols_fwd_kernel<L>, dim3(cd.wgs, pl.batch), dim3(cd.threads), 0, ctx->stream,
                        x, add, S, pl.tw_n1, pl.tw_M, pl.N, frozen, tvp);
 }
 template <int L>
 static void launch_cols_inv(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale,
                             const int *frozen) {
-    const int nseq = cols_nseq(pl);
-    hipLaunchKernelGGL((fft_cols_inv_kernel<L, false>), dim3(pl.N / nseq, pl.batch), dim3(nseq * (pl.n1 / 8)), 0,
+    const PassDims cd = cols_dims(pl);
+    hipLaunchKernelGGL((fft_cols_inv_kernel<L, false>), dim3(cd.wgs, pl.batch), dim3(cd.threads), 0,
                        ctx->stream, S, x, pl.tw_n1, pl.tw_M, pl.N, scale, frozen, ColsPost{});
 }
 template <int L>
 static void launch_cols_inv_post(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale,
                                  const int *frozen, const ColsPost &post) {
-    const int nseq = cols_nseq(pl);
-    hipLaunchKernelGGL((fft_cols_inv_kernel<L, true>), dim3(pl.N / nseq, pl.batch), dim3(nseq * (pl.n1 / 8)), 0,
+    const PassDims cd = cols_dims(pl);
+    hipLaunchKernelGGL((fft_cols_inv_kernel<L, true>), dim3(cd.wgs, pl.batch), dim3(cd.threads), 0,
                        ctx->stream, S, x, pl.tw_n1, pl.tw_M, pl.N, scale, frozen, post);
 }
 
@@ -977,10 +989,11 @@ static void launch_cols_inv_post(sbtv_ctx *ctx, const FftPlan &pl, const double2
 bool fft_cols_tv_ok(const FftPlan &pl) { return !pl.generic; }
 int fft_cols_fwd_f(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const double *add, double2 *S,
                    const int *frozen, double *tvp) {
-    if (tvp && (pl.generic || add)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_fwd: TV partials not available for this call");
+    if (tvp && (!fft_cols_tv_ok(pl) || add)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_fwd: TV partials not available for this call");
     if (pl.generic) return any_cols_fwd(ctx, pl, x, add, S, frozen);
     if (pl.wave) {
-        const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+        const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
         if (pl.n1 == 1024)
             hipLaunchKernelGGL((cols_fwd_wave_kernel<10, 16>), grid, block, 0, ctx->stream, x, add, S, pl.tw_n1, pl.tw_M,
                                pl.N, frozen, tvp);
@@ -1004,7 +1017,8 @@ int fft_cols_fwd(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const double
 int fft_cols_inv_f(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale, const int *frozen) {
     if (pl.generic) return any_cols_inv(ctx, pl, S, x, scale, frozen, nullptr);
     if (pl.wave) {
-        const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+        const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
         if (pl.n1 == 1024)
             hipLaunchKernelGGL((cols_inv_wave_kernel<10, 16, 0>), grid, block, 0, ctx->stream, S, x, pl.tw_n1,
                                pl.tw_M, pl.N, scale, frozen, ColsPost{});
@@ -1022,13 +1036,18 @@ int fft_cols_inv_f(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x
     return 0;
 }
 bool fft_cols_inv_step_ok(const FftPlan &pl) { return !pl.generic && pl.wave; }
+static int fft_cols_step_check(sbtv_ctx *ctx, const FftPlan &pl, const char *who) {
+    if (!fft_cols_inv_step_ok(pl)) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": size not on the wave-granular path");
+    return 0;
+}
 int fft_cols_inv_step(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *y, double scale, double alpha,
                       const int *frozen) {
-    if (!fft_cols_inv_step_ok(pl)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_step: size not on the wave-granular path");
+    SBTV_TRY(fft_cols_step_check(ctx, pl, "fft_cols_inv_step"));
     ColsPost post;
     post.ystep = y;
     post.alpha = alpha;
-    const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+    const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
     if (pl.n1 == 1024)
         hipLaunchKernelGGL((cols_inv_wave_kernel<10, 16, 8>), grid, block, 0, ctx->stream, S, (double *)nullptr, pl.tw_n1,
                            pl.tw_M, pl.N, scale, frozen, post);
@@ -1039,11 +1058,12 @@ int fft_cols_inv_step(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double
     return 0;
 }
 int fft_cols_inv_sub(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale, const double *b, double *g) {
-    if (!fft_cols_inv_step_ok(pl)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_sub: size not on the wave-granular path");
+    SBTV_TRY(fft_cols_step_check(ctx, pl, "fft_cols_inv_sub"));
     ColsPost post;
     post.bu_in = b;
     post.g = g;
-    const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+    const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
     if (pl.n1 == 1024)
         hipLaunchKernelGGL((cols_inv_wave_kernel<10, 16, 64>), grid, block, 0, ctx->stream, S, x, pl.tw_n1, pl.tw_M, pl.N, scale,
                            (const int *)nullptr, post);
@@ -1056,7 +1076,7 @@ int fft_cols_inv_sub(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double 
 int fft_cols_inv_myula(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double scale, double *X, const double *prox,
                        const double *Z, const double *sigma2_dev, double gam, double lamb, const RngArgs *rng,
                        const ProxArm *arm, const MomArgs *mom) {
-    if (!fft_cols_inv_step_ok(pl)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_myula: size not on the wave-granular path");
+    SBTV_TRY(fft_cols_step_check(ctx, pl, "fft_cols_inv_myula"));
     if (!Z && !rng) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_myula: neither a noise array nor generator arguments");
     ColsPost post;
     post.ystep = X;
@@ -1068,7 +1088,8 @@ int fft_cols_inv_myula(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, doubl
     post.msq2g = sqrt(2 * gam);
     if (rng) post.mrng = *rng;
     if (arm) post.marm = *arm;
-    const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+    const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
     if (mom) {
         post.mom = *mom;
         if (pl.n1 == 1024)
@@ -1096,7 +1117,8 @@ int fft_cols_inv_post(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double
         return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_post: bu_in + skip_x go together and need the wave-granular column pass");
     if (pl.generic) return any_cols_inv(ctx, pl, S, x, scale, frozen, &post);
     if (pl.wave) {
-        const dim3 grid(pl.N / TW, pl.batch), block(64 * TW);
+        const PassDims cd = cols_dims(pl);
+        const dim3 grid(cd.wgs, pl.batch), block(cd.threads);
         if (post.skip_x && (!post.bu_in || post.bu_in == post.bu || post.xprev))
             return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_post: skip_x needs a separate bu_in and no xprev");
         const int pm = 1 + (post.tru ? 2 : 0) + (post.xprev ? 4 : 0) + (post.skip_x ? 32 : 0);
@@ -1139,25 +1161,37 @@ static inline int rows_rk(const FftPlan &pl) {
     const int small = (N == 512) ? 1 : (N == 256) ? 2 : rk;
     return (pl.n1 / rk < 128) ? small : rk;
 }
+static inline PassDims rows_dims(const FftPlan &pl) {
+    if (pl.generic) return {0, ANY_SPEC_THREADS, ANY_SPEC_BLOCKS};   // the point-wise operator over the whole spectrum
+    if (pl.wave) return {4, pl.N / 4, pl.n1 / 4};                    // rows_pipe_kernel: two row pairs per workgroup
+    const int rk = rows_rk(pl);
+    return {rk, rk * (pl.N / 8), pl.n1 / rk};
+}
 bool fft_rows_csalsa_ok(const FftPlan &pl) { return !pl.generic; }
+static int fft_rows_check(sbtv_ctx *ctx, const FftPlan &pl, int op) {
+    if (op == OP_CSALSA && !fft_rows_csalsa_ok(pl)) return fail(ctx, SBTV_ERR_SIZE, "row pass: OP_CSALSA is not built for this plan");
+    return 0;
+}
 int fft_rows_blocks(const FftPlan &pl) {
-    if (pl.generic) return ANY_SPEC_BLOCKS;
-    if (pl.wave) return pl.n1 / 4;
-    return pl.n1 / rows_rk(pl);
+    return rows_dims(pl).wgs;
 }
 
-template <int L>
-static void launch_rows_pipe(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p0) {
-    // chains sharing one spectrum set: fold the batch into grid.x (needs a row-block count per image that is a multiple of
-    // the 8 XCDs, so that every XCD's share of the folded list holds whole groups of `batch` workgroups)
+// chains sharing one spectrum set: fold the batch into grid.x (needs a row-block count per image that is a multiple of
+// the 8 XCDs, so that every XCD's share of the folded list holds whole groups of `batch` workgroups)
+static inline bool rows_fold_ok(const FftPlan &pl, int shared_spec) {
     static const bool fold_wanted = [] {
         const char *e = getenv("SBTV_ROWS_FOLD");
         return !(e && e[0] == '0');
     }();
+    return fold_wanted && pl.wave && shared_spec && pl.batch > 1 && ((pl.n1 / 4) % 8 == 0);
+}
+template <int L>
+static void launch_rows_pipe(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p0) {
     RowsParams p = p0;
-    const bool fold = fold_wanted && p.shared_spec && pl.batch > 1 && ((pl.n1 / 4) % 8 == 0);
+    const bool fold = rows_fold_ok(pl, p.shared_spec);
     p.fold = fold ? pl.batch : 0;
-    const dim3 grid(fold ? (pl.n1 / 4) * pl.batch : pl.n1 / 4, fold ? 1 : pl.batch), block((1 << L) / 4);
+    const PassDims rd = rows_dims(pl);
+    const dim3 grid(fold ? rd.wgs * pl.batch : rd.wgs, fold ? 1 : pl.batch), block(rd.threads);
 #define SBTV_ROWS_OP(OP_)                                                                                     \
     case OP_: hipLaunchKernelGGL((rows_pipe_kernel<L, OP_>), grid, block, 0, ctx->stream, p); break;
     switch (p.op) {
@@ -1178,7 +1212,8 @@ static void launch_rows_pipe(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams 
 
 template <int L, int RK>
 static void launch_rows(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p) {
-    const dim3 grid(pl.n1 / RK, pl.batch), block(RK * ((1 << L) / 8));
+    const PassDims rd = rows_dims(pl);          // (fft_rows picks the instantiation with RK = rows_rk(pl))
+    const dim3 grid(rd.wgs, pl.batch), block(rd.threads);
 #define SBTV_ROWS_OP(OP_)                                                                                     \
     case OP_: hipLaunchKernelGGL((fft_rows_kernel<L, RK, OP_>), grid, block, 0, ctx->stream, p); break;
     switch (p.op) {
@@ -1219,7 +1254,7 @@ int fft_rows(sbtv_ctx *ctx, const FftPlan &pl, const double2 *Sin, double2 *Sout
     p.fold = 0;
     p.u_img = pl.u_img;
     p.u_tiled = pl.u_tiled;
-    if (a.op == OP_CSALSA && !fft_rows_csalsa_ok(pl)) return fail(ctx, SBTV_ERR_SIZE, "row pass: OP_CSALSA is not built for this plan");
+    SBTV_TRY(fft_rows_check(ctx, pl, a.op));
     if (pl.generic) return any_rows(ctx, pl, p, Sout);
     const int L = ilog2(pl.N);
     if (L > 12) return fail(ctx, SBTV_ERR_SIZE, "row FFT: N must be <= 4096");
@@ -1276,6 +1311,12 @@ int spec_unpack(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double2 *U) 
     return 0;
 }
 
+// values of l one thread of psf_spectrum_kernel walks (see the kernel)
+static inline int psf_lch(const FftPlan &pl) {
+    const size_t elems = (size_t)(pl.n1 + 1) * pl.N * pl.batch;
+    const int lch = (int)(elems >> 19);                 // 512^2, 1024^2: 1;  2048^2: 4;  8 x 1024^2: 8
+    return lch < 1 ? 1 : (lch > 16 ? 16 : lch);
+}
 // spectra of `nsets` (<= 3) tap sets of the same size: one launch (the arbitrary-size path: one call per set)
 int psf_spectrum_sets(sbtv_ctx *ctx, const FftPlan &pl, const double *const *taps_dev, int taille, double2 *const *U, int nsets) {
     const int thr = 64;
@@ -1285,9 +1326,7 @@ int psf_spectrum_sets(sbtv_ctx *ctx, const FftPlan &pl, const double *const *tap
         for (int q = 0; q < nsets; ++q) SBTV_TRY(any_psf_spectrum(ctx, pl, taps_dev[q], taille, U[q]));
         return 0;
     }
-    const size_t elems = (size_t)(pl.n1 + 1) * pl.N * pl.batch;
-    int lch = (int)(elems >> 19);                       // 512^2, 1024^2: 1;  2048^2: 4;  8 x 1024^2: 8
-    lch = lch < 1 ? 1 : (lch > 16 ? 16 : lch);
+    const int lch = psf_lch(pl);
     PsfSets ps{};
     for (int q = 0; q < 3; ++q) {
         ps.taps[q] = taps_dev[q < nsets ? q : 0];
@@ -1539,6 +1578,207 @@ int sbtv_diag_time_pass(sbtv_ctx *ctx, int pass, int M, int N, int batch, int re
     SBTV_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
     *ms_avg = (double)ms / reps;
     if (alg_bytes) *alg_bytes = bytes;
+    return canary_epilogue(ctx, 0);
+}
+
+int sbtv_diag_fft_plan(sbtv_ctx *ctx, int M, int N, int batch, int out[16]) {
+    if (!ctx || !out || batch < 1) return SBTV_ERR_BADARG;
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    FftPlan pl;
+    SBTV_TRY(fft_plan(ctx, M, N, batch, &pl));
+    for (int q = 0; q < 16; ++q) out[q] = 0;
+    out[0] = pl.generic;
+    out[1] = pl.wave;
+    out[2] = pl.n1;
+    const PassDims cd = cols_dims(pl), rd = rows_dims(pl);
+    out[3] = cd.per_wg;
+    out[4] = cd.threads;
+    out[5] = cd.wgs;
+    out[6] = rd.per_wg;
+    out[7] = rd.threads;
+    out[8] = rd.wgs;
+    out[9] = pl.generic ? 2 : (pl.wave ? 1 : 0);
+    if (pl.generic) {
+        int logL;
+        any_axis_len(M, &out[11], &logL);
+        any_axis_len(N, &out[12], &logL);
+    }
+    out[10] = pl.u_tiled;
+    out[13] = pl.generic ? 0 : psf_lch(pl);
+    out[14] = rows_fold_ok(pl, 1) ? 1 : 0;
+    out[15] = (fft_cols_tv_ok(pl) ? 1 : 0) | (fft_cols_inv_step_ok(pl) ? 2 : 0) | (fft_rows_csalsa_ok(pl) ? 4 : 0);
+    return 0;
+}
+
+int sbtv_diag_spectral_pass(sbtv_ctx *ctx, const sbtv_diag_pass *a) {
+    if (!ctx || !a) return SBTV_ERR_BADARG;
+    const int M = a->M, N = a->N, batch = a->batch, op = a->op, epi = a->epilogue;
+    // ---- everything that is refused is refused here, before the first launch
+    if (batch < 1 || !a->x || a->repeats < 1) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: bad arguments");
+    if (op < OP_NONE || op > OP_CSALSA) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: unknown operator");
+    if (epi < 0 || epi > 4) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: unknown epilogue");
+    const bool cs = op == OP_CSALSA;
+    const bool needY = op == OP_SALSA || op == OP_RESID || op == OP_GRAD || op == OP_GRADF || cs;
+    const bool needD = op == OP_GRAD;
+    if (op != OP_NONE && !a->taps) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: the operator needs taps");
+    if (needY && (!a->y || !a->acc)) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: the operator needs y and acc");
+    if (needD && (!a->d1taps || !a->d2taps)) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: OP_GRAD needs both derivative tap sets");
+    if ((op == OP_INVLS || op == OP_SALSA || cs) && !a->mu) return fail(ctx, SBTV_ERR_MISSING_LS, "diag_spectral_pass: the operator needs mu");
+    if (cs && (!a->cs || !a->e0 || (a->shared_spec && batch > 1)))
+        return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: OP_CSALSA needs cs and e0, and one state per image");
+    if (op != OP_NONE && (a->taille < 1 || a->taille > 15 || a->taille > M || a->taille > N))
+        return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    const bool book = epi == 1 || epi == 4;
+    if (book && (!a->u || !a->bu || !a->g_out || !a->sums)) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: bookkeeping needs u, bu, g_out, sums");
+    if (epi == 4 && (!a->bu_in || a->xprev)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_post: skip_x needs a separate bu_in and no xprev");
+    if (epi == 2 && !a->ystep) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: step needs ystep");
+    if (epi == 3 && (!a->sub_b || !a->g_out || a->frozen)) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: sub needs b and g_out and takes no frozen mask");
+    if ((epi == 2 || epi == 4) ? a->repeats != 1 : !a->x_out) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: x_out missing, or repeats with an epilogue that does not store x");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    FftPlan pl;
+    SBTV_TRY(fft_plan(ctx, M, N, batch, &pl));
+    SBTV_TRY(fft_rows_check(ctx, pl, op));
+    if (epi == 2) SBTV_TRY(fft_cols_step_check(ctx, pl, "fft_cols_inv_step"));
+    if (epi == 3) SBTV_TRY(fft_cols_step_check(ctx, pl, "fft_cols_inv_sub"));
+    if (epi == 4 && !pl.wave)
+        return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_post: bu_in + skip_x go together and need the wave-granular column pass");
+    if (a->tv && (!fft_cols_tv_ok(pl) || a->add)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_fwd: TV partials not available for this call");
+
+    const int nspec = a->shared_spec ? 1 : batch;
+    FftPlan ps = pl;                                        // the plan the operator spectra are built with
+    ps.batch = nspec;
+    const size_t P = (size_t)M * N, cnt = P * batch, scnt = P * nspec;
+    const size_t spec = pl.u_img * nspec;
+    const int tt = a->taille * a->taille;
+    double *x = nullptr, *add = nullptr, *xo = nullptr, *u = nullptr, *bu = nullptr, *bu2 = nullptr, *g = nullptr, *tru = nullptr,
+           *xprev = nullptr, *yimg = nullptr, *mu_d = nullptr, *cs_d = nullptr, *taps_d = nullptr, *acc = nullptr, *postp = nullptr,
+           *tvp = nullptr, *red = nullptr;
+    int *frozen_d = nullptr;
+    double2 *S = nullptr, *H = nullptr, *Y = nullptr, *D1 = nullptr, *D2 = nullptr, *E = nullptr;
+    auto up = [&](const char *name, const double *h, size_t n, double **d) -> int {
+        SBTV_TRY(ws_get_t(ctx, name, n, d));
+        if (h) SBTV_HIP(ctx, hipMemcpyAsync(*d, h, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    };
+    SBTV_TRY(up("diag.x", a->x, cnt, &x));
+    if (a->add) SBTV_TRY(up("diag.add", a->add, cnt, &add));
+    SBTV_TRY(up("diag.xo", a->x_out, cnt, &xo));            // (a frozen image keeps what the caller put there)
+    if (book) {
+        SBTV_TRY(up("diag.u", a->u, cnt, &u));
+        SBTV_TRY(up("diag.bu", a->bu, cnt, &bu));
+        if (epi == 4) SBTV_TRY(up("diag.bu2", a->bu_in, cnt, &bu2));
+        if (a->tru) SBTV_TRY(up("diag.tru", a->tru, cnt, &tru));
+        if (a->xprev) SBTV_TRY(up("diag.xprev", a->xprev, cnt, &xprev));
+    }
+    if (epi == 2) SBTV_TRY(up("diag.u", a->ystep, cnt, &u));
+    if (epi == 3) SBTV_TRY(up("diag.u", a->sub_b, cnt, &u));
+    if (book || epi == 3) SBTV_TRY(up("diag.g", a->g_out, cnt, &g));
+    SBTV_TRY(ws_get_t(ctx, "diag.S", (size_t)batch * pl.s_img, &S));
+    const int nrb = fft_rows_blocks(pl), npb = fft_cols_blocks(pl);
+    SBTV_TRY(ws_get_t(ctx, "diag.acc", (size_t)batch * 3 * nrb, &acc));
+    SBTV_TRY(ws_get_t(ctx, "diag.post", (size_t)batch * 6 * npb, &postp));
+    SBTV_TRY(ws_get_t(ctx, "diag.tvp", (size_t)batch * npb, &tvp));
+    SBTV_TRY(ws_get_t(ctx, "diag.red", (size_t)batch * 6, &red));
+    if (a->mu) SBTV_TRY(up("diag.mu", a->mu, (size_t)batch, &mu_d));
+    if (cs) SBTV_TRY(up("diag.cs", a->cs, 3, &cs_d));
+    if (a->frozen) {
+        SBTV_TRY(ws_get_t(ctx, "diag.frozen", (size_t)batch, &frozen_d));
+        SBTV_HIP(ctx, hipMemcpyAsync(frozen_d, a->frozen, sizeof(int) * batch, hipMemcpyHostToDevice, ctx->stream));
+    }
+    // operator spectra: the taps directly, images (y, the C-SALSA state) the way the loops build Y
+    auto image_spectrum = [&](const double *img_h, double2 *U) -> int {
+        SBTV_TRY(up("diag.yimg", img_h, scnt, &yimg));
+        RowsArgs r{};
+        r.dir_fwd = 1;
+        r.op = OP_NONE;
+        SBTV_TRY(fft_cols_fwd(ctx, ps, yimg, nullptr, S));
+        SBTV_TRY(fft_rows(ctx, ps, S, S, r));
+        return spec_unpack(ctx, ps, S, U);
+    };
+    auto taps_spectrum = [&](const char *name, const double *taps_h, double2 **U) -> int {
+        SBTV_TRY(ws_get_t(ctx, name, spec, U));
+        SBTV_TRY(up("diag.taps", taps_h, (size_t)nspec * tt, &taps_d));
+        return psf_spectrum(ctx, ps, taps_d, a->taille, *U);
+    };
+    if (op != OP_NONE) SBTV_TRY(taps_spectrum("diag.H", a->taps, &H));
+    if (needD) {
+        SBTV_TRY(taps_spectrum("diag.D1", a->d1taps, &D1));
+        SBTV_TRY(taps_spectrum("diag.D2", a->d2taps, &D2));
+    }
+    if (needY) {
+        SBTV_TRY(ws_get_t(ctx, "diag.Y", spec, &Y));
+        SBTV_TRY(image_spectrum(a->y, Y));
+    }
+    if (cs) {
+        SBTV_TRY(ws_get_t(ctx, "diag.E", spec, &E));
+        SBTV_TRY(image_spectrum(a->e0, E));
+    }
+    const double inv_scale = 1.0 / ((double)pl.n1 * N);
+    for (int rep = 0; rep < a->repeats; ++rep) {
+        // (a frozen image writes no partial sums: its sums read as zero)
+        SBTV_HIP(ctx, hipMemsetAsync(acc, 0, sizeof(double) * batch * 3 * nrb, ctx->stream));
+        SBTV_HIP(ctx, hipMemsetAsync(postp, 0, sizeof(double) * batch * 6 * npb, ctx->stream));
+        SBTV_HIP(ctx, hipMemsetAsync(tvp, 0, sizeof(double) * batch * npb, ctx->stream));
+        // (passes after the first transform the x of the pass before; the stream orders its read before the new store)
+        SBTV_TRY(fft_cols_fwd_f(ctx, pl, rep == 0 ? x : xo, add, S, frozen_d, a->tv ? tvp : nullptr));
+        RowsArgs r{};
+        r.dir_fwd = r.dir_inv = 1;
+        r.op = op;
+        r.H = H;
+        r.Y = Y;
+        r.D1 = D1;
+        r.D2 = D2;
+        r.E = E;
+        r.cs = cs_d;
+        r.mu = mu_d;
+        r.acc = acc;
+        r.frozen = frozen_d;
+        r.shared_spec = a->shared_spec ? 1 : 0;
+        SBTV_TRY(fft_rows(ctx, pl, S, S, r));
+        ColsPost cp;
+        switch (epi) {
+            case 0: SBTV_TRY(fft_cols_inv_f(ctx, pl, S, xo, inv_scale, frozen_d)); break;
+            case 1:
+            case 4:
+                cp.u = u;
+                cp.bu = bu;
+                cp.g = g;
+                cp.tru = tru;
+                cp.xprev = xprev;
+                cp.partials = postp;
+                if (epi == 4) {
+                    cp.bu_in = bu2;
+                    cp.skip_x = 1;
+                }
+                SBTV_TRY(fft_cols_inv_post(ctx, pl, S, xo, inv_scale, frozen_d, cp));
+                break;
+            case 2: SBTV_TRY(fft_cols_inv_step(ctx, pl, S, u, inv_scale, a->alpha, frozen_d)); break;
+            default: SBTV_TRY(fft_cols_inv_sub(ctx, pl, S, xo, inv_scale, u, g)); break;
+        }
+    }
+    auto down = [&](double *h, const double *d, size_t n) -> int {
+        if (h) SBTV_HIP(ctx, hipMemcpyAsync(h, d, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        return 0;
+    };
+    if (a->acc) {
+        SBTV_TRY(reduce_partials(ctx, acc, batch * 3, nrb, red));
+        SBTV_TRY(down(a->acc, red, (size_t)batch * 3));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (a->sums && book) {
+        SBTV_TRY(reduce_partials(ctx, postp, batch * 6, npb, red));
+        SBTV_TRY(down(a->sums, red, (size_t)batch * 6));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (a->tv) {
+        SBTV_TRY(reduce_partials(ctx, tvp, batch, npb, red));
+        SBTV_TRY(down(a->tv, red, (size_t)batch));
+    }
+    if (epi != 2 && epi != 4) SBTV_TRY(down(a->x_out, xo, cnt));
+    if (book) SBTV_TRY(down(a->bu, bu, cnt));
+    if (book || epi == 3) SBTV_TRY(down(a->g_out, g, cnt));
+    if (epi == 2) SBTV_TRY(down(a->ystep, u, cnt));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return canary_epilogue(ctx, 0);
 }
 

@@ -199,17 +199,22 @@ __global__ __launch_bounds__(64) void any_psf_spectrum_kernel(const double *__re
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
+// Bluestein length of an n-point line: the next power of two >= 2 n - 1
+static inline void any_axis_len(int n, int *L_out, int *logL_out) {
+    int L = 1, logL = 0;
+    while (L < 2 * n - 1) { L <<= 1; ++logL; }
+    *L_out = L;
+    *logL_out = logL;
+}
 static int any_axis_get(sbtv_ctx *ctx, int n, AnyAxis *ax) {
+    int L, logL;
+    any_axis_len(n, &L, &logL);
     auto it = ctx->any_axes.find(n);
     if (it != ctx->any_axes.end()) {
         const double2 *base = it->second;
-        int L = 1, logL = 0;
-        while (L < 2 * n - 1) { L <<= 1; ++logL; }
         *ax = AnyAxis{n, L, logL, base, base + n, base + n + L, nullptr};
         return twiddle_get(ctx, L, &ax->twL);
     }
-    int L = 1, logL = 0;
-    while (L < 2 * n - 1) { L <<= 1; ++logL; }
     typedef long double ld;
     const ld PI = 3.14159265358979323846264338327950288L;
     std::vector<ld> cr(n), ci(n);
@@ -310,12 +315,12 @@ static int any_cols_inv(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, doub
     return 0;
 }
 
-constexpr int ANY_SPEC_BLOCKS = 256;
+constexpr int ANY_SPEC_BLOCKS = 256, ANY_SPEC_THREADS = 256;
 
 static int any_rows(sbtv_ctx *ctx, const FftPlan &pl, const RowsParams &p0, double2 *Sout) {
     RowsParams p = p0;
     const size_t P = (size_t)pl.M * pl.N;
-    const dim3 grid(ANY_SPEC_BLOCKS, pl.batch), block(256);
+    const dim3 grid(ANY_SPEC_BLOCKS, pl.batch), block(ANY_SPEC_THREADS);
     if (p.op == OP_NONE) {          // the 2-D transforms live in the column passes: nothing to do but a copy
         if (Sout && Sout != p.Sin)
             SBTV_HIP(ctx, hipMemcpyAsync(Sout, p.Sin, sizeof(double2) * P * pl.batch, hipMemcpyDeviceToDevice, ctx->stream));

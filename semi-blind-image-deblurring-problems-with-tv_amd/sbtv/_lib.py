@@ -58,6 +58,14 @@ class sbtv_moments_opts(C.Structure):
     _fields_ = [("first", C.c_int), ("thin", C.c_int), ("pooled", C.c_int)]
 
 
+class sbtv_diag_pass(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("M", "N", "batch", "op", "epilogue", "taille", "shared_spec", "repeats")]
+                + [(n, C.c_void_p) for n in ("x", "add", "taps", "d1taps", "d2taps", "y", "e0", "mu", "cs", "frozen", "u",
+                                             "bu_in", "tru", "xprev", "sub_b")]
+                + [("alpha", C.c_double)]
+                + [(n, C.c_void_p) for n in ("bu", "ystep", "x_out", "g_out", "acc", "sums", "tv")])
+
+
 def vptr(a):
     """void* of a NumPy array's data.  (numpy's `a.ctypes` builds a helper object on every access, ~25 us a time: with
     seven output arrays that was a third of the fixed cost of a SALSA call.)  The caller keeps `a` alive."""
@@ -142,6 +150,8 @@ SIGNATURES = {
     "sbtv_diag_canary": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "sbtv_diag_prox_variant": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
     "sbtv_diag_prox_geometry": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
+    "sbtv_diag_fft_plan": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
+    "sbtv_diag_spectral_pass": (_I, [_P, C.POINTER(sbtv_diag_pass)]),
     "sbtv_last_host_stats": (_I, [_P, C.POINTER(_D)]),
     "sbtv_diag_workspace": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "sbtv_diag_switches": (_I, [C.c_char_p, C.c_size_t]),
@@ -279,6 +289,96 @@ class Context:
         g = dict(zip(self.GEOMETRY, out))
         g["order"] = bool(g["order"])
         return g
+
+    FFT_PLAN = ("generic", "wave", "n1", "cols_per_wg", "cols_threads", "cols_wgs", "rows_per_wg", "rows_threads",
+                "rows_wgs", "rows_kind", "u_tiled", "L_M", "L_N", "lch", "fold", "caps")
+
+    def fft_plan(self, M, N, batch=1):
+        """Which FFT kernels an M x N x batch problem takes (sbtv_diag_fft_plan): path, workgroup shapes of the column
+        and row passes, Bluestein lengths, `lch` of the tap-spectrum launch, whether a shared-spectrum batch folds, and
+        which optional forms the plan has (tv_ok, step_ok, csalsa_ok)."""
+        out = (_I * 16)()
+        self.check(self.lib.sbtv_diag_fft_plan(self.h, int(M), int(N), int(batch), out))
+        p = dict(zip(self.FFT_PLAN, out))
+        caps = p.pop("caps")
+        for k in ("generic", "wave", "u_tiled", "fold"):
+            p[k] = bool(p[k])
+        p["rows_kind"] = {0: "workgroup", 1: "pipelined", 2: "pointwise"}[p["rows_kind"]]
+        p.update(tv_ok=bool(caps & 1), step_ok=bool(caps & 2), csalsa_ok=bool(caps & 4))
+        return p
+
+    SPEC_OPS = {"none": 0, "mul_h": 1, "mul_hc": 2, "invls": 3, "salsa": 4, "resid": 5, "grad": 6, "ata": 7, "gradf": 8,
+                "csalsa": 9}
+    EPILOGUES = {"plain": 0, "post": 1, "step": 2, "sub": 3, "post_skip_x": 4}
+
+    def spectral_pass(self, x, op="none", epilogue="plain", taps=None, d1taps=None, d2taps=None, y=None, mu=None,
+                      cs=None, e0=None, add=None, shared_spec=False, repeats=1, frozen=None, u=None, bu=None, bu_in=None,
+                      tru=None, xprev=None, ystep=None, alpha=0.0, sub_b=None, tv=False, sentinel=0.0):
+        """One forward-column, row, inverse-column triple on caller data (sbtv_diag_spectral_pass).  Images are (B, M, N)
+        or (M, N) NumPy arrays; taps (B or 1, t, t) or (t, t); y / e0 one image per tap set.  Returns a dict with the
+        arrays the epilogue writes (x, bu, g, ystep), acc (B, 3), sums (B, 6) and tv (B,) where they exist.  Outputs of a
+        frozen image hold `sentinel` (bu: its input)."""
+        def cm(a, lead=None):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 2:
+                a = a[None]
+            if lead is not None and a.shape[0] != lead:
+                raise ValueError("leading dimension %d, expected %d" % (a.shape[0], lead))
+            return np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
+        xc = cm(x)
+        B, N, M = xc.shape
+        ns = 1 if shared_spec else B
+        keep = [xc]
+        a = sbtv_diag_pass()
+        a.M, a.N, a.batch = M, N, B
+        a.op = self.SPEC_OPS[op] if isinstance(op, str) else int(op)
+        a.epilogue = self.EPILOGUES[epilogue] if isinstance(epilogue, str) else int(epilogue)
+        a.shared_spec, a.repeats, a.alpha = int(bool(shared_spec)), int(repeats), float(alpha)
+        a.x = vptr(xc)
+        tc = cm(taps, ns)
+        a.taille = tc.shape[1] if tc is not None else 0
+        for name, arr in (("add", cm(add, B)), ("taps", tc), ("d1taps", cm(d1taps, ns)), ("d2taps", cm(d2taps, ns)),
+                          ("y", cm(y, ns)), ("e0", cm(e0, ns)), ("u", cm(u, B)), ("bu_in", cm(bu_in, B)),
+                          ("tru", cm(tru, B)), ("xprev", cm(xprev, B)), ("sub_b", cm(sub_b, B))):
+            if arr is not None:
+                keep.append(arr)
+                setattr(a, name, vptr(arr))
+        for name, arr, n in (("mu", mu, B), ("cs", cs, 3)):
+            if arr is not None:
+                v = np.ascontiguousarray(np.broadcast_to(np.asarray(arr, dtype=np.float64), (n,)))
+                keep.append(v)
+                setattr(a, name, vptr(v))
+        if frozen is not None:
+            fz = np.ascontiguousarray(np.asarray(frozen, dtype=np.int32).reshape(B))
+            keep.append(fz)
+            a.frozen = vptr(fz)
+        out = {}
+        ep = a.epilogue
+        if ep in (0, 1, 3):
+            out["x"] = np.full((B, N, M), float(sentinel))
+            a.x_out = vptr(out["x"])
+        if ep in (1, 3, 4):
+            out["g"] = np.full((B, N, M), float(sentinel))
+            a.g_out = vptr(out["g"])
+        if ep in (1, 4):
+            out["sums"] = np.zeros((B, 6))
+            a.sums = vptr(out["sums"])
+            if bu is not None:
+                out["bu"] = cm(bu, B)
+                a.bu = vptr(out["bu"])
+        if ep == 2 and ystep is not None:
+            out["ystep"] = cm(ystep, B)
+            a.ystep = vptr(out["ystep"])
+        out["acc"] = np.zeros((B, 3))
+        a.acc = vptr(out["acc"])
+        if tv:
+            out["tv"] = np.zeros(B)
+            a.tv = vptr(out["tv"])
+        self.check(self.lib.sbtv_diag_spectral_pass(self.h, C.byref(a)))
+        del keep
+        return {k: (np.transpose(v, (0, 2, 1)) if v.ndim == 3 else v) for k, v in out.items()}
 
     def last_timing(self):
         out = (C.c_double * 4)()

@@ -227,8 +227,8 @@ def conv2c(x, h, ctx=None):
     """y = conv2c(x, h)  (SALSA/conv2c.m:1-50): circular 2-D convolution with the mask origin at floor((1+size)/2).
 
     Runs on the spectral blur operator (whose mask origin is the top-left tap, utils/resize.m:8): the mask is embedded
-    in a square tap array and the result rotated back by the origin offset.  Needs power-of-two image sizes like the
-    operator; masks up to 15 x 15."""
+    in a square tap array and the result rotated back by the origin offset.  Any image size the operator takes
+    (2 <= M, N <= 4096, powers of two or not); masks up to 15 x 15 that fit inside the image."""
     hh = np.atleast_2d(np.asarray(h, dtype=np.float64))
     mm, nm = hh.shape
     xi = L.Images(x)

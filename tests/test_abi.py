@@ -43,7 +43,8 @@ def test_struct_layouts_match_header():
     import tempfile
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "sbtv.h"\nint main(void){printf("%zu %zu %zu %zu\\n",'
            'sizeof(sbtv_sapg_opts), offsetof(sbtv_sapg_opts, seed), sizeof(sbtv_salsa_opts),'
-           'offsetof(sbtv_sapg_opts, lambda));return 0;}\n')
+           'offsetof(sbtv_sapg_opts, lambda));printf("%zu %zu %zu\\n", sizeof(sbtv_diag_pass),'
+           'offsetof(sbtv_diag_pass, alpha), offsetof(sbtv_diag_pass, tv));return 0;}\n')
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "t.c"), "w").write(src)
         subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o",
@@ -53,6 +54,8 @@ def test_struct_layouts_match_header():
     assert int(out[1]) == _lib.sbtv_sapg_opts.seed.offset
     assert int(out[2]) == C.sizeof(_lib.sbtv_salsa_opts)
     assert int(out[3]) == _lib.sbtv_sapg_opts.lambda_.offset
+    assert int(out[4]) == C.sizeof(_lib.sbtv_diag_pass)
+    assert int(out[5]) == _lib.sbtv_diag_pass.alpha.offset and int(out[6]) == _lib.sbtv_diag_pass.tv.offset
 
 
 def test_psf_taps_match_oracle():
