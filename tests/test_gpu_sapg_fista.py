@@ -520,7 +520,7 @@ def test_sapg_shared_gradient_chains_match_oracle(ctx):
 def test_sapg_shared_chains_peer_failure_is_reported_not_waited_for(ctx):
     """The 6th reduced element counts ranks whose iteration failed: a rank that sees it non-zero after the
     all-reduce returns SBTV_ERR_PEER instead of going on alone (a failing rank still joins the collective first,
-    sapg.hip `iterate_device`), so no rank is left waiting inside the next all-reduce."""
+    sapg.hip `host_loop`), so no rank is left waiting inside the next all-reduce."""
     import sbtv
     import sbtv_oracle as o
     M = N = 32

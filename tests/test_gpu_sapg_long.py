@@ -1,7 +1,7 @@
 """GPU: long SAPG chains (round-3 review item 1).
 
 (a) device-resident loop against the host-side loop over 2 100 samples after 1 100 warm-up steps (both cross the
-    `(ii & 1023) == 0` synchronisation of csrc/sapg.hip twice, warm-up once), eager and under graph replay;
+    `(ii & 1023) == 0` synchronisation of `device_loop` in csrc/sapg.hip twice, warm-up once), eager and under graph replay;
 (b) oracle parity with injected noise over 320 samples at 64^2 for the three PSF families with the REFERENCE'S OWN
     step scales, so that the projections of SAPG_algorithm_Guassian.m:166-194 engage and release: whole traces, the EB
     estimates and the running-mean / tolerance logs (:217-284) against the committed oracle fixture with sigma^2 fixed;
