@@ -281,6 +281,59 @@ int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
                       double *x_out, double *objective, double *distance, double *times, double *mses,
                       int *numA, int *numAt, int *n_outer, int flags);
 
+/* ---- wavelet-l1 deconvolution: the redundant wavelet frame and its SALSA driver ----------------------------------
+ * Replaces mrdwt_TI2D / mirdwt_TI2D / soft of the reference (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m, soft.m) and the solve of
+ * SALSA/run_deblur_synthesis_L1.m:160-180 (SALSA_v2 with 'Psi' / 'LS').  The Rice Wavelet Toolbox MEX behind the reference's
+ * two wrappers is not shipped (SALSA/mrdwt.m is a comment block); the transform is defined here.
+ *
+ * h: orthonormal scaling filter of even length hlen = K, 2 <= K <= 8, sum(h) = sqrt(2); h0 = h, h1[k] = (-1)^k h[K-1-k].
+ * J = levels - 1 decomposition steps (the reference's convention: levels = 4 gives 10 bands).  Level j = 1..J, stride
+ * s = 2^(j-1), along one dimension of length n with circular indices:
+ *     lo[i] = (1/sqrt 2) sum_k h0[k] a[(i + s k) mod n],     hi[i] = (1/sqrt 2) sum_k h1[k] a[(i + s k) mod n]
+ * first along dimension 1 (the contiguous row index of the column-major image), then along dimension 2.  Level j turns the
+ * approximation a_{j-1} (a_0 = x) into a_j = (lo, lo) and the details LH, HL, HH (first letter: the filter along dimension 1).
+ * z holds 3J+1 consecutive M x N column-major images per input image: band 0 = a_J, bands 1+3(j-1) .. 3+3(j-1) = LH, HL, HH
+ * of level j; in memory the reference's M x (3J+1)N matrix [temp1 temp2] with the rescaling of mrdwt_TI2D.m:19-23 applied
+ * (the 1/sqrt 2 per dimension).  The 1-D convention reproduces the example of SALSA/mrdwt.m:38-40.
+ * sbtv_mrdwt_TI2D is the analysis operator W', sbtv_mirdwt_TI2D the synthesis operator W, its exact adjoint (transposed
+ * filters, index (i - s k) mod n).  For an orthonormal h the frame is Parseval at every image size: W W' = I, ||W'x|| = ||x||.
+ * Any M, N with (K-1) 2^(J-1) < min(M, N) (a tap wraps at most once), else SBTV_ERR_SIZE; K odd or outside 2..8,
+ * levels < 2, h == NULL -> SBTV_ERR_BADARG; all refused before any GPU work.  The bare transforms accept any h.
+ * One kernel launch per level: 5 * M*N * 8 bytes of traffic each. */
+int sbtv_mrdwt_TI2D(sbtv_ctx *ctx, const double *x, int M, int N, int batch,
+                    const double *h, int hlen, int levels, double *z, int flags);
+int sbtv_mirdwt_TI2D(sbtv_ctx *ctx, const double *z, int M, int N, int batch,
+                     const double *h, int hlen, int levels, double *x, int flags);
+/* out = soft(x, T) = sign(x) .* max(abs(x) - T, 0) (SALSA/soft.m) on `batch` arrays of M*N doubles, T[batch] >= 0 (host);
+ * T = 0 passes x through. */
+int sbtv_soft(sbtv_ctx *ctx, const double *x, int M, int N, int batch, const double *T, double *out, int flags);
+/* min over xw  0.5 ||y - B W xw||^2 + tau ||xw||_1  (B: circular blur of `taps`), as SALSA/SALSA_v2.m:389-494 solves it with
+ * TVINITIALIZATION = 0, Psi = soft, Phi = l1, A = B W, AT = W' B' and the invLS of run_deblur_synthesis_L1.m:169-170.
+ * With W W' = I one outer iteration of that is exactly
+ *     u  = soft(xw - bu, tau/mu) ;  s = u + bu ;  z = W s
+ *     X  = (conj(H) .* fft2(y) + mu * fft2(z)) ./ (abs(H).^2 + mu) ;  xi = real(ifft2(X))
+ *     we = W'(xi - z) ;  xw = s + we ;  bu = -we
+ *     objective(outer+1) = 0.5 ||y - B xi||^2 + tau ||u||_1      (W xw = xi is the image estimate)
+ * which is what runs (no division by mu).  Start xw by opts->initialization: 0 zeros, 2 W' B' y, 33333 xw_init; u = xw,
+ * bu = 0, objective(1) from that state.  Stop rules 1, 2, 3 and the traces as SALSA_v2.m:442-482.
+ * true_xw / xw_init / xw_out: [batch][3J+1][M*N] coefficients in the layout of sbtv_mrdwt_TI2D; x_out (optional): W xw_out.
+ * objective / times / mses: [batch*(maxiter+1)], mses against true_xw over all coefficients; distance: [batch*maxiter] =
+ * ||xw - u|| / sqrt(||xw||^2 + ||u||^2); numA = 1 + one per outer iteration, numAt = 1 (W' B' y), as SALSA_v2 counts them.
+ * opts->TViters and the Chambolle knobs are ignored; opts->speculate bit 0: the host evaluates the stop rule one iteration
+ * late while the next iteration already runs (the state is double-buffered: the result is that of the stopping iteration).
+ * Images of a batch are solved one after another, image k bit for bit as alone.
+ * Errors before any GPU work: those of the transforms; h not orthonormal (|sum h - sqrt 2| > 1e-10 or
+ * |sum_k h[k] h[k+2m] - delta_m| > 1e-10) or mu[b] <= 0 -> SBTV_ERR_BADARG; odd pixel count -> SBTV_ERR_SIZE; stop criterion
+ * and initialization as sbtv_SALSA_v2. */
+int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                       const double *taps, int taille,
+                       const double *h, int hlen, int levels,
+                       const double *tau, const double *mu, const sbtv_salsa_opts *opts,
+                       const double *true_xw, const double *xw_init,
+                       double *xw_out, double *x_out,
+                       double *objective, double *distance, double *times, double *mses,
+                       int *numA, int *numAt, int *n_outer, int flags);
+
 /* ---- a-8: FISTA with the TV prox ----------------------------------------
  * Replaces my_fista(b,A,AT,tau,L,Phi,Psi,stopcriterion,tolerance,maxiters,true,verbose)
  * (SALSA/my_fista.m:5-56) with Psi = cold-start Chambolle(prox_iters) and Phi = TVnorm

@@ -344,6 +344,75 @@ __global__ __launch_bounds__(AB) void masked_post_kernel(const double *__restric
     ad_store_partials<NQ>(acc, partials);
 }
 
+// ---- wavelet-l1 SALSA (wavelet_one) -------------------------------------------------------------------------------
+// l1 norm of the start xw and its distance to the true coefficients: partials [2][nb]
+__global__ __launch_bounds__(AB) void wav_init_kernel(const double *__restrict__ xw, const double *__restrict__ tru,
+                                                       double *__restrict__ partials, size_t C) {
+    double acc[2] = {0.0, 0.0};
+    AD_LOOP(q, C) {
+        const double2 v = AD_LD(xw, q);
+        acc[0] += fabs(v.x) + fabs(v.y);
+        if (tru) {
+            const double2 t = AD_LD(tru, q);
+            const double m0 = v.x - t.x, m1 = v.y - t.y;
+            acc[1] += m0 * m0 + m1 * m1;
+        }
+    }
+    ad_store_partials<2>(acc, partials);
+}
+
+// The prox of an outer iteration on the state (s, we) of the previous one, xw = s + we and bu = -we:
+//   u = soft(xw - bu, T) = soft(s + 2 we, T) ; s' = u + bu = u - we ; partials [2][nb]: |u|, u^2
+__global__ __launch_bounds__(AB) void wav_prox_kernel(const double *__restrict__ s, const double *__restrict__ we,
+                                                       double *__restrict__ sn, double T, double *__restrict__ partials,
+                                                       size_t C) {
+    double acc[2] = {0.0, 0.0};
+    AD_LOOP(q, C) {
+        const double2 sv = AD_LD(s, q), wv = AD_LD(we, q);
+        const double u0 = wav_soft(sv.x + 2.0 * wv.x, T), u1 = wav_soft(sv.y + 2.0 * wv.y, T);
+        AD_ST(sn, q, make_double2(u0 - wv.x, u1 - wv.y));
+        acc[0] += fabs(u0) + fabs(u1);
+        acc[1] += u0 * u0 + u1 * u1;
+    }
+    ad_store_partials<2>(acc, partials);
+}
+
+// After the analysis we' = W'(xi - z) of an outer iteration: xw' = s' + we', u = s' + we (we: the previous iteration's), so
+// xw' - u = we' - we.  partials [4][nb]: (xw'-u)^2, xw'^2, (xw'-true)^2, (xw'-xw)^2 with xw = s + we (sp == null: not summed)
+__global__ __launch_bounds__(AB) void wav_post_kernel(const double *__restrict__ sn, const double *__restrict__ wn,
+                                                       const double *__restrict__ we, const double *__restrict__ sp,
+                                                       const double *__restrict__ tru, double *__restrict__ partials,
+                                                       size_t C) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    AD_LOOP(q, C) {
+        const double2 sv = AD_LD(sn, q), wv = AD_LD(wn, q), wo = AD_LD(we, q);
+        const double x0 = sv.x + wv.x, x1 = sv.y + wv.y;
+        const double d0 = wv.x - wo.x, d1 = wv.y - wo.y;
+        acc[0] += d0 * d0 + d1 * d1;
+        acc[1] += x0 * x0 + x1 * x1;
+        if (tru) {
+            const double2 t = AD_LD(tru, q);
+            const double m0 = x0 - t.x, m1 = x1 - t.y;
+            acc[2] += m0 * m0 + m1 * m1;
+        }
+        if (sp) {
+            const double2 so = AD_LD(sp, q);
+            const double m0 = x0 - (so.x + wo.x), m1 = x1 - (so.y + wo.y);
+            acc[3] += m0 * m0 + m1 * m1;
+        }
+    }
+    ad_store_partials<4>(acc, partials);
+}
+
+// xw = s + we
+__global__ __launch_bounds__(AB) void wav_sum_kernel(const double *__restrict__ s, const double *__restrict__ we,
+                                                      double *__restrict__ xw, size_t C) {
+    AD_LOOP(q, C) {
+        const double2 sv = AD_LD(s, q), wv = AD_LD(we, q);
+        AD_ST(xw, q, make_double2(sv.x + wv.x, sv.y + wv.y));
+    }
+}
+
 inline int ad_blocks(size_t P) {
     size_t nb = (P / 2 + AB - 1) / AB;
     if (nb > 1024) nb = 1024;
@@ -1160,6 +1229,176 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Wavelet-l1 deconvolution in the synthesis form (SALSA/run_deblur_synthesis_L1.m:160-180):
+//     min over xw   0.5 ||y - B W xw||^2 + tau ||xw||_1,
+// W the Parseval frame of wavelet.hip (W W' = I), solved as SALSA_v2.m:389-494 does with Psi = soft, Phi = l1, A = B W,
+// AT = W' B' and invLS(r) = (r - W' F W r) / mu, F = |H|^2 / (|H|^2 + mu) in the Fourier domain.  With W W' = I one outer
+// iteration of that is exactly
+//     u = soft(xw - bu, tau / mu) ; s = u + bu ; z = W s ;
+//     X = (conj(H) fft2(y) + mu fft2(z)) / (|H|^2 + mu) ; xi = real(ifft2(X))      (the row pass OP_SALSA on z)
+//     we = W'(xi - z) ; xw = s + we ; bu = -we
+// with the image estimate W xw = xi and ||y - B xi||^2 from the row pass's Parseval sum.  The coefficient state is (s, we):
+// the next prox input is s + 2 we.  Both and xi are double-buffered, so the result of the stopping iteration is intact when
+// the host evaluates the stop rule one iteration late.  Per outer iteration: the prox pass, one synthesis (J launches), the
+// FFT triple, the difference, one analysis (J launches), the sums pass and one reduction launch.
+int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
+                double mu, const sbtv_salsa_opts *opts, const double *td, const double *xwi, double *xw_out_dev,
+                double *x_out_dev, double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
+                int *n_outer) {
+    AdmmCommon c;
+    SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
+    const size_t P = c.P, C = P * wp.bands();
+    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
+    double *sbuf[2], *wbuf[2], *xibuf[2], *z, *d, *par, *partials, *sums, *acc;
+    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &sbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &sbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &wbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "wav.we1", C, &wbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &xibuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &xibuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &z));
+    SBTV_TRY(ws_get_t(ctx, "admm.g", P, &d));
+    SBTV_TRY(ws_get_t(ctx, "admm.par", (size_t)4, &par));               // mu
+    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..1] prox sums, [2..5] post sums, nb each
+    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0] |u|, [1] u^2, [2..5] post sums, [8] resid2
+    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
+    double *hs = nullptr;
+    {
+        void *pz = nullptr;
+        SBTV_TRY(pinned_get(ctx, sizeof(double) * 192, &pz));
+        hs = static_cast<double *>(pz);
+    }
+    {
+        const double h[4] = {mu, 0.0, 0.0, 0.0};
+        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const double T = tau / mu;                                           // :394
+    const int maxiter = opts->maxiter;
+    int h_numA = 0, h_numAt = 1;                                         // ATy (:288)
+    ctx->calls += 2;                                                     // AT(y), invLS(ATy)
+    // the start xw as the state (s, we) = (xw, 0): bu = -we = 0 (:367-393)
+    double *s0 = sbuf[0];
+    if (opts->initialization == 0) {
+        SBTV_HIP(ctx, hipMemsetAsync(s0, 0, sizeof(double) * C, ctx->stream));
+        ctx->calls += 1;
+    } else if (opts->initialization == 2) {                              // xw = W' B' y
+        SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, yd, d));
+        SBTV_TRY(wav_analysis(ctx, wp, d, s0, 1));
+    } else {
+        SBTV_HIP(ctx, hipMemcpyAsync(s0, xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    SBTV_HIP(ctx, hipMemsetAsync(wbuf[0], 0, sizeof(double) * C, ctx->stream));
+    // initial objective (:399-401): resid = y - B W xw
+    {
+        RowsArgs a{};
+        a.dir_fwd = 1;
+        a.op = OP_RESID;
+        a.H = c.Hs;
+        a.Y = c.Ys;
+        a.acc = acc;
+        SBTV_TRY(wav_synthesis(ctx, wp, s0, xibuf[0], 1));
+        SBTV_TRY(fft_cols_fwd(ctx, c.fp, xibuf[0], nullptr, c.S));
+        SBTV_TRY(fft_rows(ctx, c.fp, c.S, nullptr, a));
+        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
+        hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)s0, td, partials, C);
+        RedJobs jb;
+        jb.add(partials, 2, nb, sums);
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        h_numA += 1;
+        ctx->calls += 1;
+        const double f0 = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
+        if (objective) objective[0] = f0;
+        if (times) times[0] = 0.0;
+        if (mses && td) mses[0] = hs[1] / (double)C;                     // :414
+        hs[15] = f0;
+    }
+    double obj_prev = hs[15];
+    const auto t0 = std::chrono::steady_clock::now();
+    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    const int lag = (opts->speculate & 1) ? 1 : 0;
+    AdmmSlots slots;
+    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    double *hslot[2] = {hs, hs + 96};
+    auto enqueue = [&](int outer) -> int {                               // :423
+        const int o = outer & 1, p = o ^ 1;
+        double *sn = sbuf[o], *wn = wbuf[o], *xi = xibuf[o];
+        const double *sp = sbuf[p], *we = wbuf[p];
+        hipLaunchKernelGGL(wav_prox_kernel, dim3(nb), dim3(AB), 0, ctx->stream, sp, we, sn, T, partials, C);      // :432
+        SBTV_TRY(wav_synthesis(ctx, wp, sn, z, 1));
+        {                                                                // :434-436
+            RowsArgs a{};
+            a.dir_fwd = 1;
+            a.dir_inv = 1;
+            a.op = OP_SALSA;
+            a.H = c.Hs;
+            a.Y = c.Ys;
+            a.mu = par;
+            a.acc = acc;
+            SBTV_TRY(fft_cols_fwd(ctx, c.fp, z, nullptr, c.S));
+            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
+            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xi, c.inv_scale));
+        }
+        hipLaunchKernelGGL(ad_sub_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xi, (const double *)z, d, P);
+        SBTV_TRY(wav_analysis(ctx, wp, d, wn, 1));
+        hipLaunchKernelGGL(wav_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sn, (const double *)wn, we,
+                           (opts->stopcriterion == 2) ? sp : (const double *)nullptr, td, partials + (size_t)2 * nb, C);
+        RedJobs jb;
+        jb.add(partials, 6, nb, sums);
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_HIP(ctx, hipMemcpyAsync(hslot[o], sums, sizeof(double) * 12, hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipEventRecord(slots.ev[o], ctx->stream));
+        return 0;
+    };
+    bool stop = false;
+    // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
+    auto process = [&](int outer) -> int {
+        const double *hsl = hslot[outer & 1];
+        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
+        h_numA += 1;                                                     // :443
+        ctx->calls += 2;                                                 // invLS, A
+        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :444
+        if (objective) objective[outer] = f;
+        if (mses && td) mses[outer] = hsl[4] / (double)C;                // :446-449
+        if (distance) distance[outer - 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[1]);   // :451
+        if (times) times[outer] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (outer > 1) {                                                 // :453
+            double crit;
+            if (opts->stopcriterion == 1)
+                crit = fabs(f - obj_prev) / obj_prev;                    // :458
+            else if (opts->stopcriterion == 2)
+                crit = fabs(sqrt(hsl[5]) / sqrt(hsl[3]));                // :462
+            else
+                crit = f;                                                // :465
+            stop = crit < opts->tolA;                                    // :472
+        }
+        obj_prev = f;
+        return 0;
+    };
+    int last = 0;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
+    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SBTV_TRY(loop_timing(ctx, 0.0, 0, 1, P));
+    hipLaunchKernelGGL(wav_sum_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sbuf[last & 1],
+                       (const double *)wbuf[last & 1], xw_out_dev, C);
+    SBTV_HIP(ctx, hipGetLastError());
+    if (x_out_dev)
+        SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xibuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (numA) *numA = h_numA;
+    if (numAt) *numAt = h_numAt;
+    if (n_outer) *n_outer = last;
+    return 0;
+}
+
 }  // namespace
 }  // namespace sbtv
 
@@ -1298,6 +1537,52 @@ int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
         }));
     }
     SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return canary_epilogue(ctx, 0);
+}
+
+int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                       const double *h, int hlen, int levels, const double *tau, const double *mu,
+                       const sbtv_salsa_opts *opts, const double *true_xw, const double *xw_init, double *xw_out,
+                       double *x_out, double *objective, double *distance, double *times, double *mses, int *numA,
+                       int *numAt, int *n_outer, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!y || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: missing required argument");
+    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
+    if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
+    if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
+        return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
+    if (opts->initialization == 33333 && !xw_init) return fail(ctx, SBTV_ERR_INIT, "Initialization = array but xw_init is NULL");
+    if (opts->maxiter < 1) return fail(ctx, SBTV_ERR_MAXITER, "SALSA_wavelet: maxiter must be positive");
+    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    if (!tau || !mu || !xw_out) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: missing required argument");
+    WavPlan wp;
+    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
+    for (int b = 0; b < batch; ++b)
+        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: mu must be > 0");
+    if (((size_t)M * N) & 1)
+        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
+    const size_t P = (size_t)M * N, C = P * wp.bands(), cnt = P * batch, ccnt = C * batch;
+    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "wav.in.true", true_xw, ccnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "wav.in.xinit", xw_init, ccnt, flags, &xi));
+    double *xwo = nullptr, *xo = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "wav.out.xw", xw_out, ccnt, flags, &xwo));
+    if (x_out) SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
+    const int mi = opts->maxiter;
+    for (int b = 0; b < batch; ++b) {
+        const size_t o = (size_t)b * P, oc = (size_t)b * C;
+        SBTV_TRY(wavelet_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, wp, tau[b], mu[b], opts,
+                             td ? td + oc : nullptr, xi ? xi + oc : nullptr, xwo + oc, xo ? xo + o : nullptr,
+                             objective ? objective + (size_t)b * (mi + 1) : nullptr, distance ? distance + (size_t)b * mi : nullptr,
+                             times ? times + (size_t)b * (mi + 1) : nullptr, mses ? mses + (size_t)b * (mi + 1) : nullptr,
+                             numA ? numA + b : nullptr, numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr));
+    }
+    SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
+    if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return canary_epilogue(ctx, 0);
 }

@@ -691,6 +691,21 @@ int fft_cols_fwd_f(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const doub
 bool fft_cols_tv_ok(const FftPlan &pl);
 int fft_cols_inv_f(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale, const int *frozen);
 
+// ----------------------------- redundant wavelet frame (wavelet.hip) ---------
+// one checked transform: image size, filter length K, J = levels - 1 decomposition steps, h0 / sqrt 2 and h1 / sqrt 2
+struct WavPlan {
+    int M, N, K, J;
+    double f0[8], f1[8];
+    int bands() const { return 3 * J + 1; }
+};
+// argument checks of the transforms (host only, before any GPU work); orthonormal: also those of the solver
+int wav_plan(sbtv_ctx *ctx, int M, int N, const double *h, int hlen, int levels, bool orthonormal, WavPlan *pl);
+// z[batch][3J+1][M N] = W' x (mrdwt_TI2D) and x[batch][M N] = W z (mirdwt_TI2D), device pointers, no sync
+int wav_analysis(sbtv_ctx *ctx, const WavPlan &pl, const double *x, double *z, int batch);
+int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, int batch);
+// soft(x, T) = sign(x) max(|x| - T, 0)  (SALSA/soft.m); T = 0 passes x through
+__device__ __forceinline__ double wav_soft(double x, double T) { return copysign(fmax(fabs(x) - T, 0.0), x); }
+
 #include "psf_taps.inc"   // psf_taps_point(): PSF formulas shared by host and device
 
 }  // namespace sbtv

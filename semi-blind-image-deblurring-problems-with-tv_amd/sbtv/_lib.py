@@ -114,6 +114,11 @@ SIGNATURES = {
                            _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_SALSA_masked": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _I]),
+    "sbtv_mrdwt_TI2D": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I]),
+    "sbtv_mirdwt_TI2D": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I]),
+    "sbtv_soft": (_I, [_P, _P, _I, _I, _I, _P, _P, _I]),
+    "sbtv_SALSA_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P, _P,
+                                _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),

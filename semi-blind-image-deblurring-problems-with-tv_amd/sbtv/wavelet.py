@@ -1,0 +1,162 @@
+"""Host mirror of the wavelet-l1 path (SALSA/run_deblur_synthesis_L1.m): the redundant, translation-invariant wavelet frame
+`mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
+with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
+`SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo).  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
+[a_J | LH1 HL1 HH1 | LH2 ...], or (B, M, (3J+1) N) for a batch; host and device arrays as everywhere in this package."""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib as L
+from .admm import _common
+from .tv import _parse_varargin
+
+_WAVELET_OPTIONS = {"MU", "WAVELET", "LEVELS", "AT", "STOPCRITERION", "TOLERANCEA", "MAXITERA", "TRUE_X", "INITIALIZATION",
+                    "VERBOSE", "SPECULATE"}
+
+_vp = L.vptr
+
+
+def daubcqf(N):
+    """Daubechies scaling filter of even length N = 2, 4, 6, 8, minimum phase, sum(h) = sqrt(2) (SALSA/daubcqf.m with 'min').
+    Spectral factorisation: with y = (2 - z - 1/z) / 4 the polynomial P(y) = sum_k C(N/2-1+k, k) y^k has N/2 - 1 roots, each
+    gives a pair (z, 1/z); the minimum-phase filter takes the one inside the unit circle next to the N/2 zeros at z = -1."""
+    N = int(N)
+    if N not in (2, 4, 6, 8):
+        raise ValueError("daubcqf: N must be 2, 4, 6 or 8")
+    p = N // 2
+    h = np.array([1.0])
+    for _ in range(p):
+        h = np.convolve(h, [1.0, 1.0])
+    if p > 1:
+        coef = [math.comb(p - 1 + k, k) for k in range(p)]              # ascending powers of y
+        for yr in np.roots(coef[::-1]):
+            b = 2.0 - 4.0 * yr                                           # z^2 - b z + 1 = 0
+            d = np.sqrt(b * b - 4.0 + 0j)
+            z = (b + d) / 2.0
+            if abs(z) > 1.0:
+                z = (b - d) / 2.0
+            h = np.convolve(h, [1.0, -z])
+        h = np.real(h)
+    return h * (math.sqrt(2.0) / h.sum())
+
+
+def _filter(h):
+    a = np.ascontiguousarray(np.asarray(h, dtype=np.float64).ravel())
+    return a, _vp(a), int(a.size)
+
+
+def _resized(ref: L.Images, N):
+    """An output buffer like `ref` with N columns per image."""
+    r = copy.copy(ref)
+    r.N = int(N)
+    return L.empty_like_images(r)
+
+
+def _bands(levels):
+    return 3 * (int(levels) - 1) + 1
+
+
+def mrdwt_TI2D(x, h, levels, ctx=None):
+    """z = mrdwt_TI2D(x, h, levels): analysis W' of the redundant wavelet frame, (M, N) -> (M, (3 (levels-1) + 1) N)."""
+    ctx = ctx or L.default_context()
+    xi = L.Images(x)
+    ha, hp, K = _filter(h)
+    zo = _resized(xi, xi.N * max(_bands(levels), 1))
+    ctx.check(ctx.lib.sbtv_mrdwt_TI2D(ctx.h, xi.ptr, xi.M, xi.N, xi.B, hp, K, int(levels), zo.ptr, xi.flags), xi.flags)
+    return L.images_result(zo, (x.dim() == 2) if xi.torch else xi.squeeze)
+
+
+def mirdwt_TI2D(z, h, levels, ctx=None):
+    """x = mirdwt_TI2D(z, h, levels): synthesis W, the exact adjoint of mrdwt_TI2D; W W' = I for an orthonormal h."""
+    ctx = ctx or L.default_context()
+    zi = L.Images(z)
+    ha, hp, K = _filter(h)
+    nb = max(_bands(levels), 1)
+    if zi.N % nb:
+        raise ValueError("z must have (3 (levels-1) + 1) N columns")
+    xo = _resized(zi, zi.N // nb)
+    ctx.check(ctx.lib.sbtv_mirdwt_TI2D(ctx.h, zi.ptr, zi.M, zi.N // nb, zi.B, hp, K, int(levels), xo.ptr, zi.flags), zi.flags)
+    return L.images_result(xo, (z.dim() == 2) if zi.torch else zi.squeeze)
+
+
+def soft(x, T, ctx=None):
+    """y = soft(x, T) = sign(x) .* max(abs(x) - T, 0) (SALSA/soft.m); T a scalar or one value per array of a batch."""
+    ctx = ctx or L.default_context()
+    xi = L.Images(x)
+    Ta, Tp = L.dvec(T, xi.B)
+    yo = L.empty_like_images(xi)
+    ctx.check(ctx.lib.sbtv_soft(ctx.h, xi.ptr, xi.M, xi.N, xi.B, Tp, yo.ptr, xi.flags), xi.flags)
+    return L.images_result(yo, (x.dim() == 2) if xi.torch else xi.squeeze)
+
+
+def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
+    """[xw, x, numA, numAt, objective, distance, times, mses] = SALSA_wavelet(y, A, tau, 'MU', mu, 'WAVELET', h, 'LEVELS', L,
+    'AT', A.T, ...)
+
+    minimise 0.5 ||y - A W xw||^2 + tau ||xw||_1 over the coefficients xw of the redundant wavelet frame W (`mirdwt_TI2D`), as
+    SALSA_v2 does in SALSA/run_deblur_synthesis_L1.m:160-180; the iteration is stated in include/sbtv.h (sbtv_SALSA_wavelet).
+    x = W xw is the image estimate.  Options: 'MU' (required), 'WAVELET' (an orthonormal scaling filter, default daubcqf(2)),
+    'LEVELS' (4), 'AT', 'STOPCRITERION', 'TOLERANCEA', 'MAXITERA', 'TRUE_X' (the true COEFFICIENTS, e.g. mrdwt_TI2D(x_true)),
+    'INITIALIZATION' (0, 2 = W' A' y, or a coefficient array), 'VERBOSE', and 'SPECULATE' (sbtv_salsa_opts.speculate: 0 makes the
+    host evaluate the stop rule without the one-iteration lag; the result is the same)."""
+    opts = _parse_varargin(varargin, _WAVELET_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("SALSA_wavelet has no sharded variant")
+    levels = int(opts.get("LEVELS", 4))
+    nb = max(_bands(levels), 1)
+    # the coefficient arguments have (3J+1) N columns: _common compares TRUE_X with y, so they are handled here
+    copts = {k: v for k, v in opts.items() if k not in ("TRUE_X", "INITIALIZATION")}
+    so, yi, _, _ = _common(y, A, copts, ctx, 1)
+    if "MU" not in opts:
+        raise L.SbtvError(-1, "SALSA_wavelet: 'MU' is required")
+    ha, hp, K = _filter(opts.get("WAVELET", daubcqf(2)))
+    B, M, N = yi.B, yi.M, yi.N
+    init = opts.get("INITIALIZATION", 0)
+    xinit = None
+    if np.ndim(init) > 0 or L._is_torch(init):
+        xinit = L.Images(init)
+        so.initialization = 33333
+    else:
+        so.initialization = int(init)
+        if so.initialization not in (0, 2):
+            raise L.SbtvError(-7, "Unknown 'Initialization' option")
+    true = opts.get("TRUE_X", None)
+    ti = L.Images(true) if true is not None else None
+    so.compute_mse = 1 if ti is not None else 0
+    for other in (xinit, ti):
+        if other is not None:
+            if (other.B, other.M, other.N) != (B, M, nb * N):
+                raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+            if other.flags != yi.flags:
+                raise ValueError("all image arguments must live in the same memory space")
+    Kmax = so.maxiter
+    xwo = _resized(yi, nb * N)
+    xo = L.empty_like_images(yi)
+    objective, times, mses = np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1))
+    distance = np.zeros((B, Kmax))
+    numA, numAt, nout = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+    taps = A._cm(B)
+    keep = [L.dvec(v, B) for v in (tau, opts["MU"])]
+    tv, mu = (k[1] for k in keep)
+    ctx.check(ctx.lib.sbtv_SALSA_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, tv, mu, C.byref(so),
+                                         ti.ptr if ti else None, xinit.ptr if xinit else None, xwo.ptr, xo.ptr,
+                                         _vp(objective), _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt,
+                                         nout, yi.flags), yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    xw, x = L.images_result(xwo, sq), L.images_result(xo, sq)
+    n = np.array(nout[:])
+    if sq or B == 1:
+        k = int(n[0])
+        return (xw, x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(),
+                times[0, :k + 1].copy(), mses[0, :k + 1].copy() if ti else np.array([]))
+    return (xw, x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
+            [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
+            [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])

@@ -1,0 +1,213 @@
+"""GPU: the redundant wavelet frame (sbtv_mrdwt_TI2D / sbtv_mirdwt_TI2D, csrc/wavelet.hip), sbtv_soft and the wavelet-l1
+SALSA driver (sbtv_SALSA_wavelet, csrc/admm.hip) against the NumPy restatement (tests/wavelet_restatement.py).
+
+Transforms: atol 1e-12 max|x| (about 2 K J roundings of 1.1e-16 per output: under 1e-14 relative); adjoint and Parseval
+identities on the device's own output to 1e-11 relative.  Solver: the bars of tests/test_gpu_admm.py and test_gpu_masked.py
+against the LITERAL SALSA_v2 iteration: same stopping iteration, objective / mses rtol 1e-9, distance rtol 1e-7,
+max |xw - ref| < 1e-7, max |x - W ref| < 1e-7, numA / numAt equal, times[0] == 0 and non-decreasing."""
+import numpy as np
+import pytest
+
+import wavelet_cases as wc
+import wavelet_restatement as wr
+
+pytestmark = pytest.mark.gpu
+
+# (M, N), filter length, levels, batch
+TRANSFORM_CASES = [
+    ((13, 13), 4, 4, 1),          # reach 12 = size - 1: every tap wraps
+    ((17, 9), 2, 4, 1),           # odd, rectangular
+    ((24, 20), 4, 4, 1),          # rectangular
+    ((64, 64), 8, 3, 1),          # the longest filter
+    ((96, 160), 4, 4, 3),         # tile seams in both dimensions, non-square, a batch
+    ((256, 192), 2, 5, 1),
+    ((512, 512), 2, 4, 1),        # full launch geometry
+    # strides beyond the run caps of csrc/wavelet.hip (16 / 8 / 4 rows, 4 / 2 columns by filter length): the tiles of the
+    # deepest levels are combs of runs along both dimensions, and no size is a multiple of the stride
+    ((96, 160), 2, 7, 1),         # s = 32 > 16
+    ((160, 96), 4, 6, 2),         # s = 16 > 8, reach 48, a batch
+    ((150, 131), 8, 5, 1),        # s = 8 > 4, reach 56, odd sizes
+]
+
+
+@pytest.mark.parametrize("shape,K,levels,batch", TRANSFORM_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_transforms_match_restatement_and_are_a_parseval_frame(ctx, shape, K, levels, batch):
+    import sbtv
+    h = sbtv.daubcqf(K)
+    rng = np.random.default_rng(shape[0] * 7 + K)
+    x = rng.standard_normal((batch,) + shape) * 100.0
+    nb = 3 * (levels - 1) + 1
+    arg = x[0] if batch == 1 else x
+    z = np.asarray(sbtv.mrdwt_TI2D(arg, h, levels, ctx=ctx)).reshape(batch, shape[0], nb * shape[1])
+    zr = np.stack([wr.mrdwt_TI2D(x[b], h, levels) for b in range(batch)])
+    scale = np.max(np.abs(x))
+    ea = np.max(np.abs(z - zr))
+    c = rng.standard_normal(z.shape) * 100.0
+    carg = c[0] if batch == 1 else c
+    wc_ = np.asarray(sbtv.mirdwt_TI2D(carg, h, levels, ctx=ctx)).reshape(batch, *shape)
+    wcr = np.stack([wr.mirdwt_TI2D(c[b], h, levels) for b in range(batch)])
+    es = np.max(np.abs(wc_ - wcr))
+    back = np.asarray(sbtv.mirdwt_TI2D(z[0] if batch == 1 else z, h, levels, ctx=ctx)).reshape(batch, *shape)
+    er = np.max(np.abs(back - x))
+    print(f"{shape} K={K} levels={levels} batch={batch}: analysis {ea / scale:.1e}, synthesis {es / np.max(np.abs(c)):.1e}, "
+          f"W W'x - x {er / scale:.1e} (relative to max|x|)")
+    assert ea <= 1e-12 * scale
+    assert es <= 1e-12 * np.max(np.abs(c))
+    assert er <= 1e-12 * scale
+    for b in range(batch):                                    # on the device's own output
+        lhs, rhs = float(np.vdot(z[b], c[b])), float(np.vdot(x[b], wc_[b]))
+        adj = abs(lhs - rhs) / (np.linalg.norm(z[b]) * np.linalg.norm(c[b]))
+        pars = abs(np.linalg.norm(z[b]) / np.linalg.norm(x[b]) - 1.0)
+        print(f"  image {b}: adjoint {adj:.1e}, Parseval {pars:.1e}")
+        assert adj <= 1e-11 and pars <= 1e-11
+
+
+def test_transforms_take_device_tensors(ctx):
+    import sbtv
+    h = sbtv.daubcqf(4)
+    x = np.random.default_rng(1).standard_normal((2, 48, 40))
+    zd = sbtv.mrdwt_TI2D(sbtv.to_device(x), h, 3, ctx=ctx)
+    zh = sbtv.mrdwt_TI2D(x, h, 3, ctx=ctx)
+    np.testing.assert_array_equal(sbtv.to_host(zd), np.asarray(zh))
+    xd = sbtv.mirdwt_TI2D(zd, h, 3, ctx=ctx)
+    assert np.max(np.abs(sbtv.to_host(xd) - x)) <= 1e-12 * np.max(np.abs(x))
+
+
+def test_soft(ctx):
+    import sbtv
+    rng = np.random.default_rng(2)
+    x = rng.standard_normal((3, 33, 21)) * 3.0
+    x[0, 0, :4] = [0.0, -0.0, 1.5, -1.5]
+    T = np.array([0.0, 1.5, 0.7])
+    got = np.asarray(sbtv.soft(x, T, ctx=ctx))
+    ref = np.stack([wr.soft(x[b], T[b]) for b in range(3)])
+    assert np.all(np.abs(got - ref) <= np.spacing(np.abs(ref)))          # 1 ulp
+    np.testing.assert_array_equal(got[0], x[0])                           # T = 0 passes x through
+    assert np.all(got[1][np.abs(x[1]) <= 1.5] == 0.0)
+    one = np.asarray(sbtv.soft(x[2], 0.7, ctx=ctx))
+    np.testing.assert_array_equal(one, got[2])
+
+
+def _blur(p):
+    import sbtv
+    return sbtv.BlurOperator(sbtv.psf_family("gaussian", 7, p["p_true"])[0])
+
+
+def test_refusals(ctx):
+    """Each is refused with its error code before any launch."""
+    import sbtv
+    x = np.ones((32, 32))
+    d4 = sbtv.daubcqf(4)
+    for h, levels, arr, code in ((np.ones(3), 3, x, -1), (np.ones(10), 2, x, -1), (d4, 1, x, -1),
+                                 (d4, 4, np.ones((12, 12)), -2), (d4, 4, np.ones((40, 12)), -2)):
+        with pytest.raises(sbtv.SbtvError) as e:
+            sbtv.mrdwt_TI2D(arr, h, levels, ctx=ctx)
+        assert e.value.code == code, (h.size, levels, arr.shape, e.value.code)
+        nb = max(3 * (levels - 1) + 1, 1)
+        with pytest.raises(sbtv.SbtvError) as e:
+            sbtv.mirdwt_TI2D(np.ones((arr.shape[0], nb * arr.shape[1])), h, levels, ctx=ctx)
+        assert e.value.code == code
+    sbtv.mrdwt_TI2D(np.ones((13, 13)), d4, 4, ctx=ctx)                    # reach 12 < 13 is accepted
+    sbtv.mrdwt_TI2D(x, np.array([1.0, 0.25]), 3, ctx=ctx)                 # the bare transforms accept any h
+    p = wc.problem("a")
+    op = _blur(p)
+    common = ("AT", op.T, "LEVELS", 4, "MAXITERA", 3)
+    with pytest.raises(sbtv.SbtvError) as e:                              # a filter that is not orthonormal
+        sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", p["mu"], "WAVELET", np.array([1.0, 0.25]), *common, ctx=ctx)
+    assert e.value.code == -1
+    with pytest.raises(sbtv.SbtvError) as e:                              # sum h = sqrt 2 but not of unit norm
+        sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", p["mu"], "WAVELET", np.sqrt(2.0) * np.array([0.75, 0.25]), *common, ctx=ctx)
+    assert e.value.code == -1
+    with pytest.raises(sbtv.SbtvError) as e:
+        sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", 0.0, "WAVELET", p["h"], *common, ctx=ctx)
+    assert e.value.code == -1
+    with pytest.raises(sbtv.SbtvError) as e:                              # an odd pixel count (the solver only: SBTV_ERR_SIZE)
+        sbtv.SALSA_wavelet(np.ones((33, 35)), op, p["tau"], "MU", p["mu"], "WAVELET", p["h"], *common, ctx=ctx)
+    assert e.value.code == -2
+    with pytest.raises(sbtv.SbtvError) as e:                              # the random start of SALSA_v2 is not offered
+        sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", p["mu"], "WAVELET", p["h"], "INITIALIZATION", 1, *common, ctx=ctx)
+    assert e.value.code == -7
+    with pytest.raises(sbtv.SbtvError):                                   # levels far beyond any shift width
+        sbtv.mrdwt_TI2D(x, d4, 80, ctx=ctx)
+
+
+def _solve(ctx, p, **kw):
+    import sbtv
+    op = _blur(p)
+    args = dict(MU=p["mu"], WAVELET=p["h"], LEVELS=p["levels"], AT=op.T, STOPCRITERION=p["stop"], TOLERANCEA=p["tolA"],
+                MAXITERA=p["maxiter"], TRUE_X=p["true_xw"], INITIALIZATION=p["init"], VERBOSE=0)
+    args.update(kw)
+    return sbtv.SALSA_wavelet(p["y"], op, p["tau"], ctx=ctx, **args)
+
+
+def _check(got, ref):
+    xw, x, numA, numAt, objective, distance, times, mses = got
+    print(f"outer iterations {len(objective) - 1} / {ref['n_outer']}, max|xw - ref| = {np.max(np.abs(xw - ref['xw'])):.2e}, "
+          f"max|x - W ref| = {np.max(np.abs(x - ref['x'])):.2e}, objective rel "
+          f"{np.max(np.abs(objective[:2] - ref['objective'][:2]) / ref['objective'][:2]):.2e} (first two)")
+    assert len(objective) == len(ref["objective"]) == ref["n_outer"] + 1, "different stopping iteration"
+    assert (numA, numAt) == (ref["numA"], ref["numAt"])
+    np.testing.assert_allclose(objective, ref["objective"], rtol=1e-9)
+    np.testing.assert_allclose(mses, ref["mses"], rtol=1e-9)
+    assert distance.shape == ref["distance"].shape
+    np.testing.assert_allclose(distance, ref["distance"], rtol=1e-7)
+    assert np.max(np.abs(xw - ref["xw"])) < 1e-7
+    assert np.max(np.abs(x - ref["x"])) < 1e-7
+    assert times[0] == 0 and np.all(np.diff(times) >= 0) and len(times) == len(objective)
+
+
+@pytest.mark.parametrize("name", sorted(wc.SOLVER_CASES))
+def test_solver_matches_the_literal_restatement(ctx, name):
+    """(a) 64 x 64 Haar, stop rule 1 firing inside (2, 60): the rule that the host evaluates one iteration late; (b) 128 x 128
+    D4, rule 2, zero start; (c) 128 x 128 Haar, levels 3, rule 3, a random coefficient start; (d) 100 x 90: the chirp-z FFT
+    path; (e) 1024 x 1024: the pipelined row kernel."""
+    p, ref = wc.problem(name), wc.reference(name)
+    if name == "a":
+        assert 2 < ref["n_outer"] < p["maxiter"], ref["n_outer"]
+    else:
+        assert ref["n_outer"] == p["maxiter"]
+    _check(_solve(ctx, p), ref)
+
+
+def test_solver_without_the_lagged_stop_rule_gives_the_same_result(ctx):
+    p = wc.problem("a")
+    lag, exact = _solve(ctx, p), _solve(ctx, p, SPECULATE=0)
+    for a, b, name in zip(lag, exact, ("xw", "x", "numA", "numAt", "objective", "distance", "times", "mses")):
+        if name != "times":
+            np.testing.assert_array_equal(a, b, err_msg=name)
+    _check(exact, wc.reference("a"))
+
+
+def test_batch_of_two_equals_the_single_calls_bit_for_bit(ctx):
+    import sbtv
+    pa = wc.problem("a")
+    x2 = wc.synth_image(64, 64, 9)
+    st2 = wc.setup(x2, seed=6)
+    op = _blur(pa)
+    y = np.stack([pa["y"], st2["y"]])
+    tau = np.array([pa["tau"], 0.5 * st2["sigma"] ** 2])
+    mu = np.array([pa["mu"], 0.1])
+    tx = np.stack([pa["true_xw"], wr.mrdwt_TI2D(x2, pa["h"], pa["levels"])])
+    args = ("WAVELET", pa["h"], "LEVELS", pa["levels"], "AT", op.T, "STOPCRITERION", 1, "TOLERANCEA", 1e-4, "MAXITERA", 40,
+            "INITIALIZATION", 2)
+    both = sbtv.SALSA_wavelet(y, op, tau, "MU", mu, "TRUE_X", tx, *args, ctx=ctx)
+    for b in range(2):
+        one = sbtv.SALSA_wavelet(y[b], op, tau[b], "MU", mu[b], "TRUE_X", tx[b], *args, ctx=ctx)
+        np.testing.assert_array_equal(both[0][b], one[0])
+        np.testing.assert_array_equal(both[1][b], one[1])
+        assert (both[2][b], both[3][b]) == (one[2], one[3])
+        for q in (4, 5, 7):
+            np.testing.assert_array_equal(both[q][b], one[q])
+
+
+def test_solver_takes_device_tensors(ctx):
+    import sbtv
+    p = wc.problem("d")
+    op = _blur(p)
+    host = _solve(ctx, p)
+    dev = sbtv.SALSA_wavelet(sbtv.to_device(p["y"]), op, p["tau"], "MU", p["mu"], "WAVELET", p["h"], "LEVELS", p["levels"],
+                             "AT", op.T, "STOPCRITERION", p["stop"], "TOLERANCEA", p["tolA"], "MAXITERA", p["maxiter"],
+                             "TRUE_X", sbtv.to_device(p["true_xw"]), "INITIALIZATION", 2, ctx=ctx)
+    np.testing.assert_array_equal(sbtv.to_host(dev[0]), np.asarray(host[0]))
+    np.testing.assert_array_equal(sbtv.to_host(dev[1]), np.asarray(host[1]))
+    np.testing.assert_array_equal(dev[4], host[4])
