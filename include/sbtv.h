@@ -334,6 +334,65 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                        double *objective, double *distance, double *times, double *mses,
                        int *numA, int *numAt, int *n_outer, int flags);
 
+/* ---- empirical-Bayes estimate of theta for the wavelet-l1 prior (SALSA/run_deblur_synthesis_L1.m:125-156) -----------------
+ * The script estimates the regularisation parameter before it solves the MAP problem: a MYULA chain on the wavelet
+ * coefficients drives the log-scale stochastic update of SALSA/SAPG_algorithm_1.m:165-216, and the solve then runs at
+ * tau = theta_EB sigma^2, mu = theta_EB (:167,175).  SAPG_algorithm_1.m as shipped cannot be called by that script: it wants
+ * op.to_init, op.grad_t and a two-argument gradF for a second parameter `tau` that the script never defines (SURVEY.md
+ * section 2.3).  This entry point is its theta part, which is what the script's comments and constants describe.
+ * One chain per image y_b; state X: [3J+1][M*N] coefficients in the layout of sbtv_mrdwt_TI2D, dimX = (3J+1) M N; W =
+ * mirdwt_TI2D, W' = mrdwt_TI2D, B = circular blur of taps[b], soft = SALSA/soft.m (the script's proxG, :137):
+ *     X = xw0 (NULL: W' y, :153) ;  prox = soft(X, lambda theta(1))
+ *     warm-up, ii = 2..warmup, theta fixed at th_init (SAPG_algorithm_1.m:131-141):
+ *         X = X + gamma (prox - X)/lambda - gamma W'B'(B W X - y)/sigma2 + sqrt(2 gamma) Z ;  prox = soft(X, lambda th_init)
+ *         logpi_wu(ii) = -||y - B W X||^2 / (2 sigma2) - th_init ||X||_1                   (logpi_wu(1) = 0)
+ *     logpi(1) = logPi(X, theta(1)) ;  eta(1) = log th_init
+ *     ii = 2..samples (:171-216):
+ *         X = (same step) ;  prox = soft(X, lambda theta(ii-1)) ;  g = ||X||_1
+ *         eta(ii) = clamp(eta(ii-1) + delta(ii) (dimX/theta(ii-1) - g) exp(eta(ii-1)), log min_th, log max_th)
+ *         theta(ii) = exp(eta(ii)) ;  delta(i) = d_scale i^(-d_exp) / dimX                  (:111,180-182)
+ *         gx(ii-1) = g ;  logpi(ii) = -||y - B W X||^2 / (2 sigma2) - theta(ii-1) g        (:190-191; gx(samples) = 0)
+ *         tol_thetas(ii) = |m(ii) - m(ii-1)| / m(ii-1), m(i) = exp(mean(eta(burnIn..i)))    (:199-200; NaN while a window
+ *             is empty, i.e. for 2 <= ii <= burnIn, like MATLAB's mean of an empty range; tol_thetas(1) = 0)
+ *         mean_thetas(ii - burnIn) = m(ii) for ii > burnIn                                  (:209-211)
+ *     theta_eb = exp(mean(eta(burnIn..samples)))                                            (:226)
+ * op.stopTol is computed into tol_thetas but never breaks the loop (the shipped loop has no break either).  The means are
+ * running sums in iteration order.
+ * What runs: the prox is never stored.  One element-wise kernel per iteration recomputes soft(X, lambda theta) from X and the
+ * theta the prox was formed with (theta(ii-2) in iteration ii, theta(1) at ii = 2), takes or draws the normals, reads X and
+ * the gradient once, writes X once and leaves per-workgroup sums of |X|; a one-workgroup-per-chain kernel sums them in a
+ * fixed order, steps eta / theta and writes the traces on the device, so the host enqueues iterations without waiting (one
+ * synchronisation per 1024 iterations and at the end).  ||y - B W X||^2 of sample ii is the Parseval sum of the next
+ * iteration's gradient pass; the last sample costs one extra synthesis + forward transform.  Chains of a batch share every
+ * launch; every reduction is per chain and in a fixed order, so chain b is computed bit for bit as alone.
+ *   noise: NULL (device Philox randn: pair q of chain b's coefficients in step s draws counter (q, s, chain_offset + b), steps
+ *          count from 0 through the warm-up and on, as in sbtv_SAPG_algorithm) or host/device array of
+ *          (max(warmup-1,0) + samples-1) * batch * dimX doubles, step-major, each step [batch][dimX] in the layout of X
+ *   traces (host, may be NULL): thetas, gx, logpi, tol_thetas [batch*samples]; logpi_wu [batch*warmup];
+ *          mean_thetas [batch*(samples-burnIn)];  theta_eb [batch] (required);  xw_last: last sample (may be NULL)
+ *   SBTV_DEVICE_PTRS applies to y / xw0 / noise / xw_last.
+ * Refused before any GPU work: what sbtv_SALSA_wavelet refuses for h / levels / size (non-orthonormal h -> SBTV_ERR_BADARG,
+ * odd pixel count -> SBTV_ERR_SIZE); samples < 2, warmup < 0, burnIn < 1 or > samples, lambda / gamma / sigma2 <= 0, th_init
+ * not within 0 < min_th <= th_init <= max_th, chain_offset < 0 -> SBTV_ERR_BADARG. */
+typedef struct sbtv_sapg_wavelet_opts {
+    int    samples;           /* op.samples                                              */
+    int    warmup;            /* op.warmup; 0 and 1: no warm-up step                     */
+    int    burnIn;            /* op.burnIn (1-based like the reference)                  */
+    double lambda, gamma;     /* op.lambda, op.gamma (run_deblur_synthesis_L1.m:149-150) */
+    double sigma2;            /* noise variance of the likelihood (:141-142)             */
+    double th_init, min_th, max_th;
+    double d_scale, d_exp;    /* delta(i) = d_scale * i^-d_exp / dimX                    */
+    unsigned long long seed;  /* Philox seed when noise == NULL                          */
+    int    chain_offset;      /* chain b draws the Philox stream chain_offset + b        */
+} sbtv_sapg_wavelet_opts;
+int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                      const double *taps, int taille,
+                      const double *h, int hlen, int levels,
+                      const sbtv_sapg_wavelet_opts *op, const double *xw0, const double *noise,
+                      double *thetas, double *gx, double *logpi, double *logpi_wu,
+                      double *mean_thetas, double *tol_thetas, double *theta_eb,
+                      double *xw_last, int flags);
+
 /* ---- a-8: FISTA with the TV prox ----------------------------------------
  * Replaces my_fista(b,A,AT,tau,L,Phi,Psi,stopcriterion,tolerance,maxiters,true,verbose)
  * (SALSA/my_fista.m:5-56) with Psi = cold-start Chambolle(prox_iters) and Phi = TVnorm

@@ -54,6 +54,14 @@ class sbtv_sapg_opts(C.Structure):
                 ("seed", C.c_ulonglong), ("chain_offset", C.c_int), ("iter_offset", C.c_int)]
 
 
+class sbtv_sapg_wavelet_opts(C.Structure):
+    _fields_ = [("samples", C.c_int), ("warmup", C.c_int), ("burnIn", C.c_int),
+                ("lambda_", C.c_double), ("gamma", C.c_double), ("sigma2", C.c_double),
+                ("th_init", C.c_double), ("min_th", C.c_double), ("max_th", C.c_double),
+                ("d_scale", C.c_double), ("d_exp", C.c_double),
+                ("seed", C.c_ulonglong), ("chain_offset", C.c_int)]
+
+
 class sbtv_moments_opts(C.Structure):
     _fields_ = [("first", C.c_int), ("thin", C.c_int), ("pooled", C.c_int)]
 
@@ -119,6 +127,8 @@ SIGNATURES = {
     "sbtv_soft": (_I, [_P, _P, _I, _I, _I, _P, _P, _I]),
     "sbtv_SALSA_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P, _P,
                                 _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sbtv_SAPG_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_opts), _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _I]),
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),

@@ -1,7 +1,8 @@
 """Host mirror of the wavelet-l1 path (SALSA/run_deblur_synthesis_L1.m): the redundant, translation-invariant wavelet frame
 `mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
 with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
-`SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo).  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
+`SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), and `SAPG_wavelet`, the empirical-Bayes estimate of the
+regularisation parameter that the script runs first (the theta part of SALSA/SAPG_algorithm_1.m).  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
 [a_J | LH1 HL1 HH1 | LH2 ...], or (B, M, (3J+1) N) for a batch; host and device arrays as everywhere in this package."""
 from __future__ import annotations
 
@@ -160,3 +161,104 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
     return (xw, x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
             [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
             [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
+
+
+def _op(op, name, default=None):
+    v = op.get(name, default) if isinstance(op, dict) else getattr(op, name, default)
+    if v is None:
+        raise KeyError(f"SAPG_wavelet: op.{name} is required")
+    return v
+
+
+def SAPG_wavelet(y, A, h, levels, op, noise=None, xw0=None, ctx=None):
+    """[theta_EB, results] = SAPG_wavelet(y, A, h, levels, op)
+
+    Empirical-Bayes estimate of theta in p(xw | theta) ~ exp(-theta ||xw||_1) from y = A W xw + noise, as
+    SALSA/run_deblur_synthesis_L1.m:125-156 obtains it before the MAP solve (then SALSA_wavelet at tau = theta_EB sigma^2,
+    mu = theta_EB): a MYULA chain on the wavelet coefficients and the log-scale update of SALSA/SAPG_algorithm_1.m:165-216, theta
+    part only (its `tau` part cannot be called by the script; include/sbtv.h, sbtv_SAPG_wavelet, states the loop).
+    A: the blur (sbtv.BlurOperator); h, levels: the frame, as for mrdwt_TI2D.
+    op (dict or object): samples, burnIn, th_init, min_th, max_th, d_scale, d_exp, lambda, gamma, sigma (the noise standard
+    deviation, op.sigma of the script) or sigma2; optional warmup (0, as the script sets it), X0 (start coefficients, default
+    W'y), seed (1), chain_offset (0).
+    noise: optional (steps, [B,] M, (3J+1) N) normals instead of the device Philox stream, steps = max(warmup-1, 0) +
+    samples-1; host array or a device tensor already in the library's layout (step-major, column-major coefficient arrays).
+    xw0 overrides op.X0.  y may be a batch (B, M, N): one chain per image, theta_EB is then an array and results a list.
+    results keys (SAPG_algorithm_1.m:219-231): last_samp, logPiTraceX, gXTrace, mean_theta, last_theta, thetas, mean_thetas,
+    tol_thetas, options, logPiTrace_WU (when warmup > 0), and Xlast_sample."""
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("SAPG_wavelet has no sharded variant")
+    yi = L.Images(y)
+    B, M, N = yi.B, yi.M, yi.N
+    nb = max(_bands(levels), 1)
+    ha, hp, K = _filter(h)
+    o = L.sbtv_sapg_wavelet_opts()
+    o.samples = int(_op(op, "samples"))
+    o.warmup = int(_op(op, "warmup", 0))
+    o.burnIn = int(_op(op, "burnIn"))
+    o.lambda_ = float(_op(op, "lambda"))
+    o.gamma = float(_op(op, "gamma"))
+    s2 = op.get("sigma2") if isinstance(op, dict) else getattr(op, "sigma2", None)
+    o.sigma2 = float(s2) if s2 is not None else float(_op(op, "sigma")) ** 2
+    o.th_init = float(_op(op, "th_init"))
+    o.min_th = float(_op(op, "min_th"))
+    o.max_th = float(_op(op, "max_th"))
+    o.d_scale = float(_op(op, "d_scale"))
+    o.d_exp = float(_op(op, "d_exp"))
+    o.seed = int(_op(op, "seed", 1))
+    o.chain_offset = int(_op(op, "chain_offset", 0))
+    S, Wn = o.samples, max(o.warmup, 0)
+    if xw0 is None:
+        xw0 = op.get("X0") if isinstance(op, dict) else getattr(op, "X0", None)
+    x0i = L.Images(xw0) if xw0 is not None else None
+    if x0i is not None:
+        if (x0i.B, x0i.M, x0i.N) != (B, M, nb * N):
+            raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+        if x0i.flags != yi.flags:
+            raise ValueError("all image arguments must live in the same memory space")
+    nz_ptr, nz_keep = None, None
+    if noise is not None:
+        if L._is_torch(noise):
+            if yi.flags != L.SBTV_DEVICE_PTRS:
+                raise ValueError("all image arguments must live in the same memory space")
+            # the step kernel reads steps * B * dimX doubles from this pointer: anything else is an out-of-bounds read
+            want = (max(Wn - 1, 0) + S - 1) * B * M * nb * N
+            # (dense: its elements fill one gap-free span of memory, as a contiguous tensor or a `to_device` view does)
+            span = 1 + sum((n - 1) * st for n, st in zip(noise.shape, noise.stride())) if noise.numel() else 0
+            if str(noise.dtype) != "torch.float64" or noise.numel() != want or span != want or any(st < 1 for st in noise.stride()):
+                raise ValueError("a device noise tensor must be dense float64 with (max(warmup-1, 0) + samples-1) * B * "
+                                 f"M * (3 (levels-1) + 1) N = {want} elements, in the library's layout")
+            nz_keep, nz_ptr = noise, C.c_void_p(noise.data_ptr())
+        else:
+            if yi.flags != L.SBTV_HOST_PTRS:
+                raise ValueError("all image arguments must live in the same memory space")
+            a = np.asarray(noise, dtype=np.float64)
+            if a.ndim == 3:
+                a = a[:, None]
+            if a.shape != (max(Wn - 1, 0) + S - 1, B, M, nb * N):
+                raise ValueError("noise must be (max(warmup-1, 0) + samples-1, [B,] M, (3 (levels-1) + 1) N)")
+            nz_keep = L.column_major_images(a.reshape((-1,) + a.shape[2:]))
+            nz_ptr = _vp(nz_keep)
+    thetas, gx, logpi, tol = (np.zeros((B, max(S, 1))) for _ in range(4))
+    logpi_wu = np.zeros((B, max(Wn, 1)))
+    means = np.zeros((B, max(S - o.burnIn, 1)))
+    eb = np.zeros(B)
+    xl = _resized(yi, nb * N)
+    taps = A._cm(B)
+    ctx.check(ctx.lib.sbtv_SAPG_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, int(levels), C.byref(o),
+                                        x0i.ptr if x0i else None, nz_ptr, _vp(thetas), _vp(gx), _vp(logpi), _vp(logpi_wu),
+                                        _vp(means), _vp(tol), _vp(eb), xl.ptr, yi.flags), yi.flags)
+    xs = L.images_result(xl, False)
+    results = []
+    for b in range(B):
+        r = dict(last_samp=S, logPiTraceX=logpi[b], gXTrace=gx[b], mean_theta=float(eb[b]), last_theta=float(thetas[b, -1]),
+                 thetas=thetas[b], mean_thetas=means[b, :max(S - o.burnIn, 0)], tol_thetas=tol[b], options=op,
+                 Xlast_sample=xs[b])
+        if Wn > 0:
+            r["logPiTrace_WU"] = logpi_wu[b, :Wn]
+        results.append(r)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    if sq:
+        return float(eb[0]), results[0]
+    return eb, results

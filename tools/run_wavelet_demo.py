@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""SALSA/run_deblur_synthesis_L1.m end to end on the MI355X through the host mirror: 9 x 9 uniform blur at BSNR 30 ->
+empirical-Bayes estimate of theta for the Laplace prior on the coefficients of the redundant 4-level Haar frame
+(`sbtv.SAPG_wavelet`, :125-156) -> MAP image by `sbtv.SALSA_wavelet` at tau = theta_EB sigma^2, mu = theta_EB (:160-185).
+
+  python tools/run_wavelet_demo.py [--image tests/golden/man_512.npy] [--samples 3000] [--seed 1]
+
+Constants follow the script (:65-83,99,106-107,164-166).  The reference's uniform_blur is centred; the library's taps sit in
+the top-left corner (utils/resize.m), which delays the blurred image by 4 pixels in both directions.  The observation is made
+with the centred blur, as the script makes it, the solver is given the 9 x 9 taps, so its estimate is the image advanced by 4
+pixels: it is rolled back before the MSE.  A non-negative mask of unit sum has spectral norm 1 (|H| <= H(0) = 1), which is
+what the script's power iteration (:101) returns.  MATLAB's randn('state',1) stream cannot be reproduced: noise comes from
+NumPy (observation) and the device Philox generator (MYULA)."""
+import argparse
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "semi-blind-image-deblurring-problems-with-tv_amd"))
+import numpy as np
+import sbtv
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--image", default=os.path.join(ROOT, "tests", "golden", "man_512.npy"))
+    ap.add_argument("--samples", type=int, default=3000)                 # op.samples (:65)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    x = np.load(a.image).astype(np.float64)
+    dimX = x.size
+    rng = np.random.default_rng(a.seed)
+    ctx = sbtv.default_context(0)
+    blur_length, levels, bsnr = 9, 4, 30.0                               # :99,107,88
+    h = sbtv.daubcqf(2)                                                  # :106
+    taps = np.full((blur_length, blur_length), 1.0 / blur_length ** 2)
+    c = blur_length // 2
+    pad = np.zeros(x.shape)
+    pad[:blur_length, :blur_length] = taps
+    Hc = np.fft.fft2(np.roll(pad, (-c, -c), axis=(0, 1)))                # the centred blur of uniform_blur.m
+    Bx = np.real(np.fft.ifft2(Hc * np.fft.fft2(x)))                      # :120
+    sigma = np.linalg.norm(Bx - Bx.mean()) / math.sqrt(dimX * 10 ** (bsnr / 10))     # :121
+    y = Bx + sigma * rng.standard_normal(x.shape)                        # :123
+    evMax = 1.0
+    Lf = (evMax / sigma) ** 2                                            # :143
+    lam = min(5.0 / Lf, 2.0)                                             # :80-81,149
+    op = {"samples": a.samples, "burnIn": min(20, a.samples), "th_init": 0.01, "min_th": 1e-3, "max_th": 1.0, "d_exp": 0.8,
+          "d_scale": 0.1 / 0.01, "warmup": 0, "lambda": lam, "gamma": 0.98 / (Lf + 1.0 / lam), "sigma": sigma,
+          "seed": a.seed}                                                # :65-83,150
+    A = sbtv.BlurOperator(taps, ctx=ctx)
+    print(f"image {x.shape}, sigma {sigma:.4f}, lambda {lam:.4g}, gamma {op['gamma']:.4g}, {a.samples} samples")
+    t0 = time.perf_counter()
+    theta_EB, res = sbtv.SAPG_wavelet(y, A, h, levels, op, ctx=ctx)      # :153-156
+    t_eb = time.perf_counter() - t0
+    print(f"theta_EB {theta_EB:.6g} (last theta {res['last_theta']:.6g}, last relative change of the mean "
+          f"{res['tol_thetas'][-1]:.2e}) in {t_eb:.2f} s")
+    WTx = sbtv.mrdwt_TI2D(np.roll(x, (-c, -c), axis=(0, 1)), h, levels, ctx=ctx)    # the true coefficients of what is estimated
+    t0 = time.perf_counter()
+    out = sbtv.SALSA_wavelet(y, A, theta_EB * sigma ** 2, "MU", theta_EB, "WAVELET", h, "LEVELS", levels, "AT", A.T,
+                             "TRUE_X", WTx, "TOLERANCEA", 1e-4, "MAXITERA", 500, "VERBOSE", 0, ctx=ctx)    # :164-182
+    t_map = time.perf_counter() - t0
+    xMAP = np.roll(np.asarray(out[1]), (c, c), axis=(0, 1))              # :184, rolled back by 4 pixels
+    mse = 10 * math.log10(np.linalg.norm(x - xMAP) ** 2 / dimX)          # :185
+    print(f"SALSA_wavelet: {len(out[4]) - 1} outer iterations in {t_map:.2f} s, MSE {mse:.2f} dB "
+          f"(observation: {10 * math.log10(np.linalg.norm(x - y) ** 2 / dimX):.2f} dB)")
+    print(f"wall time {t_eb + t_map:.2f} s")
+
+
+if __name__ == "__main__":
+    main()
