@@ -526,6 +526,66 @@ int sbtv_myula_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
                        double *x_out, const sbtv_moments_opts *mo, double *post_mean, double *post_var,
                        long long *post_count, int flags);
 
+/* ---- wavelet-l1 posterior at a fixed theta: MYULA on the frame coefficients, MMSE image and pixel variance ---------------
+ * No entry of the reference.  It is the warm-up loop of SALSA/SAPG_algorithm_1.m:131-141 with the closures of
+ * SALSA/run_deblur_synthesis_L1.m:135-146 (proxG = soft, g = l1, gradF = W'B'(B W xw - y)/sigma2), run at the caller's theta:
+ * what follows sbtv_SAPG_wavelet once theta_EB is known (that entry returns only its last sample, and its theta moves).
+ * One chain per image y_b with its own theta[b] and sigma2[b] (host arrays: a batch may sweep theta, or give every image its
+ * theta_EB and noise level); state X, W, W', B, soft and dimX as for sbtv_SAPG_wavelet:
+ *     X(1) = xw0 (NULL: W' y)
+ *     ii = 2..samples:
+ *         G     = W'B'(B W X(ii-1) - y)
+ *         X(ii) = ((X + gamma (soft(X, lambda theta_b) - X)/lambda) - gamma (G/sigma2_b)) + sqrt(2 gamma) Z,   X = X(ii-1)
+ *     ii = 1..samples (no off-by-one):
+ *         gx(ii)    = ||X(ii)||_1
+ *         logpi(ii) = -||y - B W X(ii)||^2 / (2 sigma2_b) - theta_b gx(ii)
+ * The step is the expression of sbtv_SAPG_wavelet's step, one shared device function: a warm-up of that entry at
+ * th_init = theta gives the same bits.
+ * What runs: one iteration is that of sbtv_SAPG_wavelet without its parameter update.  ||y - B W X(ii)||^2 is the Parseval
+ * sum of iteration ii+1's gradient pass; the last sample costs one extra synthesis + forward transform.  Nothing is
+ * reduced per iteration: the partial sums of up to 1024 iterations wait in a ring, and one launch turns them into trace
+ * entries on the device, one workgroup per chain and iteration, every sum in a fixed order.  The host enqueues without
+ * waiting: one synchronisation per 1024 iterations and one at the end.  Chains of a batch share every launch; chain b is
+ * computed bit for bit as alone.  The call counter advances as in sbtv_SAPG_wavelet.  No lanes, no graph capture and no
+ * sharded variant.
+ *   noise: NULL (device Philox randn with the counters of sbtv_SAPG_wavelet: pair q of chain b in step s draws
+ *          (q, s, chain_offset + b), s = ii - 2) or host/device array of (samples-1) * batch * dimX doubles, step-major, each
+ *          step [batch][dimX] in the layout of X
+ *   gx, logpi: [batch*samples], host, may be NULL;  xw_last: the last sample, may be NULL
+ * Moments (mo != NULL), of the iterations 1..samples: selection (first = 0 means 1, thin >= 1; first, first + thin, ...),
+ * outputs (var = M2/(n-1), zeros for n = 1; post_count = n, host) and pooled = 1 (Chan's combination in chain order; only
+ * for chains with the same y, taps, theta and sigma2) as for sbtv_myula_moments.
+ *   post_mean / post_var: IMAGE domain, [batch or 1][M*N]: mean and variance of W X(ii), the MMSE image and its pixel
+ *          variance.  The image of sample ii exists inside the level-1 synthesis launch of iteration ii+1 (of the final
+ *          residual pass for ii = samples); that launch accumulates it in Welford form on the value it stores: 32 B per
+ *          pixel and selected iteration, no extra launch, no re-read.
+ *   coef_mean / coef_var: COEFFICIENT domain, [batch or 1][dimX]: E[xw | y] and the marginal variance per coefficient,
+ *          accumulated by the step kernel on X(ii) in registers: 32 B per coefficient and selected iteration.
+ *   At least one of post_mean, coef_mean; post_var needs post_mean, coef_var needs coef_mean.  Unselected iterations
+ *   launch the plain kernels, and no bit of the chain or its traces depends on what is accumulated.
+ *   SBTV_DEVICE_PTRS applies to y / xw0 / noise / xw_last / post_mean / post_var / coef_mean / coef_var.
+ * Refused before any GPU work: what sbtv_SAPG_wavelet refuses for taps / h / levels / size, with its codes; with
+ * SBTV_ERR_BADARG: samples < 2, lambda or gamma <= 0, any theta[b] or sigma2[b] <= 0, non-finite values, chain_offset < 0,
+ * theta == NULL, sigma2 == NULL, thin < 1, first < 0, first > samples, a moment output without what it needs (above), a
+ * moment output with mo == NULL, pooled = 1 on chains of different posteriors. */
+typedef struct sbtv_myula_wavelet_opts {
+    int    samples;            /* >= 2: iteration 1 is the start state, samples-1 MYULA steps follow */
+    double lambda, gamma;      /* as sbtv_sapg_wavelet_opts                                          */
+    unsigned long long seed;   /* Philox seed when noise == NULL                                     */
+    int    chain_offset;       /* chain b draws the Philox stream chain_offset + b                   */
+} sbtv_myula_wavelet_opts;
+int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                       const double *taps, int taille, const double *h, int hlen, int levels,
+                       const sbtv_myula_wavelet_opts *op,
+                       const double *theta, const double *sigma2,
+                       const double *xw0, const double *noise,
+                       double *gx, double *logpi,
+                       double *xw_last,
+                       const sbtv_moments_opts *mo,
+                       double *post_mean, double *post_var, long long *post_count,
+                       double *coef_mean, double *coef_var,
+                       int flags);
+
 /* ---- a-9: largest eigenvalue of A'A by power iteration --------------------
  * Replaces max_eigenval(A,At,params,im_size,tol,max_iter,verbose)
  * (utils/max_eigenval_Gaussian_Moffat.m:1-27, max_eigenval_Laplace.m:1-28).

@@ -267,12 +267,6 @@ using namespace sbtv;
 // a-6: plain MYULA chain at fixed parameters (SALSA/myula.m:1-22)
 // ---------------------------------------------------------------------------
 namespace sbtv {
-// iterations of the accumulator: first, first + thin, ... <= last; 0 when iteration ii is not one of them
-static inline int mom_sample_of(const MomReq *mr, int ii) {
-    if (!mr || ii < mr->first || (ii - mr->first) % mr->thin != 0) return 0;
-    return (ii - mr->first) / mr->thin + 1;
-}
-static inline long long mom_count(const MomReq &mr, int last) { return (last - mr.first) / mr.thin + 1; }
 // sbtv_moments_opts -> MomReq: checks first / thin (first = 0 -> first0) against the last iteration `last`
 static int mom_resolve(sbtv_ctx *ctx, const char *who, const sbtv_moments_opts *mo, int first0, int last, double *post_mean,
                        double *post_var, long long *post_count, int flags, MomReq *out) {

@@ -320,6 +320,12 @@ struct MomReq {
     bool dev;
     bool raw;                   // var receives M2 per chain (a lane of a pooled call: the parent pools)
 };
+// iterations of the accumulator: first, first + thin, ... <= last; 0 when iteration ii is not one of them
+inline int mom_sample_of(const MomReq *mr, int ii) {
+    if (!mr || ii < mr->first || (ii - mr->first) % mr->thin != 0) return 0;
+    return (ii - mr->first) / mr->thin + 1;
+}
+inline long long mom_count(const MomReq &mr, int last) { return (last - mr.first) / mr.thin + 1; }
 // iteration 1 (the start state) as sample 1: mean = X, m2 = 0
 int moments_seed(sbtv_ctx *ctx, const double *X, double *mean, double *m2, size_t P, int batch);
 // mean / m2 of `batch` chains of n samples each -> req's outputs: per chain (var = m2 / (n-1), 0 for n = 1), or pooled over
@@ -703,8 +709,41 @@ int wav_plan(sbtv_ctx *ctx, int M, int N, const double *h, int hlen, int levels,
 // z[batch][3J+1][M N] = W' x (mrdwt_TI2D) and x[batch][M N] = W z (mirdwt_TI2D), device pointers, no sync
 int wav_analysis(sbtv_ctx *ctx, const WavPlan &pl, const double *x, double *z, int batch);
 int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, int batch);
+// the same synthesis; mom non-null with k > 0: every pixel of x is also sample k of the running mean / M2 mom->mean /
+// mom->m2 [batch][M N], accumulated by the level-1 launch on the value it stores (wav_synthesis_moments_kernel).  x holds
+// the same bits either way.
+int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, int batch, const MomArgs *mom);
 // soft(x, T) = sign(x) max(|x| - T, 0)  (SALSA/soft.m); T = 0 passes x through
 __device__ __forceinline__ double wav_soft(double x, double T) { return copysign(fmax(fabs(x) - T, 0.0), x); }
+// one coefficient of the MYULA step on the frame coefficients (SAPG_algorithm_1.m:133,174 with proxG = soft):
+//     x + gam (soft(x, T) - x) / lamb - gam g / s2 + sqrt(2 gam) z,   T = lamb theta
+// ONE definition for the step kernel of sbtv_SAPG_wavelet and those of sbtv_myula_wavelet, no contraction anywhere in it
+__device__ __forceinline__ double wav_myula_nocontract(double x, double g, double z, double T, double gam, double lamb,
+                                                       double s2, double sq2g) {
+#pragma clang fp contract(off)
+    return ((x + gam * (wav_soft(x, T) - x) / lamb) - gam * (g / s2)) + sq2g * z;
+}
+// the element-wise passes over the coefficients (wavelet_sapg.hip, wavelet_myula.hip): WAV_EWB lanes per workgroup, at
+// most WAV_EW_MAXBLK workgroups (= partial sums) per chain, a grid-stride loop beyond
+constexpr int WAV_EWB = 256;
+constexpr int WAV_EW_MAXBLK = 2048;
+inline int wav_ew_blocks(size_t dimX) {
+    const size_t nb = (dimX / 2 + WAV_EWB - 1) / WAV_EWB;
+    return nb > (size_t)WAV_EW_MAXBLK ? WAV_EW_MAXBLK : (nb < 1 ? 1 : (int)nb);
+}
+__device__ __forceinline__ double wav_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// sum over a workgroup of WAV_EWB lanes in a fixed order (lanes, then the four waves); every lane returns the total
+__device__ __forceinline__ double wav_block_sum(double v, double *red) {
+    v = wav_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
 
 #include "psf_taps.inc"   // psf_taps_point(): PSF formulas shared by host and device
 

@@ -123,11 +123,13 @@ __global__ __launch_bounds__(WNW * 64) void wav_analysis_kernel(const double *__
 }
 
 // ---- synthesis: a_j (ll), lh, hl, hh -> a_{j-1} (transposed filters: index i - s k) -------------------------------
-template <int K>
-__global__ __launch_bounds__(WNW * 64) void wav_synthesis_kernel(const double *__restrict__ ll, const double *__restrict__ lh,
-                                                                  const double *__restrict__ hl, const double *__restrict__ hh,
-                                                                  size_t ll_img, double *__restrict__ out, WavTaps tp,
-                                                                  WavGeom g) {
+// ONE body for the plain kernel and for the one that also accumulates the posterior moments of the image it stores (MOM,
+// level 1 only: sample k of mom.mean / mom.m2 [batch][M N]), so both store the same bits
+template <int K, bool MOM>
+__device__ __forceinline__ void wav_synthesis_body(const double *__restrict__ ll, const double *__restrict__ lh,
+                                                   const double *__restrict__ hl, const double *__restrict__ hh,
+                                                   size_t ll_img, double *__restrict__ out, const WavTaps &tp,
+                                                   const WavGeom &g, const MomArgs &mom) {
     constexpr int L1 = WT1 + wav_cap1(K) * (K - 1), L2 = WS_T2 + wav_cap2(K) * (K - 1);
     __shared__ double ta[L2 * L1], tb[L2 * L1];
     __shared__ double lo[WS_T2 * L1], hi[WS_T2 * L1];
@@ -165,6 +167,7 @@ __global__ __launch_bounds__(WNW * 64) void wav_synthesis_kernel(const double *_
     }
     __syncthreads();
     const int gr = wav_index(lane, b1, g.lq1, g.ls, 0);
+    const double rk = 1.0 / (double)(MOM && mom.k > 0 ? mom.k : 1);
     for (int c = w; c < WS_T2; c += WNW) {                             // dimension 1
         const int gc = wav_index(c, b2, g.lq2, g.ls, 0);
         double v = 0.0;
@@ -173,8 +176,41 @@ __global__ __launch_bounds__(WNW * 64) void wav_synthesis_kernel(const double *_
             const int rr = lane + (K - 1 - k) * q1;
             v += tp.f0[k] * lo[c * L1 + rr] + tp.f1[k] * hi[c * L1 + rr];
         }
-        if (gr < g.M && gc < g.N) out[(size_t)blockIdx.z * g.img_out + (size_t)gc * g.M + gr] = v;
+        if (gr < g.M && gc < g.N) {
+            out[(size_t)blockIdx.z * g.img_out + (size_t)gc * g.M + gr] = v;
+            if (MOM) {
+                const size_t o = ((size_t)blockIdx.z * g.N + gc) * g.M + gr;
+                double mu = 0.0, s = 0.0;
+                if (mom.k > 1) {
+                    mu = mom.mean[o];
+                    s = mom.m2[o];
+                }
+                welford_nocontract(mu, s, v, mom.k, rk);
+                mom.mean[o] = mu;
+                mom.m2[o] = s;
+            }
+        }
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(WNW * 64) void wav_synthesis_kernel(const double *__restrict__ ll, const double *__restrict__ lh,
+                                                                  const double *__restrict__ hl, const double *__restrict__ hh,
+                                                                  size_t ll_img, double *__restrict__ out, WavTaps tp,
+                                                                  WavGeom g) {
+    wav_synthesis_body<K, false>(ll, lh, hl, hh, ll_img, out, tp, g, MomArgs{});
+}
+
+// level-1 synthesis with a Welford epilogue: the pixel about to be stored is sample mom.k >= 1 of the running mean / M2
+// (k = 1 starts them without reading): 32 B per pixel on top of the plain kernel, no extra launch, no re-read of the image
+template <int K>
+__global__ __launch_bounds__(WNW * 64) void wav_synthesis_moments_kernel(const double *__restrict__ ll,
+                                                                          const double *__restrict__ lh,
+                                                                          const double *__restrict__ hl,
+                                                                          const double *__restrict__ hh, size_t ll_img,
+                                                                          double *__restrict__ out, WavTaps tp, WavGeom g,
+                                                                          MomArgs mom) {
+    wav_synthesis_body<K, true>(ll, lh, hl, hh, ll_img, out, tp, g, mom);
 }
 
 // ---- soft threshold, one T per image ------------------------------------------------------------------------------
@@ -228,7 +264,7 @@ int wav_level_analysis(sbtv_ctx *ctx, const WavPlan &pl, int level, const double
 
 template <int K>
 int wav_level_synthesis(sbtv_ctx *ctx, const WavPlan &pl, int level, const double *ll, size_t ll_img, const double *det,
-                        double *out, size_t out_img, int batch) {
+                        double *out, size_t out_img, int batch, const MomArgs *mom) {
     WavGeom g = wav_geom(pl, level);
     const size_t P = (size_t)pl.M * pl.N;
     g.img_in = (size_t)pl.bands() * P;
@@ -239,8 +275,12 @@ int wav_level_synthesis(sbtv_ctx *ctx, const WavPlan &pl, int level, const doubl
         tp.f1[k] = pl.f1[k];
     }
     const dim3 grid(wav_tiles(pl.M, g.ls, g.lq1, g.nr1, WT1), wav_tiles(pl.N, g.ls, g.lq2, g.nr2, WS_T2), (unsigned)batch);
-    hipLaunchKernelGGL(wav_synthesis_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, ll, det, det + P, det + 2 * P, ll_img, out,
-                       tp, g);
+    if (mom)
+        hipLaunchKernelGGL(wav_synthesis_moments_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, ll, det, det + P, det + 2 * P,
+                           ll_img, out, tp, g, *mom);
+    else
+        hipLaunchKernelGGL(wav_synthesis_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, ll, det, det + P, det + 2 * P, ll_img,
+                           out, tp, g);
     return 0;
 }
 
@@ -308,6 +348,13 @@ int wav_analysis(sbtv_ctx *ctx, const WavPlan &pl, const double *x, double *z, i
 
 // x[batch][M N] <- W z[batch][3J+1][M N] (device pointers)
 int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, int batch) {
+    return wav_synthesis(ctx, pl, z, x, batch, nullptr);
+}
+
+// ... and, with mom (k > 0), the image as sample k of the moments: the level-1 launch (the one that stores x) accumulates
+int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, int batch, const MomArgs *mom) {
+    if (mom && (mom->k < 1 || !mom->mean || !mom->m2))
+        return fail(ctx, SBTV_ERR_BADARG, "wav_synthesis: moments without a sample number or accumulators");
     const size_t P = (size_t)pl.M * pl.N, zi = (size_t)pl.bands() * P;
     double *tmp[2] = {nullptr, nullptr};
     if (pl.J > 1) SBTV_TRY(ws_get_t(ctx, "wav.tmp", P * batch, &tmp[0]));
@@ -318,10 +365,10 @@ int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, 
         double *out = (j == 1) ? x : tmp[j & 1];
         const double *det = z + (size_t)(1 + 3 * (j - 1)) * P;
         switch (pl.K) {
-            case 2: SBTV_TRY(wav_level_synthesis<2>(ctx, pl, j, ll, ll_img, det, out, P, batch)); break;
-            case 4: SBTV_TRY(wav_level_synthesis<4>(ctx, pl, j, ll, ll_img, det, out, P, batch)); break;
-            case 6: SBTV_TRY(wav_level_synthesis<6>(ctx, pl, j, ll, ll_img, det, out, P, batch)); break;
-            default: SBTV_TRY(wav_level_synthesis<8>(ctx, pl, j, ll, ll_img, det, out, P, batch)); break;
+            case 2: SBTV_TRY(wav_level_synthesis<2>(ctx, pl, j, ll, ll_img, det, out, P, batch, j == 1 ? mom : nullptr)); break;
+            case 4: SBTV_TRY(wav_level_synthesis<4>(ctx, pl, j, ll, ll_img, det, out, P, batch, j == 1 ? mom : nullptr)); break;
+            case 6: SBTV_TRY(wav_level_synthesis<6>(ctx, pl, j, ll, ll_img, det, out, P, batch, j == 1 ? mom : nullptr)); break;
+            default: SBTV_TRY(wav_level_synthesis<8>(ctx, pl, j, ll, ll_img, det, out, P, batch, j == 1 ? mom : nullptr)); break;
         }
         ll = out;
         ll_img = P;

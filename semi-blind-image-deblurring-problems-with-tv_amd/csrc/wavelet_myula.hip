@@ -1,0 +1,362 @@
+// MYULA chain on the coefficients of the redundant wavelet frame at a FIXED theta, with the posterior mean / variance of its
+// samples in the image and in the coefficient domain.  No entry of the reference: it is the warm-up loop of
+// SALSA/SAPG_algorithm_1.m:131-141 with the closures of SALSA/run_deblur_synthesis_L1.m:135-146 (proxG = soft, g = l1,
+// gradF = W' B'(B W xw - y) / sigma2), run at the caller's theta - what a user does with the theta_EB of sbtv_SAPG_wavelet.
+//
+// One iteration is that of wavelet_sapg.hip without the parameter update: J synthesis launches, the FFT triple with OP_GRADF
+// (its Parseval sum is ||B W X - y||^2 of the state BEFORE the step), J analysis launches and one step kernel (the
+// element-wise update of wav_myula_nocontract and the partial sums of |X_new|).  Nothing is reduced per iteration: the row
+// pass and the step kernel leave their partial sums in a ring of up to WM_RING slots, and wav_myula_trace_kernel turns a full
+// ring into gx / logpi entries in one launch, one workgroup per chain and iteration, every sum in a fixed order.
+//
+// Moments.  The image W X(ii) exists only inside the level-1 synthesis launch of iteration ii + 1 (or of the final residual
+// pass): wav_synthesis_moments_kernel (wavelet.hip) accumulates it there, on the value it is about to store.  The
+// coefficients X(ii) are in registers of the step kernel: wav_myula_moments_kernel accumulates them with moments_pair.
+// Unselected iterations launch the plain kernels; the chain's bits do not depend on what is accumulated.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "sbtv_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace sbtv {
+
+namespace {
+
+constexpr int WMB = WAV_EWB;      // lanes per workgroup of the kernels below
+constexpr int WM_RING = 1024;     // iterations between two trace launches (and two synchronisations)
+
+struct WavMyulaDev {
+    const double *par;           // [2][batch]: theta | sigma2
+    const double *part;          // ring [slot][batch][nblk]: partial sums of |X| after the slot's step
+    const double *acc;           // ring [slot][batch][3][nrb]: accumulators of the slot's row pass, q = 0: ||B W X - y||^2
+    double *gx, *logpi;          // [batch][samples]
+    int batch, nblk, nrb, samples;
+    double parseval;
+};
+
+// ||X||_1 of the start state: partials [batch][gridDim.x]
+__global__ __launch_bounds__(WMB) void wav_abs_sum_kernel(const double *__restrict__ X, size_t dimX,
+                                                           double *__restrict__ part) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const double *x = X + (size_t)b * dimX;
+    double a = 0.0;
+    for (size_t q = (size_t)blockIdx.x * WMB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WMB) {
+        const double2 v = *reinterpret_cast<const double2 *>(x + 2 * q);
+        a += fabs(v.x) + fabs(v.y);
+    }
+    a = wav_block_sum(a, red);
+    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+}
+
+// One MYULA step of every chain at its own theta[b] / sigma2[b] (par), two coefficients per lane (dimX is even):
+//     X = X + gamma (soft(X, lambda theta_b) - X) / lambda - gamma G / sigma2_b + sqrt(2 gamma) Z
+// the expression of wav_myula_kernel (wav_myula_nocontract).  Z: injected normals in the layout of X, or null: pair q of chain
+// b draws philox_normal_pair(q, step, chain0 + b, seed).  X and G are read once, X is written once; part [batch][gridDim.x]
+// receives the workgroup's sum of |X_new|.  MOM: X_new is also sample mom.k of the running mean / M2 of the coefficients.
+template <bool MOM>
+__device__ __forceinline__ void wav_myula_fixed_body(double *__restrict__ X, const double *__restrict__ G,
+                                                     const double *__restrict__ Z, const double *__restrict__ par,
+                                                     int batch, double gam, double lamb, double sq2g, size_t dimX,
+                                                     const RngArgs &rng, double *__restrict__ part, const MomArgs &mom) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const size_t base = (size_t)b * dimX;
+    const double T = lamb * par[b], s2 = par[batch + b];
+    const int k = MOM ? mom.k : 0;
+    const double rk = 1.0 / (double)(k > 0 ? k : 1);
+    double a = 0.0;
+    for (size_t q = (size_t)blockIdx.x * WMB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WMB) {
+        const size_t o = base + 2 * q;
+        const double2 xv = *reinterpret_cast<const double2 *>(X + o);
+        const double2 gv = *reinterpret_cast<const double2 *>(G + o);
+        const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
+                             : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
+        double2 r;
+        r.x = wav_myula_nocontract(xv.x, gv.x, zv.x, T, gam, lamb, s2, sq2g);
+        r.y = wav_myula_nocontract(xv.y, gv.y, zv.y, T, gam, lamb, s2, sq2g);
+        *reinterpret_cast<double2 *>(X + o) = r;
+        if (MOM && k > 0) moments_pair(mom, o, r, k, rk);
+        a += fabs(r.x) + fabs(r.y);
+    }
+    a = wav_block_sum(a, red);
+    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+}
+
+__global__ __launch_bounds__(WMB) void wav_myula_fixed_kernel(double *__restrict__ X, const double *__restrict__ G,
+                                                               const double *__restrict__ Z,
+                                                               const double *__restrict__ par, int batch, double gam,
+                                                               double lamb, double sq2g, size_t dimX, RngArgs rng,
+                                                               double *__restrict__ part) {
+    wav_myula_fixed_body<false>(X, G, Z, par, batch, gam, lamb, sq2g, dimX, rng, part, MomArgs{});
+}
+
+__global__ __launch_bounds__(WMB) void wav_myula_moments_kernel(double *__restrict__ X, const double *__restrict__ G,
+                                                                 const double *__restrict__ Z,
+                                                                 const double *__restrict__ par, int batch, double gam,
+                                                                 double lamb, double sq2g, size_t dimX, RngArgs rng,
+                                                                 double *__restrict__ part, MomArgs mom) {
+    wav_myula_fixed_body<true>(X, G, Z, par, batch, gam, lamb, sq2g, dimX, rng, part, mom);
+}
+
+// The traces of the iterations ii0, ii0 + 1, ... whose partial sums sit in the ring slots 0, 1, ...: grid (batch, slots), one
+// workgroup per chain and iteration.  Slot s of iteration ii holds R = ||B W X(ii-1) - y||^2 (has_r: the row pass ran before
+// the step) and g = ||X(ii)||_1 (has_g: the step ran):
+//     logpi(ii-1) = -R / (2 sigma2_b) - theta_b gx(ii-1) ;  gx(ii) = g
+// gx(ii-1) is summed again from the slot before (the same additions in the same order as the workgroup that stores it), or,
+// for slot 0, read from the trace an earlier launch wrote.  Start state: has_g only (ii0 = 1); final residual: has_r only
+// (ii0 = samples + 1).
+__global__ __launch_bounds__(WMB) void wav_myula_trace_kernel(WavMyulaDev u, int ii0, int has_r, int has_g) {
+    __shared__ double red[4];
+    const int b = blockIdx.x, s = blockIdx.y, ii = ii0 + s, S = u.samples;
+    if (has_r) {
+        const double *a = u.acc + ((size_t)s * u.batch + b) * 3 * u.nrb;
+        double r = 0.0, gp = 0.0;
+        for (int i = threadIdx.x; i < u.nrb; i += WMB) r += a[i];
+        r = wav_block_sum(r, red);
+        if (s > 0) {
+            const double *p = u.part + ((size_t)(s - 1) * u.batch + b) * u.nblk;
+            for (int i = threadIdx.x; i < u.nblk; i += WMB) gp += p[i];
+            gp = wav_block_sum(gp, red);
+        } else {
+            gp = u.gx[(size_t)b * S + (ii - 2)];
+        }
+        const double f = (r * u.parseval) / (2 * u.par[u.batch + b]);
+        if (threadIdx.x == 0) u.logpi[(size_t)b * S + (ii - 2)] = -f - u.par[b] * gp;
+    }
+    if (has_g) {
+        const double *p = u.part + ((size_t)s * u.batch + b) * u.nblk;
+        double g = 0.0;
+        for (int i = threadIdx.x; i < u.nblk; i += WMB) g += p[i];
+        g = wav_block_sum(g, red);
+        if (threadIdx.x == 0) u.gx[(size_t)b * S + (ii - 1)] = g;
+    }
+}
+
+inline bool positive_finite(double v) { return v > 0.0 && std::isfinite(v); }
+
+}  // namespace
+}  // namespace sbtv
+
+using namespace sbtv;
+
+extern "C" {
+
+int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                       const double *h, int hlen, int levels, const sbtv_myula_wavelet_opts *op, const double *theta,
+                       const double *sigma2, const double *xw0, const double *noise, double *gx, double *logpi,
+                       double *xw_last, const sbtv_moments_opts *mo, double *post_mean, double *post_var,
+                       long long *post_count, double *coef_mean, double *coef_var, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!y || !op || !theta || !sigma2 || batch < 1)
+        return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: missing required argument (y, op, theta, sigma2, batch >= 1)");
+    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
+    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    WavPlan wp;
+    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
+    if (op->samples < 2) return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: need samples >= 2");
+    if (!positive_finite(op->lambda) || !positive_finite(op->gamma))
+        return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: lambda and gamma must be finite and > 0");
+    for (int b = 0; b < batch; ++b)
+        if (!positive_finite(theta[b]) || !positive_finite(sigma2[b]))
+            return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: every theta[b] and sigma2[b] must be finite and > 0");
+    if (op->chain_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: chain_offset must be >= 0");
+    if (((size_t)M * N) & 1)
+        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    const int samples = op->samples;
+    const size_t P = (size_t)M * N, cnt = P * batch, dimX = P * wp.bands(), ccnt = dimX * batch;
+    const bool dev = (flags & SBTV_DEVICE_PTRS) != 0;
+    // the moments request: one selection for both domains
+    MomReq sel{};
+    const MomReq *selp = nullptr;
+    if (mo) {
+        if (!post_mean && !coef_mean)
+            return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: moments need post_mean or coef_mean");
+        if ((post_var && !post_mean) || (coef_var && !coef_mean))
+            return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: post_var needs post_mean and coef_var needs coef_mean");
+        const int first = mo->first == 0 ? 1 : mo->first;
+        if (mo->thin < 1 || first < 1 || first > samples)
+            return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: need thin >= 1 and 1 <= first <= samples");
+        sel = MomReq{first, mo->thin, mo->pooled ? 1 : 0, nullptr, nullptr, nullptr, dev, false};
+        selp = &sel;
+        if (sel.pooled && batch > 1) {
+            // pooling needs chains of ONE posterior: the same y, taps, theta and sigma2 in every chain
+            const size_t t2 = (size_t)taille * taille;
+            bool same = true;
+            for (int b = 1; same && b < batch; ++b)
+                same = theta[b] == theta[0] && sigma2[b] == sigma2[0] && !memcmp(taps, taps + b * t2, sizeof(double) * t2);
+            if (same) {
+                std::vector<double> yh;
+                const double *yv = y;
+                if (dev) {
+                    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+                    yh.resize(cnt);
+                    SBTV_HIP(ctx, hipMemcpy(yh.data(), y, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+                    yv = yh.data();
+                }
+                for (int b = 1; same && b < batch; ++b) same = !memcmp(yv, yv + b * P, sizeof(double) * P);
+            }
+            if (!same)
+                return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: pooled = 1 needs chains with the same y, taps, theta and sigma2");
+        }
+    } else if (post_mean || post_var || post_count || coef_mean || coef_var) {
+        return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: moment outputs without moments options");
+    }
+    const bool mom_img = selp && post_mean, mom_coef = selp && coef_mean;
+
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    FftPlan fp;
+    SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
+    const size_t spec = fp.u_img;
+    const int nblk = wav_ew_blocks(dimX), nrb = fft_rows_blocks(fp);
+    const int ring = samples - 1 < WM_RING ? samples - 1 : WM_RING;
+    const bool noise_host = noise && !dev;
+
+    const double *yd = nullptr, *x0d = nullptr;
+    SBTV_TRY(stage_in(ctx, "wmy.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "wmy.G", xw0, ccnt, flags, &x0d));               // staged where the gradient goes later
+    double *X = nullptr, *G = nullptr, *img = nullptr, *Z = nullptr, *par = nullptr, *taps_d = nullptr, *acc = nullptr,
+           *part = nullptr, *tr_d = nullptr, *im_mean = nullptr, *im_m2 = nullptr, *c_mean = nullptr, *c_m2 = nullptr;
+    double2 *S = nullptr, *Hs = nullptr, *Ys = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "wmy.X", xw_last, ccnt, flags, &X));
+    SBTV_TRY(ws_get_t(ctx, "wmy.G", ccnt, &G));
+    SBTV_TRY(ws_get_t(ctx, "wmy.img", cnt, &img));
+    if (noise_host) SBTV_TRY(ws_get_t(ctx, "wmy.Z", ccnt, &Z));
+    SBTV_TRY(ws_get_t(ctx, "wmy.S", (size_t)batch * fp.s_img, &S));
+    SBTV_TRY(ws_get_t(ctx, "wmy.H", spec * batch, &Hs));
+    SBTV_TRY(ws_get_t(ctx, "wmy.Y", spec * batch, &Ys));
+    SBTV_TRY(ws_get_t(ctx, "wmy.acc", (size_t)ring * batch * 3 * nrb, &acc));
+    SBTV_TRY(ws_get_t(ctx, "wmy.part", (size_t)ring * batch * nblk, &part));
+    const size_t t2b = (size_t)taille * taille * batch, npar = 2 * (size_t)batch + t2b;
+    SBTV_TRY(ws_get_t(ctx, "wmy.par", npar, &par));                          // [theta | sigma2 | taps]
+    taps_d = par + 2 * (size_t)batch;
+    const size_t bs = (size_t)batch * samples, trlen = 2 * bs;
+    SBTV_TRY(ws_get_t(ctx, "wmy.traces", trlen, &tr_d));
+    if (mom_img) {
+        SBTV_TRY(ws_get_t(ctx, "wmy.im_mean", cnt, &im_mean));
+        SBTV_TRY(ws_get_t(ctx, "wmy.im_m2", cnt, &im_m2));
+    }
+    if (mom_coef) {
+        SBTV_TRY(ws_get_t(ctx, "wmy.c_mean", ccnt, &c_mean));
+        SBTV_TRY(ws_get_t(ctx, "wmy.c_m2", ccnt, &c_m2));
+    }
+    WavMyulaDev u{};
+    u.par = par; u.part = part; u.acc = acc; u.gx = tr_d; u.logpi = tr_d + bs; u.batch = batch; u.nblk = nblk; u.nrb = nrb;
+    u.samples = samples; u.parseval = 1.0 / ((double)M * N);
+
+    // constants, spectra of the PSF and of y, the start state
+    {
+        std::vector<double> hp(npar);
+        for (int b = 0; b < batch; ++b) {
+            hp[b] = theta[b];
+            hp[batch + b] = sigma2[b];
+        }
+        for (size_t q = 0; q < t2b; ++q) hp[2 * (size_t)batch + q] = taps[q];
+        SBTV_HIP(ctx, hipMemcpyAsync(par, hp.data(), sizeof(double) * npar, hipMemcpyHostToDevice, ctx->stream));
+        SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));                    // the staging vector goes out of scope
+    }
+    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
+    {
+        RowsArgs a{};
+        a.dir_fwd = 1;
+        SBTV_TRY(fft_cols_fwd(ctx, fp, yd, nullptr, S));
+        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
+        SBTV_TRY(spec_unpack(ctx, fp, S, Ys));
+    }
+    if (x0d) {
+        if (x0d != X) SBTV_HIP(ctx, hipMemcpyAsync(X, x0d, sizeof(double) * ccnt, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        SBTV_TRY(wav_analysis(ctx, wp, yd, X, batch));                       // X(1) = W'y  (run_deblur_synthesis_L1.m:153)
+    }
+    const dim3 grid(nblk, batch);
+    hipLaunchKernelGGL(wav_abs_sum_kernel, grid, dim3(WMB), 0, ctx->stream, (const double *)X, dimX, part);
+    hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, 1), dim3(WMB), 0, ctx->stream, u, 1, 0, 1);        // gx(1)
+    SBTV_HIP(ctx, hipGetLastError());
+    if (mom_coef && mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, X, c_mean, c_m2, dimX, batch));        // iteration 1
+
+    const double inv_scale = 1.0 / ((double)fp.n1 * N), gam = op->gamma, lamb = op->lambda, sq2g = sqrt(2 * gam);
+    RowsArgs ra{};
+    ra.dir_fwd = 1;
+    ra.H = Hs;
+    ra.Y = Ys;
+    // W' B'(B W X - y) -> G and ||B W X - y||^2 -> the slot's accumulators, or (resid_only) the sum alone; X is sample
+    // number `of` of the chain: its image is accumulated while the level-1 synthesis stores it
+    auto operator_pass = [&](bool resid_only, int slot, int of) -> int {
+        const MomArgs ma{im_mean, im_m2, mom_img ? mom_sample_of(selp, of) : 0, nullptr, 1, 1};
+        SBTV_TRY(wav_synthesis(ctx, wp, X, img, batch, ma.k > 0 ? &ma : nullptr));
+        SBTV_TRY(fft_cols_fwd(ctx, fp, img, nullptr, S));
+        ra.dir_inv = resid_only ? 0 : 1;
+        ra.op = resid_only ? OP_RESID : OP_GRADF;
+        ra.acc = acc + (size_t)slot * batch * 3 * nrb;
+        SBTV_TRY(fft_rows(ctx, fp, S, resid_only ? nullptr : S, ra));
+        if (resid_only) return 0;
+        SBTV_TRY(fft_cols_inv(ctx, fp, S, img, inv_scale));
+        return wav_analysis(ctx, wp, img, G, batch);
+    };
+    int filled = 0;                                                          // ring slots waiting for the trace kernel
+    for (int ii = 2; ii <= samples; ++ii) {                                  // SAPG_algorithm_1.m:131-141 at theta_b
+        const size_t step = (size_t)(ii - 2);
+        const int slot = filled;
+        SBTV_TRY(operator_pass(false, slot, ii - 1));
+        const double *zd = nullptr;
+        if (noise_host) {
+            SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * ccnt, sizeof(double) * ccnt, hipMemcpyHostToDevice, ctx->stream));
+            zd = Z;
+        } else if (noise) {
+            zd = noise + step * ccnt;
+        }
+        const RngArgs r{op->seed, (unsigned)step, (unsigned)op->chain_offset, nullptr};
+        double *pslot = part + (size_t)slot * batch * nblk;
+        const MomArgs mc{c_mean, c_m2, mom_coef ? mom_sample_of(selp, ii) : 0, nullptr, 1, 1};
+        if (mc.k > 0)
+            hipLaunchKernelGGL(wav_myula_moments_kernel, grid, dim3(WMB), 0, ctx->stream, X, (const double *)G, zd,
+                               (const double *)par, batch, gam, lamb, sq2g, dimX, r, pslot, mc);
+        else
+            hipLaunchKernelGGL(wav_myula_fixed_kernel, grid, dim3(WMB), 0, ctx->stream, X, (const double *)G, zd,
+                               (const double *)par, batch, gam, lamb, sq2g, dimX, r, pslot);
+        SBTV_HIP(ctx, hipGetLastError());
+        ctx->calls += 2 * (long long)batch;
+        if (++filled == ring || ii == samples) {
+            hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, filled), dim3(WMB), 0, ctx->stream, u, ii - filled + 1, 1, 1);
+            SBTV_HIP(ctx, hipGetLastError());
+            if (filled == WM_RING) SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            filled = 0;
+        }
+    }
+    SBTV_TRY(operator_pass(true, 0, samples));                               // the residual (and the image) of the last sample
+    hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, 1), dim3(WMB), 0, ctx->stream, u, samples + 1, 1, 0);
+    SBTV_HIP(ctx, hipGetLastError());
+    ctx->calls += batch;
+
+    if (selp) {
+        const long long n = mom_count(sel, samples);
+        if (mom_img) {
+            MomReq rq = sel;
+            rq.mean = post_mean;
+            rq.var = post_var;
+            SBTV_TRY(moments_finish(ctx, im_mean, im_m2, P, batch, n, rq));
+        }
+        if (mom_coef) {
+            MomReq rq = sel;
+            rq.mean = coef_mean;
+            rq.var = coef_var;
+            SBTV_TRY(moments_finish(ctx, c_mean, c_m2, dimX, batch, n, rq));
+        }
+        for (int c = 0; post_count && c < (sel.pooled ? 1 : batch); ++c) post_count[c] = sel.pooled ? n * batch : n;
+    }
+    std::vector<double> tr(trlen);
+    SBTV_HIP(ctx, hipMemcpyAsync(tr.data(), tr_d, sizeof(double) * trlen, hipMemcpyDeviceToHost, ctx->stream));
+    SBTV_TRY(stage_out_copy(ctx, xw_last, X, ccnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < bs; ++i) {
+        if (gx) gx[i] = tr[i];
+        if (logpi) logpi[i] = tr[bs + i];
+    }
+    return canary_epilogue(ctx, 0);
+}
+
+}  // extern "C"

@@ -22,8 +22,7 @@ namespace sbtv {
 
 namespace {
 
-constexpr int WSB = 256;          // lanes per workgroup of the kernels below
-constexpr int WS_MAXBLK = 2048;   // most workgroups (= partial sums) per chain
+constexpr int WSB = WAV_EWB;      // lanes per workgroup of the kernels below
 
 // what the update kernel keeps per chain between two iterations
 struct WavSapgChain {
@@ -53,21 +52,6 @@ struct WavSapgDev {
 
 enum { WS_PH_START = 0, WS_PH_WARMUP = 1, WS_PH_MAIN = 2, WS_PH_LAST = 3 };
 
-__device__ __forceinline__ double ws_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup in a fixed order (lanes, then the four waves); every lane returns the total
-__device__ __forceinline__ double ws_block_sum(double v, double *red) {
-    v = ws_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ||X||_1 of the start state: partials [batch][gridDim.x]
 __global__ __launch_bounds__(WSB) void wav_l1_kernel(const double *__restrict__ X, size_t dimX,
                                                       double *__restrict__ part) {
@@ -79,7 +63,7 @@ __global__ __launch_bounds__(WSB) void wav_l1_kernel(const double *__restrict__ 
         const double2 v = *reinterpret_cast<const double2 *>(x + 2 * q);
         a += fabs(v.x) + fabs(v.y);
     }
-    a = ws_block_sum(a, red);
+    a = wav_block_sum(a, red);
     if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
 }
 
@@ -107,12 +91,12 @@ __global__ __launch_bounds__(WSB) void wav_myula_kernel(double *__restrict__ X, 
         const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
                              : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
         double2 r;
-        r.x = ((xv.x + gam * (wav_soft(xv.x, T) - xv.x) / lamb) - gam * (gv.x / s2)) + sq2g * zv.x;
-        r.y = ((xv.y + gam * (wav_soft(xv.y, T) - xv.y) / lamb) - gam * (gv.y / s2)) + sq2g * zv.y;
+        r.x = wav_myula_nocontract(xv.x, gv.x, zv.x, T, gam, lamb, s2, sq2g);
+        r.y = wav_myula_nocontract(xv.y, gv.y, zv.y, T, gam, lamb, s2, sq2g);
         *reinterpret_cast<double2 *>(X + o) = r;
         a += fabs(r.x) + fabs(r.y);
     }
-    a = ws_block_sum(a, red);
+    a = wav_block_sum(a, red);
     if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
 }
 
@@ -128,11 +112,11 @@ __global__ __launch_bounds__(WSB) void wav_sapg_update_kernel(WavSapgDev u, int 
     double r = 0.0, g = 0.0;
     if (phase != WS_PH_START) {
         for (int i = threadIdx.x; i < u.nrb; i += WSB) r += u.acc[(size_t)b * 3 * u.nrb + i];
-        r = ws_block_sum(r, red);
+        r = wav_block_sum(r, red);
     }
     if (phase != WS_PH_LAST) {
         for (int i = threadIdx.x; i < u.nblk; i += WSB) g += u.part[(size_t)b * u.nblk + i];
-        g = ws_block_sum(g, red);
+        g = wav_block_sum(g, red);
     }
     if (threadIdx.x != 0) return;
     WavSapgChain c = u.chain[b];
@@ -173,11 +157,6 @@ __global__ __launch_bounds__(WSB) void wav_sapg_update_kernel(WavSapgDev u, int 
     u.chain[b] = c;
 }
 
-inline int ws_blocks(size_t dimX) {
-    const size_t nb = (dimX / 2 + WSB - 1) / WSB;
-    return nb > (size_t)WS_MAXBLK ? WS_MAXBLK : (nb < 1 ? 1 : (int)nb);
-}
-
 }  // namespace
 }  // namespace sbtv
 
@@ -209,7 +188,7 @@ int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
     const int samples = op->samples, warmup = op->warmup, wsteps = warmup > 0 ? warmup - 1 : 0, wstride = warmup > 0 ? warmup : 1;
     const size_t P = (size_t)M * N, cnt = P * batch, dimX = P * wp.bands(), ccnt = dimX * batch, spec = fp.u_img;
-    const int nblk = ws_blocks(dimX), nrb = fft_rows_blocks(fp);
+    const int nblk = wav_ew_blocks(dimX), nrb = fft_rows_blocks(fp);
     const bool noise_host = noise && !(flags & SBTV_DEVICE_PTRS);
 
     const double *yd = nullptr, *x0d = nullptr;

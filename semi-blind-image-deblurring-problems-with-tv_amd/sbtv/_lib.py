@@ -66,6 +66,11 @@ class sbtv_moments_opts(C.Structure):
     _fields_ = [("first", C.c_int), ("thin", C.c_int), ("pooled", C.c_int)]
 
 
+class sbtv_myula_wavelet_opts(C.Structure):
+    _fields_ = [("samples", C.c_int), ("lambda_", C.c_double), ("gamma", C.c_double), ("seed", C.c_ulonglong),
+                ("chain_offset", C.c_int)]
+
+
 class sbtv_diag_pass(C.Structure):
     _fields_ = ([(n, C.c_int) for n in ("M", "N", "batch", "op", "epilogue", "taille", "shared_spec", "repeats")]
                 + [(n, C.c_void_p) for n in ("x", "add", "taps", "d1taps", "d2taps", "y", "e0", "mu", "cs", "frozen", "u",
@@ -137,6 +142,8 @@ SIGNATURES = {
     "sbtv_myula": (_I, [_P, _P, _I, _I, _I, _P, _I, _D, _D, _P, _P, _I, _I, C.c_ulonglong, _I, _P, _P, _I]),
     "sbtv_myula_moments": (_I, [_P, _P, _I, _I, _I, _P, _I, _D, _D, _P, _P, _I, _I, C.c_ulonglong, _I, _P, _P,
                                 C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
+    "sbtv_myula_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, C.POINTER(sbtv_myula_wavelet_opts), _P, _P, _P, _P, _P,
+                                _P, _P, C.POINTER(sbtv_moments_opts), _P, _P, _P, _P, _P, _I]),
     "sbtv_max_eigenval": (_I, [_P, _P, _I, _P, _I, _I, _D, _I, _P, _P, _I]),
     "sbtv_PSNR": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
     "sbtv_MSE": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),

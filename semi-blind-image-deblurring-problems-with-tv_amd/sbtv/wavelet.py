@@ -2,7 +2,8 @@
 `mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
 with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
 `SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), and `SAPG_wavelet`, the empirical-Bayes estimate of the
-regularisation parameter that the script runs first (the theta part of SALSA/SAPG_algorithm_1.m).  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
+regularisation parameter that the script runs first (the theta part of SALSA/SAPG_algorithm_1.m), and `myula_wavelet`, the
+MYULA chain at a fixed theta with the posterior mean / variance of its samples.  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
 [a_J | LH1 HL1 HH1 | LH2 ...], or (B, M, (3J+1) N) for a batch; host and device arrays as everywhere in this package."""
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import numpy as np
 
 from . import _lib as L
 from .admm import _common
+from .sapg import _moment_buffers, _moments_opts
 from .tv import _parse_varargin
 
 _WAVELET_OPTIONS = {"MU", "WAVELET", "LEVELS", "AT", "STOPCRITERION", "TOLERANCEA", "MAXITERA", "TRUE_X", "INITIALIZATION",
@@ -166,8 +168,35 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
 def _op(op, name, default=None):
     v = op.get(name, default) if isinstance(op, dict) else getattr(op, name, default)
     if v is None:
-        raise KeyError(f"SAPG_wavelet: op.{name} is required")
+        raise KeyError(f"op.{name} is required")
     return v
+
+
+def _chain_noise(noise, yi, steps, nb, steps_text):
+    """(array kept alive, pointer) of the injected normals of a chain on the coefficients: `steps` steps of [B][M, nb N]."""
+    if noise is None:
+        return None, None
+    B, M, N = yi.B, yi.M, yi.N
+    if L._is_torch(noise):
+        if yi.flags != L.SBTV_DEVICE_PTRS:
+            raise ValueError("all image arguments must live in the same memory space")
+        # the step kernel reads steps * B * dimX doubles from this pointer: anything else is an out-of-bounds read
+        want = steps * B * M * nb * N
+        # (dense: its elements fill one gap-free span of memory, as a contiguous tensor or a `to_device` view does)
+        span = 1 + sum((n - 1) * st for n, st in zip(noise.shape, noise.stride())) if noise.numel() else 0
+        if str(noise.dtype) != "torch.float64" or noise.numel() != want or span != want or any(st < 1 for st in noise.stride()):
+            raise ValueError(f"a device noise tensor must be dense float64 with ({steps_text}) * B * "
+                             f"M * (3 (levels-1) + 1) N = {want} elements, in the library's layout")
+        return noise, C.c_void_p(noise.data_ptr())
+    if yi.flags != L.SBTV_HOST_PTRS:
+        raise ValueError("all image arguments must live in the same memory space")
+    a = np.asarray(noise, dtype=np.float64)
+    if a.ndim == 3:
+        a = a[:, None]
+    if a.shape != (steps, B, M, nb * N):
+        raise ValueError(f"noise must be ({steps_text}, [B,] M, (3 (levels-1) + 1) N)")
+    keep = L.column_major_images(a.reshape((-1,) + a.shape[2:]))
+    return keep, _vp(keep)
 
 
 def SAPG_wavelet(y, A, h, levels, op, noise=None, xw0=None, ctx=None):
@@ -217,29 +246,7 @@ def SAPG_wavelet(y, A, h, levels, op, noise=None, xw0=None, ctx=None):
             raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
         if x0i.flags != yi.flags:
             raise ValueError("all image arguments must live in the same memory space")
-    nz_ptr, nz_keep = None, None
-    if noise is not None:
-        if L._is_torch(noise):
-            if yi.flags != L.SBTV_DEVICE_PTRS:
-                raise ValueError("all image arguments must live in the same memory space")
-            # the step kernel reads steps * B * dimX doubles from this pointer: anything else is an out-of-bounds read
-            want = (max(Wn - 1, 0) + S - 1) * B * M * nb * N
-            # (dense: its elements fill one gap-free span of memory, as a contiguous tensor or a `to_device` view does)
-            span = 1 + sum((n - 1) * st for n, st in zip(noise.shape, noise.stride())) if noise.numel() else 0
-            if str(noise.dtype) != "torch.float64" or noise.numel() != want or span != want or any(st < 1 for st in noise.stride()):
-                raise ValueError("a device noise tensor must be dense float64 with (max(warmup-1, 0) + samples-1) * B * "
-                                 f"M * (3 (levels-1) + 1) N = {want} elements, in the library's layout")
-            nz_keep, nz_ptr = noise, C.c_void_p(noise.data_ptr())
-        else:
-            if yi.flags != L.SBTV_HOST_PTRS:
-                raise ValueError("all image arguments must live in the same memory space")
-            a = np.asarray(noise, dtype=np.float64)
-            if a.ndim == 3:
-                a = a[:, None]
-            if a.shape != (max(Wn - 1, 0) + S - 1, B, M, nb * N):
-                raise ValueError("noise must be (max(warmup-1, 0) + samples-1, [B,] M, (3 (levels-1) + 1) N)")
-            nz_keep = L.column_major_images(a.reshape((-1,) + a.shape[2:]))
-            nz_ptr = _vp(nz_keep)
+    nz_keep, nz_ptr = _chain_noise(noise, yi, max(Wn - 1, 0) + S - 1, nb, "max(warmup-1, 0) + samples-1")
     thetas, gx, logpi, tol = (np.zeros((B, max(S, 1))) for _ in range(4))
     logpi_wu = np.zeros((B, max(Wn, 1)))
     means = np.zeros((B, max(S - o.burnIn, 1)))
@@ -262,3 +269,85 @@ def SAPG_wavelet(y, A, h, levels, op, noise=None, xw0=None, ctx=None):
     if sq:
         return float(eb[0]), results[0]
     return eb, results
+
+
+def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=None, posterior=None, ctx=None):
+    """results = myula_wavelet(y, A, h, levels, op, theta, sigma2)
+
+    MYULA chain on the wavelet coefficients at a FIXED theta: samples of p(xw | y, theta) ~ exp(-||y - A W xw||^2 / (2 sigma2)
+    - theta ||xw||_1), e.g. at the theta_EB of SAPG_wavelet, with the posterior mean (the MMSE image) and variance of the
+    samples accumulated on the device.  It is the warm-up loop of SALSA/SAPG_algorithm_1.m:131-141 with the closures of
+    run_deblur_synthesis_L1.m:135-146 (include/sbtv.h, sbtv_myula_wavelet, states it); iteration 1 is the start state, samples-1
+    steps follow.
+    A, h, levels: as for SAPG_wavelet.  op (dict or object): samples, lambda, gamma; optional theta, sigma2 (or sigma), X0, seed
+    (1), chain_offset (0).  theta / sigma2 (default op.theta / op.sigma2): a scalar or one value per image of a batch.
+    noise: optional (samples-1, [B,] M, (3J+1) N) normals instead of the device Philox stream, as for SAPG_wavelet.
+    posterior: None (no moments), True, or dict(first=1, thin=1, pooled=False, coefficients=False): the iterations first,
+    first + thin, ... of 1..samples; pooled: one set over the chains of the call (chains of one posterior only);
+    coefficients: also the mean / variance per coefficient.
+    Returns a dict (a list of dicts for a batch): Xlast_sample, gXTrace (||X(ii)||_1), logPiTraceX, options, and with posterior:
+    posteriormean, posteriorvar (images W X(ii)), posteriorcount, and coefmean, coefvar when coefficients are requested.
+    Device tensors in give device tensors out."""
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("myula_wavelet has no sharded variant")
+    yi = L.Images(y)
+    B, M, N = yi.B, yi.M, yi.N
+    nb = max(_bands(levels), 1)
+    ha, hp, K = _filter(h)
+    o = L.sbtv_myula_wavelet_opts()
+    o.samples = int(_op(op, "samples"))
+    o.lambda_ = float(_op(op, "lambda"))
+    o.gamma = float(_op(op, "gamma"))
+    o.seed = int(_op(op, "seed", 1))
+    o.chain_offset = int(_op(op, "chain_offset", 0))
+    get = lambda name: op.get(name) if isinstance(op, dict) else getattr(op, name, None)
+    if theta is None:
+        theta = _op(op, "theta")
+    if sigma2 is None:
+        sigma2 = get("sigma2")
+        if sigma2 is None:
+            sigma2 = np.asarray(_op(op, "sigma"), dtype=np.float64) ** 2
+    keep = [L.dvec(theta, B), L.dvec(sigma2, B)]
+    S = o.samples
+    if xw0 is None:
+        xw0 = get("X0")
+    x0i = L.Images(xw0) if xw0 is not None else None
+    if x0i is not None:
+        if (x0i.B, x0i.M, x0i.N) != (B, M, nb * N):
+            raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+        if x0i.flags != yi.flags:
+            raise ValueError("all image arguments must live in the same memory space")
+    nz_keep, nz_ptr = _chain_noise(noise, yi, max(S - 1, 0), nb, "samples-1")
+    gx, logpi = np.zeros((B, max(S, 1))), np.zeros((B, max(S, 1)))
+    xl = _resized(yi, nb * N)
+    taps = A._cm(B)
+    mo, pm, pv, pc, cm, cv, pooled = None, None, None, None, None, None, False
+    if posterior is not None and posterior is not False:
+        p = {} if posterior is True else dict(posterior)
+        coefficients = bool(p.pop("coefficients", False))
+        mo = _moments_opts(p if p else True)
+        pooled = bool(mo.pooled)
+        pm, pv, pc = _moment_buffers(yi, 1 if pooled else B)
+        if coefficients:
+            cm, cv, _ = _moment_buffers(xl, 1 if pooled else B)
+    ptr = lambda im: im.ptr if im is not None else None
+    ctx.check(ctx.lib.sbtv_myula_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, int(levels), C.byref(o),
+                                         keep[0][1], keep[1][1], ptr(x0i), nz_ptr, _vp(gx), _vp(logpi), xl.ptr,
+                                         C.byref(mo) if mo is not None else None, ptr(pm), ptr(pv),
+                                         _vp(pc) if pc is not None else None, ptr(cm), ptr(cv), yi.flags), yi.flags)
+    xs = L.images_result(xl, False)
+    moments = {}
+    if mo is not None:
+        moments = {k: L.images_result(v, False) for k, v in (("posteriormean", pm), ("posteriorvar", pv), ("coefmean", cm),
+                                                             ("coefvar", cv)) if v is not None}
+    results = []
+    for b in range(B):
+        r = dict(Xlast_sample=xs[b], gXTrace=gx[b], logPiTraceX=logpi[b], options=op)
+        for k, v in moments.items():
+            r[k] = v[0 if pooled else b]
+        if mo is not None:
+            r["posteriorcount"] = int(pc[0 if pooled else b])
+        results.append(r)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    return results[0] if sq else results

@@ -2,8 +2,10 @@
 """SALSA/run_deblur_synthesis_L1.m end to end on the MI355X through the host mirror: 9 x 9 uniform blur at BSNR 30 ->
 empirical-Bayes estimate of theta for the Laplace prior on the coefficients of the redundant 4-level Haar frame
 (`sbtv.SAPG_wavelet`, :125-156) -> MAP image by `sbtv.SALSA_wavelet` at tau = theta_EB sigma^2, mu = theta_EB (:160-185).
+With `--posterior S` also S samples of the posterior at theta_EB (`sbtv.myula_wavelet`, started at the MAP coefficients): the
+MMSE image next to the MAP image, and the per-pixel standard deviation; `--out DIR` is where both are saved (.npy and .pgm).
 
-  python tools/run_wavelet_demo.py [--image tests/golden/man_512.npy] [--samples 3000] [--seed 1]
+  python tools/run_wavelet_demo.py [--image tests/golden/man_512.npy] [--samples 3000] [--seed 1] [--posterior S] [--out DIR]
 
 Constants follow the script (:65-83,99,106-107,164-166).  The reference's uniform_blur is centred; the library's taps sit in
 the top-left corner (utils/resize.m), which delays the blurred image by 4 pixels in both directions.  The observation is made
@@ -28,6 +30,10 @@ def main():
     ap.add_argument("--image", default=os.path.join(ROOT, "tests", "golden", "man_512.npy"))
     ap.add_argument("--samples", type=int, default=3000)                 # op.samples (:65)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--posterior", type=int, default=0, metavar="S",
+                    help="after theta_EB, S MYULA samples at theta_EB: MMSE image and standard-deviation map")
+    ap.add_argument("--posterior-first", type=int, default=0, help="first iteration used (default: S / 10 + 1)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "out"), help="directory for the mean / standard-deviation maps")
     a = ap.parse_args()
     x = np.load(a.image).astype(np.float64)
     dimX = x.size
@@ -66,6 +72,26 @@ def main():
     print(f"SALSA_wavelet: {len(out[4]) - 1} outer iterations in {t_map:.2f} s, MSE {mse:.2f} dB "
           f"(observation: {10 * math.log10(np.linalg.norm(x - y) ** 2 / dimX):.2f} dB)")
     print(f"wall time {t_eb + t_map:.2f} s")
+    if a.posterior >= 2:
+        first = a.posterior_first or a.posterior // 10 + 1
+        pop = {"samples": a.posterior, "lambda": lam, "gamma": op["gamma"], "seed": a.seed + 1}
+        t0 = time.perf_counter()
+        post = sbtv.myula_wavelet(y, A, h, levels, pop, theta=theta_EB, sigma2=sigma ** 2, xw0=np.asarray(out[0]),
+                                  posterior=dict(first=first), ctx=ctx)
+        t_post = time.perf_counter() - t0
+        xMMSE = np.roll(np.asarray(post["posteriormean"]), (c, c), axis=(0, 1))
+        sd = np.roll(np.sqrt(np.asarray(post["posteriorvar"])), (c, c), axis=(0, 1))
+        mmse = 10 * math.log10(np.linalg.norm(x - xMMSE) ** 2 / dimX)
+        err = np.abs(x - xMMSE)
+        print(f"myula_wavelet at theta_EB: {a.posterior} samples in {t_post:.2f} s, iterations {first}.. used "
+              f"({post['posteriorcount']}); MSE of the MMSE image {mmse:.2f} dB (MAP {mse:.2f} dB); standard deviation: "
+              f"mean {sd.mean():.3f}, max {sd.max():.3f}; correlation of |x - MMSE| with it {np.corrcoef(err.ravel(), sd.ravel())[0, 1]:.2f}")
+        os.makedirs(a.out, exist_ok=True)
+        np.save(os.path.join(a.out, "wavelet_posterior_mean.npy"), xMMSE)
+        np.save(os.path.join(a.out, "wavelet_posterior_std.npy"), sd)
+        sbtv.save_image(os.path.join(a.out, "wavelet_posterior_mean.pgm"), xMMSE, 0.0, 255.0)
+        sbtv.save_image(os.path.join(a.out, "wavelet_posterior_std.pgm"), sd)
+        print(f"saved mean and standard-deviation maps under {a.out}")
 
 
 if __name__ == "__main__":
