@@ -339,7 +339,8 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
  * coefficients drives the log-scale stochastic update of SALSA/SAPG_algorithm_1.m:165-216, and the solve then runs at
  * tau = theta_EB sigma^2, mu = theta_EB (:167,175).  SAPG_algorithm_1.m as shipped cannot be called by that script: it wants
  * op.to_init, op.grad_t and a two-argument gradF for a second parameter `tau` that the script never defines (SURVEY.md
- * section 2.3).  This entry point is its theta part, which is what the script's comments and constants describe.
+ * section 2.3).  This entry point is its theta part, which is what the script's comments and constants describe
+ * (sbtv_SAPG_wavelet_semiblind below adds the tau part, with the PSF parameters as tau).
  * One chain per image y_b; state X: [3J+1][M*N] coefficients in the layout of sbtv_mrdwt_TI2D, dimX = (3J+1) M N; W =
  * mirdwt_TI2D, W' = mrdwt_TI2D, B = circular blur of taps[b], soft = SALSA/soft.m (the script's proxG, :137):
  *     X = xw0 (NULL: W' y, :153) ;  prox = soft(X, lambda theta(1))
@@ -392,6 +393,89 @@ int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                       double *thetas, double *gx, double *logpi, double *logpi_wu,
                       double *mean_thetas, double *tol_thetas, double *theta_eb,
                       double *xw_last, int flags);
+
+/* ---- semi-blind empirical Bayes for the wavelet-l1 prior: theta, the PSF parameters and sigma2 from one chain ------------
+ * SALSA/SAPG_algorithm_1.m is a two-parameter algorithm: next to theta it carries `tau` with its own projected gradient step
+ * (:105-108,117,133,149-151,174,185-186,204-205,213,236-242).  The script run_deblur_synthesis_L1.m never defines op.to_init,
+ * op.grad_t or the two-argument gradF it needs; the TV half of this library defines exactly those closures for three PSF
+ * families (dA/dp, the tap derivatives of sbtv_psf_taps).  This entry is SAPG_algorithm_1.m with tau = the PSF parameters p,
+ * scaled as SAPG/SAPG_algorithm_laplace.m:172-178, plus the sigma2 step of SAPG_algorithm_laplace.m:181-186.  One chain per
+ * image y_b; state, frame, soft, dimX = (3J+1) M N and the noise layout are those of sbtv_SAPG_wavelet; the blur is B_p, the
+ * circular blur of sbtv_psf_taps(kind, psf_size, p): there is no `taps` argument.  P = M N, pm = p(ii-1), s = sigma2(ii-1):
+ *     X = xw0 (NULL: W' y) ;  prox = soft(X, lambda theta(1))
+ *     warm-up, ii = 2..warmup, at th_init, p_init, sigma2(1)  (SAPG_algorithm_1.m:131-141 with gradF(X, fix_tau)):
+ *         the step below ;  logpi_wu(ii) = -||y - B_p W X||^2 / (2 sigma2(1)) - th_init ||X||_1       (logpi_wu(1) = 0)
+ *     logpi(1) = logPi(X, theta(1), p(1), sigma2(1)) ;  eta(1) = log th_init ;  p(1) = p_init ;  sigma2(1) = op.sigma2
+ *     ii = 2..samples:
+ *         X    = ((X + gamma (prox - X)/lambda) - gamma (W'B_pm'(B_pm W X - y)/s)) + sqrt(2 gamma) Z               (:174)
+ *         prox = soft(X, lambda theta(ii-1)) ;  g = ||X||_1                                                         (:175)
+ *         eta(ii), theta(ii): exactly the log-scale step and clamp of sbtv_SAPG_wavelet                             (:180-182)
+ *         r = B_pm W X - y ;  R = ||r||^2
+ *         G_pq = <(dB/dp_q)(pm) W X, r> / s                                              (the script's missing op.grad_t)
+ *         p_q(ii) = clamp(fix_p[q] ? p_true[q] : p_q(ii-1) - c_p[q] delta(ii) G_pq, p_min[q], p_max[q])            (:185-186)
+ *         G_s = R/(2 s^2) - P/(2 s) ;  sigma2(ii) = clamp(fix_sigma ? sigma2(1) : s + c_sigma delta(ii) G_s, sigma2_min,
+ *             sigma2_max)                                                           (SAPG_algorithm_laplace.m:181-186)
+ *         logpi(ii) = -R/(2 s) - theta(ii-1) g ;  gx(ii-1) = g                                                      (:190-191)
+ *         tol_thetas / mean_thetas as sbtv_SAPG_wavelet ;  tol_ps(q, ii) = |a(ii) - a(ii-1)| / a(ii-1) and
+ *         mean_ps(q, ii - burnIn) = a(ii) with the ARITHMETIC mean a(i) = mean(p_q(burnIn..i))                (:204-205,213)
+ *     theta_EB = exp(mean eta(burnIn..samples)) ;  p_EB, sigma2_EB = arithmetic means over burnIn..samples        (:226,236)
+ *   delta(i) = d_scale i^(-d_exp) / dimX with dimX the COEFFICIENT count (:111); G_s uses the PIXEL count P, the dimension of
+ *   y.  The clamps apply to fixed values too, as in sbtv_SAPG_algorithm: give bounds that contain p_true / sigma2.  A fixed
+ *   PSF parameter starts at p_init like a free one and is p_true from ii = 2 on.  Laplace has one parameter: slot 1 of ps is
+ *   p_init[1] throughout (as is p1_EB), slot 1 of grads, tol_ps and mean_ps stays 0.  The means are running sums in
+ *   iteration order; an entry whose window is empty, or whose previous mean is 0, is NaN as in MATLAB.
+ *   Deliberate deviation: SAPG_algorithm_1.m:190 evaluates logPi at the unclamped new `to`; that would cost another operator
+ *   evaluation and is not what the TV family does (SAPG_algorithm_laplace.m:194).  logpi(ii) uses p(ii-1).
+ *   Moffat alpha: utils/diff_moffat_alpha.m:17 (and with it the d0 of sbtv_psf_taps, which reproduces the reference) carries
+ *   alpha/(2 pi) where the derivative of alpha^2/(2 pi) gives alpha/pi: half the derivative of psf_moffat.m, in every tap.  G_p
+ *   of this entry is the derivative of ||y - B_p W X||^2 / (2 sigma2) (checked against a finite difference), so the Moffat
+ *   G_p0 is twice the <d0-blur W X, r> / s of the TV family's closure: c_p[0] here corresponds to 2 c_alpha there.
+ * What runs: device-resident like sbtv_SAPG_wavelet; the host enqueues without waiting, one
+ * synchronisation per 1024 iterations and one at the end.  One iteration: row pass OP_GRADF on the column spectrum of W X
+ * that the previous iteration left, inverse column pass, J analysis launches; the step kernel (the shared step function of
+ * sbtv_SAPG_wavelet, sigma2 and the lagging theta read from device memory); J synthesis launches, forward column pass, a row
+ * pass without store that leaves R and the two <dB W X, r> sums, so the residual of sample ii is known in iteration ii; the
+ * update kernel, one workgroup per chain, every sum in a fixed order, which with a free PSF parameter also builds the taps
+ * and derivative taps of p(ii) (MATLAB's column-major summation order); then the tap spectra.  With every PSF parameter fixed
+ * at p_true = p_init no taps are computed on the device and no spectrum is rebuilt; the start spectra come from host taps
+ * (sbtv_psf_taps).  Chains of a batch share every launch; chain b is computed bit for bit as alone.  There is no host-loop
+ * variant, no lanes, no graph capture, no sharded variant and no reduce_fn.  PSF sizes other than 7 x 7 are accepted as far
+ * as sbtv_SAPG_algorithm accepts them but are untested in this entry.
+ *   p_start: NULL (every chain starts at op->p_init) or [batch*2], host: the start values of chain b
+ *   noise: as sbtv_SAPG_wavelet, the same Philox counters
+ *   traces (host, may be NULL): thetas, sigmas, gx, logpi, tol_thetas [batch*samples]; ps, tol_ps [batch*2*samples];
+ *          grads (G_p0, G_p1, G_s) [batch*3*samples]; logpi_wu [batch*warmup]; mean_thetas [batch*(samples-burnIn)];
+ *          mean_ps [batch*2*(samples-burnIn)];  eb (theta, p0, p1, sigma2) [batch*4] (required);  xw_last: last sample
+ *   SBTV_DEVICE_PTRS applies to y / xw0 / noise / xw_last.
+ * Refused before any GPU work: everything sbtv_SAPG_wavelet refuses, with its codes (op->sigma2 is sigma2(1)); kind or
+ * psf_size as sbtv_SAPG_algorithm refuses them (SBTV_ERR_PSF); with SBTV_ERR_BADARG: a free PSF parameter without
+ * 0 < p_min <= p_init <= p_max (every chain's start), c_p or c_sigma negative or non-finite, a free sigma2 without
+ * 0 < sigma2_min <= sigma2 <= sigma2_max. */
+typedef struct sbtv_sapg_wavelet_sb_opts {
+    int    samples, warmup, burnIn;      /* as sbtv_sapg_wavelet_opts                    */
+    double lambda, gamma;
+    double sigma2;            /* sigma2(1); the noise variance throughout if fix_sigma   */
+    double th_init, min_th, max_th;
+    double d_scale, d_exp;    /* delta(i) = d_scale * i^-d_exp / dimX                    */
+    unsigned long long seed;  /* Philox seed when noise == NULL                          */
+    int    chain_offset;      /* chain b draws the Philox stream chain_offset + b        */
+    int    kind;              /* SBTV_PSF_*        (from here on: as sbtv_sapg_opts)     */
+    int    psf_size;
+    int    fix_p[2];
+    int    fix_sigma;
+    double phi;
+    double p_init[2], p_min[2], p_max[2], p_true[2];
+    double sigma2_min, sigma2_max;
+    double c_p[2], c_sigma;
+} sbtv_sapg_wavelet_sb_opts;
+int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                                const double *h, int hlen, int levels,
+                                const sbtv_sapg_wavelet_sb_opts *op, const double *p_start,
+                                const double *xw0, const double *noise,
+                                double *thetas, double *ps, double *sigmas, double *gx, double *logpi,
+                                double *logpi_wu, double *grads, double *mean_thetas, double *tol_thetas,
+                                double *mean_ps, double *tol_ps, double *eb,
+                                double *xw_last, int flags);
 
 /* ---- a-8: FISTA with the TV prox ----------------------------------------
  * Replaces my_fista(b,A,AT,tau,L,Phi,Psi,stopcriterion,tolerance,maxiters,true,verbose)

@@ -2,7 +2,7 @@
 // on the coefficients of the redundant wavelet frame and the log-scale stochastic update of SALSA/SAPG_algorithm_1.m:120-216,
 // as SALSA/run_deblur_synthesis_L1.m:125-156 sets them up (proxG = soft, g = l1, gradF = W' B'(B W xw - y) / sigma2).  Only the
 // theta part of SAPG_algorithm_1.m is built: its second parameter `tau` needs op.to_init, op.grad_t and a two-argument gradF
-// that the script never defines.
+// that the script never defines; csrc/wavelet_sapg_sb.hip builds that part with the PSF parameters as tau.
 //
 // The loop is device-resident.  The array-sized state is the chain X [batch][3J+1][M N] and the gradient; the prox is never
 // stored: wav_myula_kernel recomputes soft(X, lambda theta) from X and the theta the reference formed it with, which lags

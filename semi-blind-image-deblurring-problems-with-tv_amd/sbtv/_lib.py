@@ -62,6 +62,20 @@ class sbtv_sapg_wavelet_opts(C.Structure):
                 ("seed", C.c_ulonglong), ("chain_offset", C.c_int)]
 
 
+class sbtv_sapg_wavelet_sb_opts(C.Structure):
+    _fields_ = [("samples", C.c_int), ("warmup", C.c_int), ("burnIn", C.c_int),
+                ("lambda_", C.c_double), ("gamma", C.c_double), ("sigma2", C.c_double),
+                ("th_init", C.c_double), ("min_th", C.c_double), ("max_th", C.c_double),
+                ("d_scale", C.c_double), ("d_exp", C.c_double),
+                ("seed", C.c_ulonglong), ("chain_offset", C.c_int),
+                ("kind", C.c_int), ("psf_size", C.c_int), ("fix_p", C.c_int * 2), ("fix_sigma", C.c_int),
+                ("phi", C.c_double),
+                ("p_init", C.c_double * 2), ("p_min", C.c_double * 2), ("p_max", C.c_double * 2),
+                ("p_true", C.c_double * 2),
+                ("sigma2_min", C.c_double), ("sigma2_max", C.c_double),
+                ("c_p", C.c_double * 2), ("c_sigma", C.c_double)]
+
+
 class sbtv_moments_opts(C.Structure):
     _fields_ = [("first", C.c_int), ("thin", C.c_int), ("pooled", C.c_int)]
 
@@ -134,6 +148,8 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_opts), _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _I]),
+    "sbtv_SAPG_wavelet_semiblind": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_sb_opts), _P, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),

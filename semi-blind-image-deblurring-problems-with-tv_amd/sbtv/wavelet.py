@@ -351,3 +351,123 @@ def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=
         results.append(r)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
     return results[0] if sq else results
+
+
+_PSF_KIND = {"gaussian": 0, "moffat": 1, "laplace": 2}
+
+
+def _pair(v, npar, fill=0.0):
+    """A one- or two-element option as a 2-vector (a one-parameter family leaves slot 1 at `fill`)."""
+    a = np.atleast_1d(np.asarray(v, dtype=np.float64)).ravel()
+    if a.size < npar or a.size > 2:
+        raise ValueError("a per-parameter option must have one entry per PSF parameter")
+    out = np.full(2, float(fill))
+    out[:a.size] = a
+    return out
+
+
+def SAPG_wavelet_semiblind(y, kind, h, levels, op, noise=None, xw0=None, ctx=None):
+    """[eb, results] = SAPG_wavelet_semiblind(y, kind, h, levels, op)
+
+    Semi-blind empirical Bayes for the wavelet-l1 prior: theta, the parameters p of a PSF family and sigma2 estimated together
+    from one device-resident MYULA chain on the wavelet coefficients.  It is SALSA/SAPG_algorithm_1.m with both of its
+    parameters, `tau` being the PSF parameters with the closures of the TV half of this package (include/sbtv.h,
+    sbtv_SAPG_wavelet_semiblind, states the loop).  No blur operator is given: the blur is psf_family(kind, psf_size, p).
+    kind: "gaussian" (w1, w2), "moffat" (alpha, beta) or "laplace" (b); h, levels: the frame, as for mrdwt_TI2D.
+    op (dict or object): everything SAPG_wavelet takes (sigma / sigma2 is sigma2(1), the noise variance itself while
+    fix_sigma), and p_init (one or two values, or one row per image of a batch); optional psf_size (7), phi (0), fix_p
+    (all free), p_true (p_init), p_min / p_max (required for a free parameter; p_true for a fixed one), c_p (1 each),
+    fix_sigma (True), and for a free sigma2: sigma2_min, sigma2_max, c_sigma.
+    noise, xw0: as for SAPG_wavelet, the same device-noise validation.
+    Returns eb = dict(theta, p, sigma2) (arrays per image for a batch) and results with the keys of SAPG_wavelet plus ps
+    (2, samples), sigmas, grads (3, samples: G_p0, G_p1, G_sigma2), mean_ps, tol_ps, p_EB, sigma2_EB, mean_theta.  Then e.g.
+    psf_family(kind, psf_size, p_EB) -> SALSA_wavelet / myula_wavelet."""
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("SAPG_wavelet_semiblind has no sharded variant")
+    yi = L.Images(y)
+    B, M, N = yi.B, yi.M, yi.N
+    nb = max(_bands(levels), 1)
+    ha, hp, K = _filter(h)
+    get = lambda name, default=None: op.get(name, default) if isinstance(op, dict) else getattr(op, name, default)
+    o = L.sbtv_sapg_wavelet_sb_opts()
+    o.samples = int(_op(op, "samples"))
+    o.warmup = int(_op(op, "warmup", 0))
+    o.burnIn = int(_op(op, "burnIn"))
+    o.lambda_ = float(_op(op, "lambda"))
+    o.gamma = float(_op(op, "gamma"))
+    s2 = get("sigma2")
+    o.sigma2 = float(s2) if s2 is not None else float(_op(op, "sigma")) ** 2
+    o.th_init = float(_op(op, "th_init"))
+    o.min_th = float(_op(op, "min_th"))
+    o.max_th = float(_op(op, "max_th"))
+    o.d_scale = float(_op(op, "d_scale"))
+    o.d_exp = float(_op(op, "d_exp"))
+    o.seed = int(_op(op, "seed", 1))
+    o.chain_offset = int(_op(op, "chain_offset", 0))
+    o.kind = _PSF_KIND[kind] if isinstance(kind, str) else int(kind)
+    npar = 1 if o.kind == 2 else 2
+    o.psf_size = int(_op(op, "psf_size", 7))
+    o.phi = float(_op(op, "phi", 0.0))
+    pin = np.asarray(_op(op, "p_init"), dtype=np.float64)
+    if pin.ndim == 2:
+        if pin.shape[0] != B:
+            raise ValueError("p_init must have one row per image")
+        pstart = np.ascontiguousarray(np.stack([_pair(r, npar) for r in pin]))
+    else:
+        pstart = np.ascontiguousarray(np.tile(_pair(pin, npar), (B, 1)))
+    fix = np.atleast_1d(np.asarray(get("fix_p", [False] * npar))).ravel().astype(bool)
+    fix = np.concatenate([fix, np.ones(2 - fix.size, dtype=bool)])
+    ptrue = _pair(get("p_true", pstart[0, :npar]), npar)
+    c_p = _pair(get("c_p", [1.0] * npar), npar)
+    pmin, pmax = get("p_min"), get("p_max")
+    if (pmin is None or pmax is None) and not all(fix[:npar]):
+        raise KeyError("op.p_min and op.p_max are required for a free PSF parameter")
+    pmin = ptrue.copy() if pmin is None else _pair(pmin, npar)
+    pmax = ptrue.copy() if pmax is None else _pair(pmax, npar)
+    for q in range(2):
+        o.fix_p[q] = int(fix[q])
+        o.p_init[q], o.p_true[q], o.p_min[q], o.p_max[q], o.c_p[q] = pstart[0, q], ptrue[q], pmin[q], pmax[q], c_p[q]
+    o.fix_sigma = int(bool(_op(op, "fix_sigma", True)))
+    if o.fix_sigma:
+        o.sigma2_min, o.sigma2_max = float(get("sigma2_min", o.sigma2)), float(get("sigma2_max", o.sigma2))
+        o.c_sigma = float(get("c_sigma", 0.0))
+    else:
+        o.sigma2_min, o.sigma2_max = float(_op(op, "sigma2_min")), float(_op(op, "sigma2_max"))
+        o.c_sigma = float(_op(op, "c_sigma"))
+    S, Wn = o.samples, max(o.warmup, 0)
+    if xw0 is None:
+        xw0 = get("X0")
+    x0i = L.Images(xw0) if xw0 is not None else None
+    if x0i is not None:
+        if (x0i.B, x0i.M, x0i.N) != (B, M, nb * N):
+            raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+        if x0i.flags != yi.flags:
+            raise ValueError("all image arguments must live in the same memory space")
+    nz_keep, nz_ptr = _chain_noise(noise, yi, max(Wn - 1, 0) + S - 1, nb, "max(warmup-1, 0) + samples-1")
+    Sn, Mn = max(S, 1), max(S - o.burnIn, 1)
+    thetas, sigmas, gx, logpi, tol = (np.zeros((B, Sn)) for _ in range(5))
+    ps, tolp, grads = np.zeros((B, 2, Sn)), np.zeros((B, 2, Sn)), np.zeros((B, 3, Sn))
+    logpi_wu = np.zeros((B, max(Wn, 1)))
+    means, meanp = np.zeros((B, Mn)), np.zeros((B, 2, Mn))
+    eb = np.zeros((B, 4))
+    xl = _resized(yi, nb * N)
+    ctx.check(ctx.lib.sbtv_SAPG_wavelet_semiblind(
+        ctx.h, yi.ptr, M, N, B, hp, K, int(levels), C.byref(o), _vp(pstart), x0i.ptr if x0i else None, nz_ptr, _vp(thetas),
+        _vp(ps), _vp(sigmas), _vp(gx), _vp(logpi), _vp(logpi_wu), _vp(grads), _vp(means), _vp(tol), _vp(meanp), _vp(tolp),
+        _vp(eb), xl.ptr, yi.flags), yi.flags)
+    xs = L.images_result(xl, False)
+    nm = max(S - o.burnIn, 0)
+    results = []
+    for b in range(B):
+        r = dict(last_samp=S, logPiTraceX=logpi[b], gXTrace=gx[b], mean_theta=float(eb[b, 0]), last_theta=float(thetas[b, -1]),
+                 thetas=thetas[b], mean_thetas=means[b, :nm], tol_thetas=tol[b], ps=ps[b], sigmas=sigmas[b], grads=grads[b],
+                 mean_ps=meanp[b, :, :nm], tol_ps=tolp[b], p_EB=eb[b, 1:1 + npar].copy(), sigma2_EB=float(eb[b, 3]),
+                 options=op, Xlast_sample=xs[b])
+        if Wn > 0:
+            r["logPiTrace_WU"] = logpi_wu[b, :Wn]
+        results.append(r)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    if sq:
+        return dict(theta=float(eb[0, 0]), p=eb[0, 1:1 + npar].copy(), sigma2=float(eb[0, 3])), results[0]
+    return dict(theta=eb[:, 0].copy(), p=eb[:, 1:1 + npar].copy(), sigma2=eb[:, 3].copy()), results

@@ -4,8 +4,13 @@ empirical-Bayes estimate of theta for the Laplace prior on the coefficients of t
 (`sbtv.SAPG_wavelet`, :125-156) -> MAP image by `sbtv.SALSA_wavelet` at tau = theta_EB sigma^2, mu = theta_EB (:160-185).
 With `--posterior S` also S samples of the posterior at theta_EB (`sbtv.myula_wavelet`, started at the MAP coefficients): the
 MMSE image next to the MAP image, and the per-pixel standard deviation; `--out DIR` is where both are saved (.npy and .pgm).
+With `--semiblind KIND` (gaussian, moffat or laplace) the blur is NOT given to the estimator: the image is blurred with the
+7 x 7 PSF of the family at its true parameters, `sbtv.SAPG_wavelet_semiblind` estimates (theta, p) from one chain with sigma^2
+known, the taps are rebuilt from p_EB, `sbtv.SALSA_wavelet` solves with them, and the estimates are printed next to the
+true values with the PSNR.
 
   python tools/run_wavelet_demo.py [--image tests/golden/man_512.npy] [--samples 3000] [--seed 1] [--posterior S] [--out DIR]
+  python tools/run_wavelet_demo.py --semiblind laplace [--samples 3000] [--seed 1]
 
 Constants follow the script (:65-83,99,106-107,164-166).  The reference's uniform_blur is centred; the library's taps sit in
 the top-left corner (utils/resize.m), which delays the blurred image by 4 pixels in both directions.  The observation is made
@@ -25,6 +30,52 @@ import numpy as np
 import sbtv
 
 
+# --semiblind: true parameters, start values, bounds (run_*_demo.m, as sbtv_oracle.DEMO lists them) and step scales c_p
+SEMIBLIND = {
+    "gaussian": dict(true=(0.4, 0.3), init=(0.7, 0.6), pmin=(0.1, 0.1), pmax=(1.0, 1.0), c_p=(1.0, 1.0)),
+    "moffat": dict(true=(0.4, 3.5), init=(0.6, 3.5), pmin=(1e-2, 0.1), pmax=(1.0, 10.0), c_p=(1.0, 1.0), fix=(False, True)),
+    "laplace": dict(true=(0.3,), init=(0.1,), pmin=(1e-3,), pmax=(1.0,), c_p=(10.0,)),
+}
+
+
+def semiblind(a, x, ctx):
+    """(theta, p) from one chain with sigma^2 known, then the MAP image with the taps of p_EB."""
+    kind, d = a.semiblind, SEMIBLIND[a.semiblind]
+    dimX, t, levels, bsnr = x.size, 7, 4, 30.0
+    rng = np.random.default_rng(a.seed)
+    h = sbtv.daubcqf(2)
+    c = t // 2
+    pad = np.zeros(x.shape)
+    pad[:t, :t] = sbtv.psf_family(kind, t, d["true"])[0]
+    Bx = np.real(np.fft.ifft2(np.fft.fft2(np.roll(pad, (-c, -c), axis=(0, 1))) * np.fft.fft2(x)))    # the centred blur
+    sigma = np.linalg.norm(Bx - Bx.mean()) / math.sqrt(dimX * 10 ** (bsnr / 10))
+    y = Bx + sigma * rng.standard_normal(x.shape)
+    Lf = (1.0 / sigma) ** 2
+    lam = min(5.0 / Lf, 2.0)
+    op = {"samples": a.samples, "burnIn": min(20, a.samples), "th_init": 0.01, "min_th": 1e-3, "max_th": 1.0, "d_exp": 0.8,
+          "d_scale": 0.1 / 0.01, "warmup": 0, "lambda": lam, "gamma": 0.98 / (Lf + 1.0 / lam), "sigma": sigma, "seed": a.seed,
+          "p_init": d["init"], "p_true": d["true"], "p_min": d["pmin"], "p_max": d["pmax"], "c_p": d["c_p"],
+          "fix_p": d.get("fix", (False,) * len(d["true"])), "fix_sigma": True}
+    print(f"image {x.shape}, {kind} PSF {t} x {t} at {d['true']}, sigma {sigma:.4f}, {a.samples} samples from p = {d['init']}")
+    t0 = time.perf_counter()
+    eb, res = sbtv.SAPG_wavelet_semiblind(y, kind, h, levels, op, ctx=ctx)
+    t_eb = time.perf_counter() - t0
+    print(f"theta_EB {eb['theta']:.6g} (last {res['last_theta']:.6g}) in {t_eb:.2f} s")
+    for q, (pe, pt) in enumerate(zip(eb["p"], d["true"])):
+        print(f"p{q}_EB {pe:.6g}   true {pt:.6g}   last {res['ps'][q, -1]:.6g}   last relative change of the mean "
+              f"{res['tol_ps'][q, -1]:.2e}")
+    A = sbtv.BlurOperator(sbtv.psf_family(kind, t, tuple(eb["p"]))[0], ctx=ctx)
+    out = sbtv.SALSA_wavelet(y, A, eb["theta"] * sigma ** 2, "MU", eb["theta"], "WAVELET", h, "LEVELS", levels, "AT", A.T,
+                             "TOLERANCEA", 1e-4, "MAXITERA", 500, "VERBOSE", 0, ctx=ctx)
+    xMAP = np.roll(np.asarray(out[1]), (c, c), axis=(0, 1))              # the taps sit in the top-left corner: roll back
+    At = sbtv.BlurOperator(sbtv.psf_family(kind, t, d["true"])[0], ctx=ctx)
+    ref = sbtv.SALSA_wavelet(y, At, eb["theta"] * sigma ** 2, "MU", eb["theta"], "WAVELET", h, "LEVELS", levels, "AT", At.T,
+                             "TOLERANCEA", 1e-4, "MAXITERA", 500, "VERBOSE", 0, ctx=ctx)
+    xREF = np.roll(np.asarray(ref[1]), (c, c), axis=(0, 1))
+    print(f"SALSA_wavelet with the taps of p_EB: PSNR {sbtv.PSNR(x, xMAP, ctx=ctx):.2f} dB; with the true taps "
+          f"{sbtv.PSNR(x, xREF, ctx=ctx):.2f} dB; observation {sbtv.PSNR(x, y, ctx=ctx):.2f} dB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--image", default=os.path.join(ROOT, "tests", "golden", "man_512.npy"))
@@ -34,8 +85,12 @@ def main():
                     help="after theta_EB, S MYULA samples at theta_EB: MMSE image and standard-deviation map")
     ap.add_argument("--posterior-first", type=int, default=0, help="first iteration used (default: S / 10 + 1)")
     ap.add_argument("--out", default=os.path.join(ROOT, "out"), help="directory for the mean / standard-deviation maps")
+    ap.add_argument("--semiblind", default=None, choices=sorted(SEMIBLIND), metavar="KIND",
+                    help="estimate (theta, p) of this PSF family with sigma^2 known instead of taking the blur as given")
     a = ap.parse_args()
     x = np.load(a.image).astype(np.float64)
+    if a.semiblind:
+        return semiblind(a, x, sbtv.default_context(0))
     dimX = x.size
     rng = np.random.default_rng(a.seed)
     ctx = sbtv.default_context(0)
