@@ -4,7 +4,8 @@ SALSA driver (sbtv_SALSA_wavelet, csrc/admm.hip) against the NumPy restatement (
 Transforms: atol 1e-12 max|x| (about 2 K J roundings of 1.1e-16 per output: under 1e-14 relative); adjoint and Parseval
 identities on the device's own output to 1e-11 relative.  Solver: the bars of tests/test_gpu_admm.py and test_gpu_masked.py
 against the LITERAL SALSA_v2 iteration: same stopping iteration, objective / mses rtol 1e-9, distance rtol 1e-7,
-max |xw - ref| < 1e-7, max |x - W ref| < 1e-7, numA / numAt equal, times[0] == 0 and non-decreasing."""
+max |xw - ref| < 1e-7, max |x - W ref| < 1e-7, numA / numAt equal, times[0] == 0 and non-decreasing.  The length-6 filter
+has instantiations of its own: two transform cases and one chain with moments (sbtv_myula_wavelet) launch them."""
 import numpy as np
 import pytest
 
@@ -27,6 +28,9 @@ TRANSFORM_CASES = [
     ((96, 160), 2, 7, 1),         # s = 32 > 16
     ((160, 96), 4, 6, 2),         # s = 16 > 8, reach 48, a batch
     ((150, 131), 8, 5, 1),        # s = 8 > 4, reach 56, odd sizes
+    # filter length 6: its own instantiations and LDS footprint (runs capped at 4 rows / 2 columns, 84 rows per tile column)
+    ((40, 44), 6, 4, 2),          # reach 20, tiles cut at both edges, a batch
+    ((150, 131), 6, 5, 1),        # s = 8 above both caps, reach 40
 ]
 
 
@@ -211,3 +215,34 @@ def test_solver_takes_device_tensors(ctx):
     np.testing.assert_array_equal(sbtv.to_host(dev[0]), np.asarray(host[0]))
     np.testing.assert_array_equal(sbtv.to_host(dev[1]), np.asarray(host[1]))
     np.testing.assert_array_equal(dev[4], host[4])
+
+
+def test_filter_length_6_chain_and_moments_match_the_restatement(ctx):
+    """sbtv.myula_wavelet with the length-6 filter at 40 x 44, levels 4, four samples with the image and coefficient moments:
+    wav_synthesis_moments_kernel<6> next to the plain length-6 kernels, against tests/wavelet_myula_restatement.py at the bars
+    of tests/test_gpu_wavelet_posterior.py (traces rtol 1e-9, last sample 1e-9 max|X|, _assert_moments)."""
+    import sbtv
+    import wavelet_myula_restatement as wmr
+    import wavelet_sapg_cases as wsc
+    from test_gpu_posterior import _assert_moments
+    M, N, levels, S, theta = 40, 44, 4, 4, 0.03
+    h = sbtv.daubcqf(6)
+    y, sigma, H = wsc._setup(wc.synth_image(M, N, 4), 7, 3)
+    op = wsc.options(sigma, S, 0)
+    nz = np.random.default_rng(26).standard_normal((S - 1, M, wsc.bands(levels) * N))
+    ref = wmr.myula_wavelet_chain(y, H, h, levels, op, theta, op["sigma2"], nz)
+    A = sbtv.BlurOperator(sbtv.psf_family("gaussian", 7, wc.PSF_PARAMS)[0])
+    r = sbtv.myula_wavelet(y, A, h, levels, op, theta=theta, sigma2=op["sigma2"], noise=nz,
+                           posterior=dict(coefficients=True), ctx=ctx)
+    for k, c in (("gXTrace", ref["gx"]), ("logPiTraceX", ref["logpi"])):
+        a = np.asarray(r[k])
+        assert a.shape == c.shape == (S,)
+        print(f"{k}: worst rel {np.max(np.abs(a / c - 1)):.1e}")
+        np.testing.assert_allclose(a, c, rtol=1e-9, atol=0, err_msg=k)
+    xs = float(np.max(np.abs(ref["samples"][-1])))
+    ex = float(np.max(np.abs(np.asarray(r["Xlast_sample"]) - ref["samples"][-1])))
+    print(f"max|X - ref| / max|X| = {ex / xs:.1e}, n = {r['posteriorcount']}")
+    assert ex <= 1e-9 * xs
+    assert r["posteriorcount"] == S
+    _assert_moments(r["posteriormean"], r["posteriorvar"], *wmr.two_pass(ref["images"]))
+    _assert_moments(r["coefmean"], r["coefvar"], *wmr.two_pass(ref["samples"]))
