@@ -371,17 +371,21 @@ class BlurModel:
     `calls_fft` counts 2-D FFTs so the redundancy is visible to the baseline.
     """
 
-    def __init__(self, kind, im_shape, psf_size=7):
+    def __init__(self, kind, im_shape, psf_size=7, phi=0.0):
         self.kind = kind
         self.im_shape = tuple(im_shape)
         self.psf_size = psf_size
+        self.phi = float(phi)                # rotation of the Gaussian's axes (Gaussian_psf.m `phi`); other families ignore it
         self._taps, self._dtaps = PSF_TAPS[kind]
 
+    def _p(self, p):
+        return tuple(p[:2]) + (self.phi,) if self.kind == "gaussian" else p
+
     def taps(self, *p):
-        return self._taps(self.psf_size, p)
+        return self._taps(self.psf_size, self._p(p))
 
     def dtaps(self, i, *p):
-        return self._dtaps[i](self.psf_size, p)
+        return self._dtaps[i](self.psf_size, self._p(p))
 
     def H_FFT(self, *p):
         return resize(self.taps(*p), self.im_shape)
@@ -871,7 +875,7 @@ def SAPG_algorithm(setup, samples, warmup, burnIn, randn, chambolleit=25, p_init
     return dict(theta_EB=float(np.mean(thetas[b0:])), p_EB=[float(np.mean(ps[q, b0:])) for q in range(npar)],
                 sigma_EB=float(np.mean(sigmas[b0:])), thetas=thetas, ps=ps, sigmas=sigmas,
                 logPiTraceX=logPiTraceX, logPiTrace_WU=logPiTrace_WU, gXTrace=gX, grads=grads,
-                Xlast_sample=X, prox_last=prox, err_psf=err_psf_trace(kind, ps, p_true, model.psf_size), X_at=X_at)
+                Xlast_sample=X, prox_last=prox, err_psf=err_psf_trace(kind, ps, p_true, model.psf_size, model.phi), X_at=X_at)
 
 
 def SAPG_algorithm_shared(setup, chains, samples, warmup, burnIn, randn, chambolleit=25, p_init=None, fix=None,
@@ -961,19 +965,23 @@ def SAPG_algorithm_shared(setup, chains, samples, warmup, burnIn, randn, chambol
     b0 = int(burnIn) - 1
     return dict(theta_EB=float(np.mean(thetas[b0:])), p_EB=[float(np.mean(ps[q, b0:])) for q in range(npar)],
                 sigma_EB=float(np.mean(sigmas[b0:])), thetas=thetas, ps=ps, sigmas=sigmas,
-                logPiTraceX=logPiTraceX, gXTrace=gX, grads=grads, Xlast_samples=Xs)
+                logPiTraceX=logPiTraceX, gXTrace=gX, grads=grads, Xlast_samples=Xs,
+                err_psf=err_psf_trace(kind, ps, p_true, model.psf_size, model.phi))
 
 
-def err_psf_trace(kind, ps, p_true, psf_size=7):
+def err_psf_trace(kind, ps, p_true, psf_size=7, phi=0.0):
     """The PSF-tracking trace `results.err_psf`: l2 (squared SPECTRAL norm, quirk Q9) between the PSF at the current
     parameters and the true one.  Per family:
       gaussian  err(1) = l2(psf(w1s(1), w2s(1)), true); err(ii) = l2(psf(w1s(ii), w2s(ii-1)), true)  -- the w2 of the
                 PREVIOUS iteration, quirk Q8 (SAPG_algorithm_Guassian.m:144-146,203-204)
       moffat    the initial value is stored under another name (`psf_err(1)`, SAPG_algorithm_moffat.m:156), so
                 err_psf(1) stays 0; err(ii) = l2(psf(alphas(ii), betas(ii)), true)   (:204-205)
-      laplace   err(ii) = l2(psf(bs(ii)), true) for every ii   (SAPG_algorithm_laplace.m:134-136,190-191)"""
+      laplace   err(ii) = l2(psf(bs(ii)), true) for every ii   (SAPG_algorithm_laplace.m:134-136,190-191)
+    phi rotates both Gaussian PSFs; the other families ignore it."""
     ps = np.atleast_2d(np.asarray(ps, dtype=np.float64))
     builder = PSF_TAPS[kind][0]
+    if kind == "gaussian":
+        builder = lambda t, p: PSF_TAPS[kind][0](t, tuple(p[:2]) + (phi,))
     true = builder(psf_size, tuple(p_true))
     n = ps.shape[1]
     out = np.zeros(n)
