@@ -717,14 +717,15 @@ int wav_synthesis(sbtv_ctx *ctx, const WavPlan &pl, const double *z, double *x, 
 __device__ __forceinline__ double wav_soft(double x, double T) { return copysign(fmax(fabs(x) - T, 0.0), x); }
 // one coefficient of the MYULA step on the frame coefficients (SAPG_algorithm_1.m:133,174 with proxG = soft):
 //     x + gam (soft(x, T) - x) / lamb - gam g / s2 + sqrt(2 gam) z,   T = lamb theta
-// ONE definition for the step kernel of sbtv_SAPG_wavelet and those of sbtv_myula_wavelet, no contraction anywhere in it
+// the element of wav_step_kernel (wavelet_chain.hip), no contraction anywhere in it
 __device__ __forceinline__ double wav_myula_nocontract(double x, double g, double z, double T, double gam, double lamb,
                                                        double s2, double sq2g) {
 #pragma clang fp contract(off)
     return ((x + gam * (wav_soft(x, T) - x) / lamb) - gam * (g / s2)) + sq2g * z;
 }
-// the element-wise passes over the coefficients (wavelet_sapg.hip, wavelet_myula.hip): WAV_EWB lanes per workgroup, at
-// most WAV_EW_MAXBLK workgroups (= partial sums) per chain, a grid-stride loop beyond
+// the element-wise passes over the coefficients (wavelet_chain.hip) and the per-chain kernels of the three chain drivers
+// (update and trace kernels of wavelet_sapg.hip, wavelet_myula.hip, wavelet_sapg_sb.hip): WAV_EWB lanes per workgroup; an
+// element-wise pass has at most WAV_EW_MAXBLK workgroups (= partial sums) per chain, a grid-stride loop beyond
 constexpr int WAV_EWB = 256;
 constexpr int WAV_EW_MAXBLK = 2048;
 inline int wav_ew_blocks(size_t dimX) {
@@ -744,6 +745,68 @@ __device__ __forceinline__ double wav_block_sum(double v, double *red) {
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
+// The theta step of SALSA/SAPG_algorithm_1.m for the update kernels of wavelet_sapg.hip and wavelet_sapg_sb.hip, which
+// store the result into their own traces.  eta / th_cur: eta(ii-1), theta(ii-1); g = ||X(ii)||_1; sum_eta over n_eta terms:
+// the running sum of eta(burnIn:ii-1), which eta(ii) joins when burn (ii >= burnIn).
+struct WavThetaStep {
+    double eta, th;         // eta(ii), theta(ii)
+    double sum_eta, n_eta;  // the running sum with eta(ii)
+    double tol, mean;       // tol_thetas(ii); exp(mean(eta(burnIn:ii))) = mean_thetas(ii - burnIn), NaN over an empty range
+};
+__device__ __forceinline__ WavThetaStep wav_theta_step(double eta, double th_cur, double g, double delta, double dimX,
+                                                       double min_eta, double max_eta, bool burn, double sum_eta,
+                                                       double n_eta) {
+#pragma clang fp contract(off)
+    WavThetaStep t;
+    const double etaii = eta + delta * (dimX / th_cur - g) * exp(eta);           // :180
+    t.eta = fmin(fmax(etaii, min_eta), max_eta);                                 // :181
+    t.th = exp(t.eta);                                                           // :182
+    const double nan = __builtin_nan("");
+    const double m0 = n_eta > 0.0 ? exp(sum_eta / n_eta) : nan;                  // exp(mean(eta(burnIn:ii-1))), empty: NaN
+    t.sum_eta = burn ? sum_eta + t.eta : sum_eta;
+    t.n_eta = burn ? n_eta + 1.0 : n_eta;
+    t.mean = t.n_eta > 0.0 ? exp(t.sum_eta / t.n_eta) : nan;                     // :211
+    t.tol = fabs(t.mean - m0) / m0;                                              // :199-200
+    return t;
+}
+
+// ----------------------------- MYULA chain on the frame coefficients (wavelet_chain.hip) ---------
+// What sbtv_SAPG_wavelet, sbtv_myula_wavelet and sbtv_SAPG_wavelet_semiblind share: the buffers of a chain, its start, the
+// two halves of an operator pass and the step, enqueued on the context's stream.  Device pointers, but `noise`.
+struct WavChain {
+    WavPlan wp;
+    FftPlan fp;
+    int batch, nblk, nrb;        // element-wise workgroups per chain (wav_ew_blocks), row blocks per image (fft_rows_blocks)
+    size_t P, cnt, dimX, ccnt;   // M N, P batch, (3J+1) P, dimX batch
+    const double *yd, *x0d;      // y; the caller's start state or null (W'y)
+    const double *noise;         // injected normals [step][batch][dimX] (host unless Z is null) or null: Philox
+    double *X, *G, *img, *Z;     // state, gradient, image, staging of one step of host noise
+    double2 *S, *Hs, *Ys;        // column spectrum of W X; spectra of the PSF (filled by the caller) and of y
+    double inv_scale;
+};
+// plan, staging of y / xw0 and the workspaces "<prefix>.y", .G, .X, .img, .Z, .S, .H, .Y
+int wav_chain_buffers(sbtv_ctx *ctx, const char *prefix, const WavPlan &wp, int batch, const double *y, const double *xw0,
+                      const double *noise, double *xw_last, int flags, WavChain *c);
+// Ys = spectrum of y; X = xw0 or W'y (run_deblur_synthesis_L1.m:153)
+int wav_chain_start(sbtv_ctx *ctx, const WavChain &c);
+// S = column spectrum of W X; mom with k > 0: the image is sample k of the running moments (wav_synthesis)
+int wav_chain_spectrum(sbtv_ctx *ctx, const WavChain &c, const MomArgs *mom = nullptr);
+// the row pass on S with H, Y and (OP_GRAD only) D1, D2; ||B W X - y||^2 (and the OP_GRAD dot products) -> acc.  OP_RESID and
+// OP_GRAD store nothing; OP_GRADF goes on to G = W' B'(B W X - y)
+int wav_chain_rows(sbtv_ctx *ctx, const WavChain &c, int op, double *acc, const double2 *D1 = nullptr,
+                   const double2 *D2 = nullptr);
+// part [batch][nblk] = partial sums of ||X||_1
+int wav_abs_sum(sbtv_ctx *ctx, const WavChain &c, double *part);
+// where the step reads the two scalars of chain b: theta[b * stride], sigma2[b * stride] (device)
+struct WavStepPar {
+    const double *theta, *sigma2;
+    int stride;
+};
+// One MYULA step of every chain (wav_step_kernel) with the normals of step rng.step: the injected ones, or Philox on (pair,
+// rng.step, rng.chain0 + b).  part [batch][nblk] receives the partial sums of ||X_new||_1; mom with k > 0: X_new is sample k
+// of the running moments of the coefficients.
+int wav_chain_step(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, double gam, double lamb, const RngArgs &rng,
+                   double *part, const MomArgs *mom = nullptr);
 
 #include "psf_taps.inc"   // psf_taps_point(): PSF formulas shared by host and device
 

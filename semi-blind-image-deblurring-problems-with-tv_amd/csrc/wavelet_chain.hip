@@ -1,0 +1,166 @@
+// The MYULA chain on the coefficients of the redundant wavelet frame, as far as its three drivers share it (DESIGN.md
+// §3.9-3.11): sbtv_SAPG_wavelet (wavelet_sapg.hip), sbtv_myula_wavelet (wavelet_myula.hip) and sbtv_SAPG_wavelet_semiblind
+// (wavelet_sapg_sb.hip).  The buffers of a chain, the spectrum of y and the start state, the two halves of an operator pass
+// (synthesis + forward column pass; row pass, and for the gradient the inverse column pass + analysis), and the two
+// element-wise kernels: the library is built without relocatable device code, so a kernel is launched from the unit that
+// defines it and the drivers reach these through the host functions of sbtv_internal.h.  The drivers keep what differs:
+// the order of the passes, where theta and sigma2 live, the update / trace kernels.
+#include <cmath>
+#include <string>
+#include <type_traits>
+
+#include "sbtv_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace sbtv {
+
+namespace {
+
+// ||X||_1 of the start state: partials [batch][gridDim.x]
+__global__ __launch_bounds__(WAV_EWB) void wav_abs_sum_kernel(const double *__restrict__ X, size_t dimX,
+                                                               double *__restrict__ part) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const double *x = X + (size_t)b * dimX;
+    double a = 0.0;
+    for (size_t q = (size_t)blockIdx.x * WAV_EWB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WAV_EWB) {
+        const double2 v = *reinterpret_cast<const double2 *>(x + 2 * q);
+        a += fabs(v.x) + fabs(v.y);
+    }
+    a = wav_block_sum(a, red);
+    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+}
+
+struct WavNoMom {};
+
+// One MYULA step of every chain (SAPG_algorithm_1.m:133,174) on the coefficients, two per lane (dimX is even: an odd pixel
+// count is refused), at the chain's own theta_b / sigma2_b (par):
+//     X = X + gamma (soft(X, lambda theta_b) - X) / lambda - gamma G / sigma2_b + sqrt(2 gamma) Z
+// The prox is never stored: a driver whose theta moves passes the theta the reference formed it with, which lags one
+// iteration.  G = W' B'(B W X - y).  Z: injected normals in the layout of X, or null: pair q of chain b draws
+// philox_normal_pair(q, step, chain0 + b, seed).  X and G are read once, X is written once; part [batch][gridDim.x]
+// receives the workgroup's sum of |X_new|.  MOM: X_new is also sample mom.k of the running mean / M2 of the coefficients;
+// the plain instantiation carries no MomArgs.
+template <bool MOM>
+__global__ __launch_bounds__(WAV_EWB) void wav_step_kernel(double *__restrict__ X, const double *__restrict__ G,
+                                                            const double *__restrict__ Z, WavStepPar par, double gam,
+                                                            double lamb, double sq2g, size_t dimX, RngArgs rng,
+                                                            double *__restrict__ part,
+                                                            std::conditional_t<MOM, MomArgs, WavNoMom> mom) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const size_t base = (size_t)b * dimX, pb = (size_t)b * par.stride;
+    const double T = lamb * par.theta[pb], s2 = par.sigma2[pb];
+    int k = 0;
+    if constexpr (MOM) k = mom.k;
+    const double rk = 1.0 / (double)(k > 0 ? k : 1);
+    double a = 0.0;
+    for (size_t q = (size_t)blockIdx.x * WAV_EWB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WAV_EWB) {
+        const size_t o = base + 2 * q;
+        const double2 xv = *reinterpret_cast<const double2 *>(X + o);
+        const double2 gv = *reinterpret_cast<const double2 *>(G + o);
+        const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
+                             : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
+        double2 r;
+        r.x = wav_myula_nocontract(xv.x, gv.x, zv.x, T, gam, lamb, s2, sq2g);
+        r.y = wav_myula_nocontract(xv.y, gv.y, zv.y, T, gam, lamb, s2, sq2g);
+        *reinterpret_cast<double2 *>(X + o) = r;
+        if constexpr (MOM) {
+            if (k > 0) moments_pair(mom, o, r, k, rk);
+        }
+        a += fabs(r.x) + fabs(r.y);
+    }
+    a = wav_block_sum(a, red);
+    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+}
+
+}  // namespace
+
+int wav_chain_buffers(sbtv_ctx *ctx, const char *prefix, const WavPlan &wp, int batch, const double *y, const double *xw0,
+                      const double *noise, double *xw_last, int flags, WavChain *c) {
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    SBTV_TRY(fft_plan(ctx, wp.M, wp.N, batch, &c->fp));
+    c->wp = wp;
+    c->batch = batch;
+    c->P = (size_t)wp.M * wp.N;
+    c->cnt = c->P * batch;
+    c->dimX = c->P * wp.bands();
+    c->ccnt = c->dimX * batch;
+    c->nblk = wav_ew_blocks(c->dimX);
+    c->nrb = fft_rows_blocks(c->fp);
+    c->inv_scale = 1.0 / ((double)c->fp.n1 * wp.N);
+    c->noise = noise;
+    c->Z = nullptr;
+    const std::string p(prefix);
+    const size_t spec = c->fp.u_img * batch;
+    SBTV_TRY(stage_in(ctx, (p + ".y").c_str(), y, c->cnt, flags, &c->yd));
+    SBTV_TRY(stage_in(ctx, (p + ".G").c_str(), xw0, c->ccnt, flags, &c->x0d));     // staged where the gradient goes later
+    SBTV_TRY(stage_out_buf(ctx, (p + ".X").c_str(), xw_last, c->ccnt, flags, &c->X));
+    SBTV_TRY(ws_get_t(ctx, (p + ".G").c_str(), c->ccnt, &c->G));
+    SBTV_TRY(ws_get_t(ctx, (p + ".img").c_str(), c->cnt, &c->img));
+    if (noise && !(flags & SBTV_DEVICE_PTRS)) SBTV_TRY(ws_get_t(ctx, (p + ".Z").c_str(), c->ccnt, &c->Z));
+    SBTV_TRY(ws_get_t(ctx, (p + ".S").c_str(), (size_t)batch * c->fp.s_img, &c->S));
+    SBTV_TRY(ws_get_t(ctx, (p + ".H").c_str(), spec, &c->Hs));
+    return ws_get_t(ctx, (p + ".Y").c_str(), spec, &c->Ys);
+}
+
+int wav_chain_start(sbtv_ctx *ctx, const WavChain &c) {
+    RowsArgs a{};
+    a.dir_fwd = 1;
+    SBTV_TRY(fft_cols_fwd(ctx, c.fp, c.yd, nullptr, c.S));
+    SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
+    SBTV_TRY(spec_unpack(ctx, c.fp, c.S, c.Ys));
+    if (!c.x0d) return wav_analysis(ctx, c.wp, c.yd, c.X, c.batch);
+    if (c.x0d != c.X) SBTV_HIP(ctx, hipMemcpyAsync(c.X, c.x0d, sizeof(double) * c.ccnt, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+int wav_chain_spectrum(sbtv_ctx *ctx, const WavChain &c, const MomArgs *mom) {
+    SBTV_TRY(wav_synthesis(ctx, c.wp, c.X, c.img, c.batch, mom && mom->k > 0 ? mom : nullptr));
+    return fft_cols_fwd(ctx, c.fp, c.img, nullptr, c.S);
+}
+
+int wav_chain_rows(sbtv_ctx *ctx, const WavChain &c, int op, double *acc, const double2 *D1, const double2 *D2) {
+    RowsArgs ra{};
+    ra.dir_fwd = 1;
+    ra.dir_inv = op == OP_GRADF;
+    ra.op = op;
+    ra.H = c.Hs;
+    ra.Y = c.Ys;
+    ra.D1 = op == OP_GRAD ? D1 : nullptr;
+    ra.D2 = op == OP_GRAD ? D2 : nullptr;
+    ra.acc = acc;
+    SBTV_TRY(fft_rows(ctx, c.fp, c.S, ra.dir_inv ? c.S : nullptr, ra));
+    if (!ra.dir_inv) return 0;
+    SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, c.img, c.inv_scale));
+    return wav_analysis(ctx, c.wp, c.img, c.G, c.batch);
+}
+
+int wav_abs_sum(sbtv_ctx *ctx, const WavChain &c, double *part) {
+    hipLaunchKernelGGL(wav_abs_sum_kernel, dim3(c.nblk, c.batch), dim3(WAV_EWB), 0, ctx->stream, (const double *)c.X, c.dimX,
+                       part);
+    SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int wav_chain_step(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, double gam, double lamb, const RngArgs &rng,
+                   double *part, const MomArgs *mom) {
+    const double *zd = c.noise ? c.noise + (size_t)rng.step * c.ccnt : nullptr;
+    if (c.Z) {
+        SBTV_HIP(ctx, hipMemcpyAsync(c.Z, zd, sizeof(double) * c.ccnt, hipMemcpyHostToDevice, ctx->stream));
+        zd = c.Z;
+    }
+    const dim3 grid(c.nblk, c.batch), block(WAV_EWB);
+    const double sq2g = sqrt(2 * gam);
+    if (mom && mom->k > 0)
+        hipLaunchKernelGGL(wav_step_kernel<true>, grid, block, 0, ctx->stream, c.X, (const double *)c.G, zd, par, gam, lamb,
+                           sq2g, c.dimX, rng, part, *mom);
+    else
+        hipLaunchKernelGGL(wav_step_kernel<false>, grid, block, 0, ctx->stream, c.X, (const double *)c.G, zd, par, gam, lamb,
+                           sq2g, c.dimX, rng, part, WavNoMom{});
+    SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // namespace sbtv

@@ -3,15 +3,15 @@
 // SALSA/SAPG_algorithm_1.m:131-141 with the closures of SALSA/run_deblur_synthesis_L1.m:135-146 (proxG = soft, g = l1,
 // gradF = W' B'(B W xw - y) / sigma2), run at the caller's theta - what a user does with the theta_EB of sbtv_SAPG_wavelet.
 //
-// One iteration is that of wavelet_sapg.hip without the parameter update: J synthesis launches, the FFT triple with OP_GRADF
-// (its Parseval sum is ||B W X - y||^2 of the state BEFORE the step), J analysis launches and one step kernel (the
-// element-wise update of wav_myula_nocontract and the partial sums of |X_new|).  Nothing is reduced per iteration: the row
+// One iteration is that of wavelet_sapg.hip without the parameter update, from the pieces of wavelet_chain.hip: J synthesis
+// launches, the FFT triple with OP_GRADF (its Parseval sum is ||B W X - y||^2 of the state BEFORE the step), J analysis
+// launches and wav_step_kernel (the element-wise update of wav_myula_nocontract and the partial sums of |X_new|).  Nothing is reduced per iteration: the row
 // pass and the step kernel leave their partial sums in a ring of up to WM_RING slots, and wav_myula_trace_kernel turns a full
 // ring into gx / logpi entries in one launch, one workgroup per chain and iteration, every sum in a fixed order.
 //
 // Moments.  The image W X(ii) exists only inside the level-1 synthesis launch of iteration ii + 1 (or of the final residual
 // pass): wav_synthesis_moments_kernel (wavelet.hip) accumulates it there, on the value it is about to store.  The
-// coefficients X(ii) are in registers of the step kernel: wav_myula_moments_kernel accumulates them with moments_pair.
+// coefficients X(ii) are in registers of the step kernel: wav_step_kernel<true> accumulates them with moments_pair.
 // Unselected iterations launch the plain kernels; the chain's bits do not depend on what is accumulated.
 #include <cmath>
 #include <cstring>
@@ -25,7 +25,6 @@ namespace sbtv {
 
 namespace {
 
-constexpr int WMB = WAV_EWB;      // lanes per workgroup of the kernels below
 constexpr int WM_RING = 1024;     // iterations between two trace launches (and two synchronisations)
 
 struct WavMyulaDev {
@@ -37,71 +36,6 @@ struct WavMyulaDev {
     double parseval;
 };
 
-// ||X||_1 of the start state: partials [batch][gridDim.x]
-__global__ __launch_bounds__(WMB) void wav_abs_sum_kernel(const double *__restrict__ X, size_t dimX,
-                                                           double *__restrict__ part) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const double *x = X + (size_t)b * dimX;
-    double a = 0.0;
-    for (size_t q = (size_t)blockIdx.x * WMB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WMB) {
-        const double2 v = *reinterpret_cast<const double2 *>(x + 2 * q);
-        a += fabs(v.x) + fabs(v.y);
-    }
-    a = wav_block_sum(a, red);
-    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
-}
-
-// One MYULA step of every chain at its own theta[b] / sigma2[b] (par), two coefficients per lane (dimX is even):
-//     X = X + gamma (soft(X, lambda theta_b) - X) / lambda - gamma G / sigma2_b + sqrt(2 gamma) Z
-// the expression of wav_myula_kernel (wav_myula_nocontract).  Z: injected normals in the layout of X, or null: pair q of chain
-// b draws philox_normal_pair(q, step, chain0 + b, seed).  X and G are read once, X is written once; part [batch][gridDim.x]
-// receives the workgroup's sum of |X_new|.  MOM: X_new is also sample mom.k of the running mean / M2 of the coefficients.
-template <bool MOM>
-__device__ __forceinline__ void wav_myula_fixed_body(double *__restrict__ X, const double *__restrict__ G,
-                                                     const double *__restrict__ Z, const double *__restrict__ par,
-                                                     int batch, double gam, double lamb, double sq2g, size_t dimX,
-                                                     const RngArgs &rng, double *__restrict__ part, const MomArgs &mom) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const size_t base = (size_t)b * dimX;
-    const double T = lamb * par[b], s2 = par[batch + b];
-    const int k = MOM ? mom.k : 0;
-    const double rk = 1.0 / (double)(k > 0 ? k : 1);
-    double a = 0.0;
-    for (size_t q = (size_t)blockIdx.x * WMB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WMB) {
-        const size_t o = base + 2 * q;
-        const double2 xv = *reinterpret_cast<const double2 *>(X + o);
-        const double2 gv = *reinterpret_cast<const double2 *>(G + o);
-        const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
-                             : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
-        double2 r;
-        r.x = wav_myula_nocontract(xv.x, gv.x, zv.x, T, gam, lamb, s2, sq2g);
-        r.y = wav_myula_nocontract(xv.y, gv.y, zv.y, T, gam, lamb, s2, sq2g);
-        *reinterpret_cast<double2 *>(X + o) = r;
-        if (MOM && k > 0) moments_pair(mom, o, r, k, rk);
-        a += fabs(r.x) + fabs(r.y);
-    }
-    a = wav_block_sum(a, red);
-    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
-}
-
-__global__ __launch_bounds__(WMB) void wav_myula_fixed_kernel(double *__restrict__ X, const double *__restrict__ G,
-                                                               const double *__restrict__ Z,
-                                                               const double *__restrict__ par, int batch, double gam,
-                                                               double lamb, double sq2g, size_t dimX, RngArgs rng,
-                                                               double *__restrict__ part) {
-    wav_myula_fixed_body<false>(X, G, Z, par, batch, gam, lamb, sq2g, dimX, rng, part, MomArgs{});
-}
-
-__global__ __launch_bounds__(WMB) void wav_myula_moments_kernel(double *__restrict__ X, const double *__restrict__ G,
-                                                                 const double *__restrict__ Z,
-                                                                 const double *__restrict__ par, int batch, double gam,
-                                                                 double lamb, double sq2g, size_t dimX, RngArgs rng,
-                                                                 double *__restrict__ part, MomArgs mom) {
-    wav_myula_fixed_body<true>(X, G, Z, par, batch, gam, lamb, sq2g, dimX, rng, part, mom);
-}
-
 // The traces of the iterations ii0, ii0 + 1, ... whose partial sums sit in the ring slots 0, 1, ...: grid (batch, slots), one
 // workgroup per chain and iteration.  Slot s of iteration ii holds R = ||B W X(ii-1) - y||^2 (has_r: the row pass ran before
 // the step) and g = ||X(ii)||_1 (has_g: the step ran):
@@ -109,17 +43,17 @@ __global__ __launch_bounds__(WMB) void wav_myula_moments_kernel(double *__restri
 // gx(ii-1) is summed again from the slot before (the same additions in the same order as the workgroup that stores it), or,
 // for slot 0, read from the trace an earlier launch wrote.  Start state: has_g only (ii0 = 1); final residual: has_r only
 // (ii0 = samples + 1).
-__global__ __launch_bounds__(WMB) void wav_myula_trace_kernel(WavMyulaDev u, int ii0, int has_r, int has_g) {
+__global__ __launch_bounds__(WAV_EWB) void wav_myula_trace_kernel(WavMyulaDev u, int ii0, int has_r, int has_g) {
     __shared__ double red[4];
     const int b = blockIdx.x, s = blockIdx.y, ii = ii0 + s, S = u.samples;
     if (has_r) {
         const double *a = u.acc + ((size_t)s * u.batch + b) * 3 * u.nrb;
         double r = 0.0, gp = 0.0;
-        for (int i = threadIdx.x; i < u.nrb; i += WMB) r += a[i];
+        for (int i = threadIdx.x; i < u.nrb; i += WAV_EWB) r += a[i];
         r = wav_block_sum(r, red);
         if (s > 0) {
             const double *p = u.part + ((size_t)(s - 1) * u.batch + b) * u.nblk;
-            for (int i = threadIdx.x; i < u.nblk; i += WMB) gp += p[i];
+            for (int i = threadIdx.x; i < u.nblk; i += WAV_EWB) gp += p[i];
             gp = wav_block_sum(gp, red);
         } else {
             gp = u.gx[(size_t)b * S + (ii - 2)];
@@ -130,7 +64,7 @@ __global__ __launch_bounds__(WMB) void wav_myula_trace_kernel(WavMyulaDev u, int
     if (has_g) {
         const double *p = u.part + ((size_t)s * u.batch + b) * u.nblk;
         double g = 0.0;
-        for (int i = threadIdx.x; i < u.nblk; i += WMB) g += p[i];
+        for (int i = threadIdx.x; i < u.nblk; i += WAV_EWB) g += p[i];
         g = wav_block_sum(g, red);
         if (threadIdx.x == 0) u.gx[(size_t)b * S + (ii - 1)] = g;
     }
@@ -207,27 +141,12 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
     }
     const bool mom_img = selp && post_mean, mom_coef = selp && coef_mean;
 
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    FftPlan fp;
-    SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
-    const size_t spec = fp.u_img;
-    const int nblk = wav_ew_blocks(dimX), nrb = fft_rows_blocks(fp);
+    WavChain wc;
+    SBTV_TRY(wav_chain_buffers(ctx, "wmy", wp, batch, y, xw0, noise, xw_last, flags, &wc));
+    const int nblk = wc.nblk, nrb = wc.nrb;
     const int ring = samples - 1 < WM_RING ? samples - 1 : WM_RING;
-    const bool noise_host = noise && !dev;
-
-    const double *yd = nullptr, *x0d = nullptr;
-    SBTV_TRY(stage_in(ctx, "wmy.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "wmy.G", xw0, ccnt, flags, &x0d));               // staged where the gradient goes later
-    double *X = nullptr, *G = nullptr, *img = nullptr, *Z = nullptr, *par = nullptr, *taps_d = nullptr, *acc = nullptr,
-           *part = nullptr, *tr_d = nullptr, *im_mean = nullptr, *im_m2 = nullptr, *c_mean = nullptr, *c_m2 = nullptr;
-    double2 *S = nullptr, *Hs = nullptr, *Ys = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "wmy.X", xw_last, ccnt, flags, &X));
-    SBTV_TRY(ws_get_t(ctx, "wmy.G", ccnt, &G));
-    SBTV_TRY(ws_get_t(ctx, "wmy.img", cnt, &img));
-    if (noise_host) SBTV_TRY(ws_get_t(ctx, "wmy.Z", ccnt, &Z));
-    SBTV_TRY(ws_get_t(ctx, "wmy.S", (size_t)batch * fp.s_img, &S));
-    SBTV_TRY(ws_get_t(ctx, "wmy.H", spec * batch, &Hs));
-    SBTV_TRY(ws_get_t(ctx, "wmy.Y", spec * batch, &Ys));
+    double *X = wc.X, *par = nullptr, *taps_d = nullptr, *acc = nullptr, *part = nullptr, *tr_d = nullptr, *im_mean = nullptr,
+           *im_m2 = nullptr, *c_mean = nullptr, *c_m2 = nullptr;
     SBTV_TRY(ws_get_t(ctx, "wmy.acc", (size_t)ring * batch * 3 * nrb, &acc));
     SBTV_TRY(ws_get_t(ctx, "wmy.part", (size_t)ring * batch * nblk, &part));
     const size_t t2b = (size_t)taille * taille * batch, npar = 2 * (size_t)batch + t2b;
@@ -259,77 +178,42 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
         SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));                    // the staging vector goes out of scope
     }
-    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
-    {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, yd, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(spec_unpack(ctx, fp, S, Ys));
-    }
-    if (x0d) {
-        if (x0d != X) SBTV_HIP(ctx, hipMemcpyAsync(X, x0d, sizeof(double) * ccnt, hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-        SBTV_TRY(wav_analysis(ctx, wp, yd, X, batch));                       // X(1) = W'y  (run_deblur_synthesis_L1.m:153)
-    }
-    const dim3 grid(nblk, batch);
-    hipLaunchKernelGGL(wav_abs_sum_kernel, grid, dim3(WMB), 0, ctx->stream, (const double *)X, dimX, part);
-    hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, 1), dim3(WMB), 0, ctx->stream, u, 1, 0, 1);        // gx(1)
-    SBTV_HIP(ctx, hipGetLastError());
+    SBTV_TRY(psf_spectrum(ctx, wc.fp, taps_d, taille, wc.Hs));
+    SBTV_TRY(wav_chain_start(ctx, wc));
+    // the traces of `slots` ring slots, the first of them iteration ii0
+    auto trace = [&](int slots, int ii0, int has_r, int has_g) -> int {
+        hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, slots), dim3(WAV_EWB), 0, ctx->stream, u, ii0, has_r, has_g);
+        SBTV_HIP(ctx, hipGetLastError());
+        return 0;
+    };
+    SBTV_TRY(wav_abs_sum(ctx, wc, part));
+    SBTV_TRY(trace(1, 1, 0, 1));                                             // gx(1)
     if (mom_coef && mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, X, c_mean, c_m2, dimX, batch));        // iteration 1
 
-    const double inv_scale = 1.0 / ((double)fp.n1 * N), gam = op->gamma, lamb = op->lambda, sq2g = sqrt(2 * gam);
-    RowsArgs ra{};
-    ra.dir_fwd = 1;
-    ra.H = Hs;
-    ra.Y = Ys;
-    // W' B'(B W X - y) -> G and ||B W X - y||^2 -> the slot's accumulators, or (resid_only) the sum alone; X is sample
-    // number `of` of the chain: its image is accumulated while the level-1 synthesis stores it
-    auto operator_pass = [&](bool resid_only, int slot, int of) -> int {
+    const WavStepPar sp{par, par + batch, 1};
+    // W' B'(B W X - y) -> G and ||B W X - y||^2 -> the slot's accumulators (OP_GRADF), or the sum alone (OP_RESID); X is
+    // sample number `of` of the chain: its image is accumulated while the level-1 synthesis stores it
+    auto operator_pass = [&](int rows_op, int slot, int of) -> int {
         const MomArgs ma{im_mean, im_m2, mom_img ? mom_sample_of(selp, of) : 0, nullptr, 1, 1};
-        SBTV_TRY(wav_synthesis(ctx, wp, X, img, batch, ma.k > 0 ? &ma : nullptr));
-        SBTV_TRY(fft_cols_fwd(ctx, fp, img, nullptr, S));
-        ra.dir_inv = resid_only ? 0 : 1;
-        ra.op = resid_only ? OP_RESID : OP_GRADF;
-        ra.acc = acc + (size_t)slot * batch * 3 * nrb;
-        SBTV_TRY(fft_rows(ctx, fp, S, resid_only ? nullptr : S, ra));
-        if (resid_only) return 0;
-        SBTV_TRY(fft_cols_inv(ctx, fp, S, img, inv_scale));
-        return wav_analysis(ctx, wp, img, G, batch);
+        SBTV_TRY(wav_chain_spectrum(ctx, wc, &ma));
+        return wav_chain_rows(ctx, wc, rows_op, acc + (size_t)slot * batch * 3 * nrb);
     };
     int filled = 0;                                                          // ring slots waiting for the trace kernel
     for (int ii = 2; ii <= samples; ++ii) {                                  // SAPG_algorithm_1.m:131-141 at theta_b
-        const size_t step = (size_t)(ii - 2);
         const int slot = filled;
-        SBTV_TRY(operator_pass(false, slot, ii - 1));
-        const double *zd = nullptr;
-        if (noise_host) {
-            SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * ccnt, sizeof(double) * ccnt, hipMemcpyHostToDevice, ctx->stream));
-            zd = Z;
-        } else if (noise) {
-            zd = noise + step * ccnt;
-        }
-        const RngArgs r{op->seed, (unsigned)step, (unsigned)op->chain_offset, nullptr};
-        double *pslot = part + (size_t)slot * batch * nblk;
+        SBTV_TRY(operator_pass(OP_GRADF, slot, ii - 1));
+        const RngArgs r{op->seed, (unsigned)(ii - 2), (unsigned)op->chain_offset, nullptr};
         const MomArgs mc{c_mean, c_m2, mom_coef ? mom_sample_of(selp, ii) : 0, nullptr, 1, 1};
-        if (mc.k > 0)
-            hipLaunchKernelGGL(wav_myula_moments_kernel, grid, dim3(WMB), 0, ctx->stream, X, (const double *)G, zd,
-                               (const double *)par, batch, gam, lamb, sq2g, dimX, r, pslot, mc);
-        else
-            hipLaunchKernelGGL(wav_myula_fixed_kernel, grid, dim3(WMB), 0, ctx->stream, X, (const double *)G, zd,
-                               (const double *)par, batch, gam, lamb, sq2g, dimX, r, pslot);
-        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_TRY(wav_chain_step(ctx, wc, sp, op->gamma, op->lambda, r, part + (size_t)slot * batch * nblk, &mc));
         ctx->calls += 2 * (long long)batch;
         if (++filled == ring || ii == samples) {
-            hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, filled), dim3(WMB), 0, ctx->stream, u, ii - filled + 1, 1, 1);
-            SBTV_HIP(ctx, hipGetLastError());
+            SBTV_TRY(trace(filled, ii - filled + 1, 1, 1));
             if (filled == WM_RING) SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
             filled = 0;
         }
     }
-    SBTV_TRY(operator_pass(true, 0, samples));                               // the residual (and the image) of the last sample
-    hipLaunchKernelGGL(wav_myula_trace_kernel, dim3(batch, 1), dim3(WMB), 0, ctx->stream, u, samples + 1, 1, 0);
-    SBTV_HIP(ctx, hipGetLastError());
+    SBTV_TRY(operator_pass(OP_RESID, 0, samples));                           // the residual (and the image) of the last sample
+    SBTV_TRY(trace(1, samples + 1, 1, 0));
     ctx->calls += batch;
 
     if (selp) {

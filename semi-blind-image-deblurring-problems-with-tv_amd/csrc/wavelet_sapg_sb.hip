@@ -8,8 +8,8 @@
 // The loop is device-resident.  One iteration ii (launch list of csrc/sapg.hip's device loop, on the coefficients):
 //   row pass OP_GRADF on the column spectrum S of W X that the previous iteration left, with H of p(ii-1); inverse column
 //     pass; J analysis launches -> G = W' B'(B W X - y)
-//   wav_sb_step_kernel: the step of wav_myula_kernel (wav_myula_nocontract), sigma2(ii-1) and the lagging theta read from the
-//     chain block in device memory; partial sums of |X_new|
+//   wav_step_kernel (wavelet_chain.hip, which holds what the three chain drivers share): sigma2(ii-1) and the lagging theta
+//     read from the chain block in device memory; partial sums of |X_new|
 //   J synthesis launches, forward column pass -> S; row pass OP_GRAD without store, H / D1 / D2 of p(ii-1): ||B W X - y||^2
 //     and the two <dB W X, r> sums of the NEW sample per row block.  The residual of sample ii is known in iteration ii:
 //     no log-density is completed late, the last sample needs no extra pass.
@@ -30,7 +30,6 @@ namespace sbtv {
 
 namespace {
 
-constexpr int WBB = WAV_EWB;      // lanes per workgroup of the kernels below
 constexpr int WB_TMAX = 15 * 15;  // taps of the largest mask (one lane each in the update kernel)
 
 // what the update kernel keeps per chain between two iterations
@@ -54,7 +53,7 @@ struct WavSbTraces {
 
 struct WavSbDev {
     WavSbChain *chain;           // [batch]
-    const double *part;          // [batch][nblk] partial sums of |X_new| (wav_sb_step_kernel / wav_sb_l1_kernel)
+    const double *part;          // [batch][nblk] partial sums of |X_new| (wav_chain_step / wav_abs_sum)
     const double *acc;           // [batch][3][nrb] accumulators of the OP_GRAD row pass (unscaled)
     double *par;                 // [taps | d0 | d1], each [batch][taille^2]
     int nblk, nrb, samples, warmup, wstride, burnIn;
@@ -67,77 +66,32 @@ struct WavSbDev {
 
 enum { WB_PH_START = 0, WB_PH_WARMUP = 1, WB_PH_MAIN = 2 };
 
-// ||X||_1 of the start state: partials [batch][gridDim.x]
-__global__ __launch_bounds__(WBB) void wav_sb_l1_kernel(const double *__restrict__ X, size_t dimX,
-                                                         double *__restrict__ part) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const double *x = X + (size_t)b * dimX;
-    double a = 0.0;
-    for (size_t q = (size_t)blockIdx.x * WBB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WBB) {
-        const double2 v = *reinterpret_cast<const double2 *>(x + 2 * q);
-        a += fabs(v.x) + fabs(v.y);
-    }
-    a = wav_block_sum(a, red);
-    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
-}
-
-// One MYULA step of every chain (SAPG_algorithm_1.m:133,174), two coefficients per lane: the step of wav_myula_kernel
-// (csrc/wavelet_sapg.hip) through the shared wav_myula_nocontract, with sigma2(ii-1) read from the chain block next to the
-// lagging theta, because sigma2 moves here.  G = W' B_p'(B_p W X - y); Z: injected normals or null (Philox, the counters of
-// sbtv_SAPG_wavelet).  part [batch][gridDim.x] receives the workgroup's sum of |X_new|.
-__global__ __launch_bounds__(WBB) void wav_sb_step_kernel(double *__restrict__ X, const double *__restrict__ G,
-                                                           const double *__restrict__ Z,
-                                                           const WavSbChain *__restrict__ chain, double gam, double lamb,
-                                                           double sq2g, size_t dimX, RngArgs rng,
-                                                           double *__restrict__ part) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    const size_t base = (size_t)b * dimX;
-    const double T = lamb * chain[b].th_prev, s2 = chain[b].sig2;
-    double a = 0.0;
-    for (size_t q = (size_t)blockIdx.x * WBB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WBB) {
-        const size_t o = base + 2 * q;
-        const double2 xv = *reinterpret_cast<const double2 *>(X + o);
-        const double2 gv = *reinterpret_cast<const double2 *>(G + o);
-        const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
-                             : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
-        double2 r;
-        r.x = wav_myula_nocontract(xv.x, gv.x, zv.x, T, gam, lamb, s2, sq2g);
-        r.y = wav_myula_nocontract(xv.y, gv.y, zv.y, T, gam, lamb, s2, sq2g);
-        *reinterpret_cast<double2 *>(X + o) = r;
-        a += fabs(r.x) + fabs(r.y);
-    }
-    a = wav_block_sum(a, red);
-    if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
-}
-
 // mean of a running sum; NaN for an empty window, like MATLAB's mean of an empty range
 __device__ __forceinline__ double wb_mean(double s, double n) { return n > 0.0 ? s / n : __builtin_nan(""); }
 
 // End of an iteration, one workgroup per chain.  The OP_GRAD row pass has left, per row block, ||B W X - y||^2 and the two
 // <dB/dp_q W X, B W X - y> sums of the sample the step kernel just wrote (PSF parameters p(ii-1)); the step kernel (or
-// wav_sb_l1_kernel for the start state) has left the partial sums of |X|.  All four are summed here in a fixed order.
+// wav_abs_sum for the start state) has left the partial sums of |X|.  All four are summed here in a fixed order.
 //   WB_PH_START : logpi(1) of the start state                                                  (SAPG_algorithm_1.m:166)
 //   WB_PH_WARMUP: logpi_wu(ii) (:136), and logpi(1) again: the last warm-up sample is the start of the main loop
 //   WB_PH_MAIN  : iteration ii: eta / theta (:180-182), p (:185-186, SAPG_algorithm_laplace.m:172-178), sigma2
 //                 (SAPG_algorithm_laplace.m:181-186), logpi / gx (:190-191), tol / mean entries (:199-213); at ii = samples
 //                 the EB estimates (:226,236); with a free PSF parameter the taps and derivative taps of p(ii)
-__global__ __launch_bounds__(WBB) void wav_sb_update_kernel(WavSbDev u, int phase, int ii, double delta) {
+__global__ __launch_bounds__(WAV_EWB) void wav_sb_update_kernel(WavSbDev u, int phase, int ii, double delta) {
     __shared__ double red[4];
     __shared__ double sf[WB_TMAX], se0[WB_TMAX], se1[WB_TMAX], spar[3], ssum[3];
     const int b = blockIdx.x, S = u.samples, tid = threadIdx.x;
     const double *acc = u.acc + (size_t)b * 3 * u.nrb;
     double r = 0.0, d0 = 0.0, d1 = 0.0, g = 0.0;
-    for (int i = tid; i < u.nrb; i += WBB) r += acc[i];
+    for (int i = tid; i < u.nrb; i += WAV_EWB) r += acc[i];
     r = wav_block_sum(r, red);
-    for (int i = tid; i < u.nblk; i += WBB) g += u.part[(size_t)b * u.nblk + i];
+    for (int i = tid; i < u.nblk; i += WAV_EWB) g += u.part[(size_t)b * u.nblk + i];
     g = wav_block_sum(g, red);
     if (phase == WB_PH_MAIN) {
-        for (int i = tid; i < u.nrb; i += WBB) d0 += acc[u.nrb + i];
+        for (int i = tid; i < u.nrb; i += WAV_EWB) d0 += acc[u.nrb + i];
         d0 = wav_block_sum(d0, red);
         if (u.npar > 1) {
-            for (int i = tid; i < u.nrb; i += WBB) d1 += acc[2 * (size_t)u.nrb + i];
+            for (int i = tid; i < u.nrb; i += WAV_EWB) d1 += acc[2 * (size_t)u.nrb + i];
             d1 = wav_block_sum(d1, red);
         }
     }
@@ -153,9 +107,8 @@ __global__ __launch_bounds__(WBB) void wav_sb_update_kernel(WavSbDev u, int phas
             const size_t o = (size_t)b * S, i0 = (size_t)ii - 1;
             u.tr.logpi[o + i0] = lp;                                                                      // :190
             u.tr.gx[o + i0 - 1] = g;                                                                      // :191
-            const double etaii = c.eta + delta * (u.dimX / c.th_cur - g) * exp(c.eta);                    // :180
-            const double eta = fmin(fmax(etaii, u.min_eta), u.max_eta);                                   // :181
-            const double th = exp(eta);                                                                   // :182
+            const WavThetaStep t = wav_theta_step(c.eta, c.th_cur, g, delta, u.dimX, u.min_eta, u.max_eta, ii >= u.burnIn,
+                                                  c.sum_eta, c.n_sum);                            // :180-182,199-211
             // op.grad_t of the two PSF parameters and the sigma2 gradient (SAPG_algorithm_laplace.m:170,181)
             const double G0 = u.g0_scale * ((d0 * u.parseval) / s);
             const double G1 = u.npar > 1 ? (d1 * u.parseval) / s : 0.0;
@@ -169,36 +122,35 @@ __global__ __launch_bounds__(WBB) void wav_sb_update_kernel(WavSbDev u, int phas
             }
             double sn = u.fix_sigma ? u.sigma2_init : s + u.c_sigma * delta * Gs;
             sn = fmin(fmax(sn, u.s_lo), u.s_hi);
-            u.tr.thetas[o + i0] = th;
+            u.tr.thetas[o + i0] = t.th;
             u.tr.sigmas[o + i0] = sn;
             u.tr.ps[2 * o + i0] = q0;
             u.tr.ps[2 * o + S + i0] = q1;
             u.tr.grads[3 * o + i0] = G0;
             u.tr.grads[3 * o + S + i0] = G1;
             u.tr.grads[3 * o + 2 * (size_t)S + i0] = Gs;
-            // relative change of the running means (:199-205) and the means themselves (:209-213)
-            const double m0 = c.n_sum > 0.0 ? exp(c.sum_eta / c.n_sum) : __builtin_nan("");
+            // relative change of the running means (:199-205) and the means themselves (:209-213); the theta step has
+            // counted the terms of all four sums
             const double a00 = wb_mean(c.sum_p0, c.n_sum), a10 = wb_mean(c.sum_p1, c.n_sum);
+            c.sum_eta = t.sum_eta;
+            c.n_sum = t.n_eta;
             if (ii >= u.burnIn) {
-                c.sum_eta += eta;
                 c.sum_p0 += q0;
                 c.sum_p1 += q1;
                 c.sum_s += sn;
-                c.n_sum += 1.0;
             }
-            const double m1 = c.n_sum > 0.0 ? exp(c.sum_eta / c.n_sum) : __builtin_nan("");
             const double a01 = wb_mean(c.sum_p0, c.n_sum), a11 = wb_mean(c.sum_p1, c.n_sum);
-            u.tr.tol_th[o + i0] = fabs(m1 - m0) / m0;
+            u.tr.tol_th[o + i0] = t.tol;
             u.tr.tol_ps[2 * o + i0] = fabs(a01 - a00) / a00;
             if (u.npar > 1) u.tr.tol_ps[2 * o + S + i0] = fabs(a11 - a10) / a10;
             if (ii > u.burnIn) {
-                u.tr.mean_th[o + (ii - u.burnIn - 1)] = m1;
+                u.tr.mean_th[o + (ii - u.burnIn - 1)] = t.mean;
                 u.tr.mean_ps[2 * o + (ii - u.burnIn - 1)] = a01;
                 if (u.npar > 1) u.tr.mean_ps[2 * o + S + (ii - u.burnIn - 1)] = a11;
             }
-            c.eta = eta;
+            c.eta = t.eta;
             c.th_prev = c.th_cur;
-            c.th_cur = th;
+            c.th_cur = t.th;
             c.p0 = q0;
             c.p1 = q1;
             c.sig2 = sn;
@@ -312,40 +264,26 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
             if (!(pinit[2 * (size_t)b + q] == pt)) params_move = true;
     }
 
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    FftPlan fp;
-    SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
+    WavChain wc;
+    SBTV_TRY(wav_chain_buffers(ctx, "wsb", wp, batch, y, xw0, noise, xw_last, flags, &wc));
     const int samples = op->samples, warmup = op->warmup, wsteps = warmup > 0 ? warmup - 1 : 0, wstride = warmup > 0 ? warmup : 1;
-    const size_t P = (size_t)M * N, cnt = P * batch, dimX = P * wp.bands(), ccnt = dimX * batch, spec = fp.u_img;
-    const int nblk = wav_ew_blocks(dimX), nrb = fft_rows_blocks(fp);
-    const bool noise_host = noise && !(flags & SBTV_DEVICE_PTRS);
-
-    const double *yd = nullptr, *x0d = nullptr;
-    SBTV_TRY(stage_in(ctx, "wsb.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "wsb.G", xw0, ccnt, flags, &x0d));                // staged where the gradient goes later
-    double *X = nullptr, *G = nullptr, *img = nullptr, *Z = nullptr, *acc = nullptr, *part = nullptr, *tr_d = nullptr;
-    double2 *S = nullptr, *Hs = nullptr, *D1s = nullptr, *D2s = nullptr, *Ys = nullptr;
+    const size_t P = wc.P, dimX = wc.dimX, ccnt = wc.ccnt, spec = wc.fp.u_img;
+    double *X = wc.X, *acc = nullptr, *part = nullptr, *tr_d = nullptr;
+    double2 *D1s = nullptr, *D2s = nullptr;
     WavSbDev u{};
-    SBTV_TRY(stage_out_buf(ctx, "wsb.X", xw_last, ccnt, flags, &X));
-    SBTV_TRY(ws_get_t(ctx, "wsb.G", ccnt, &G));
-    SBTV_TRY(ws_get_t(ctx, "wsb.img", cnt, &img));
-    if (noise_host) SBTV_TRY(ws_get_t(ctx, "wsb.Z", ccnt, &Z));
-    SBTV_TRY(ws_get_t(ctx, "wsb.S", (size_t)batch * fp.s_img, &S));
-    SBTV_TRY(ws_get_t(ctx, "wsb.H", spec * batch, &Hs));
     SBTV_TRY(ws_get_t(ctx, "wsb.D1", spec * batch, &D1s));
     // a one-parameter PSF (Laplace) has one derivative spectrum: the second one the row pass reads IS the first (sapg.hip)
     if (npar > 1) SBTV_TRY(ws_get_t(ctx, "wsb.D2", spec * batch, &D2s));
     else D2s = D1s;
-    SBTV_TRY(ws_get_t(ctx, "wsb.Y", spec * batch, &Ys));
-    SBTV_TRY(ws_get_t(ctx, "wsb.acc", (size_t)batch * 3 * nrb, &acc));
-    SBTV_TRY(ws_get_t(ctx, "wsb.part", (size_t)batch * nblk, &part));
+    SBTV_TRY(ws_get_t(ctx, "wsb.acc", (size_t)batch * 3 * wc.nrb, &acc));
+    SBTV_TRY(ws_get_t(ctx, "wsb.part", (size_t)batch * wc.nblk, &part));
     SBTV_TRY(ws_get_t(ctx, "wsb.par", 3 * t2 * batch, &u.par));
     SBTV_TRY(ws_get_t(ctx, "wsb.chain", (size_t)batch, &u.chain));
     const size_t bs = (size_t)batch * samples, trlen = 15 * bs + (size_t)batch * wstride;
     SBTV_TRY(ws_get_t(ctx, "wsb.traces", trlen, &tr_d));
     u.tr = WavSbTraces{tr_d,          tr_d + bs,     tr_d + 2 * bs, tr_d + 3 * bs,  tr_d + 4 * bs, tr_d + 5 * bs,
                        tr_d + 6 * bs, tr_d + 8 * bs, tr_d + 10 * bs, tr_d + 12 * bs, tr_d + 15 * bs};
-    u.part = part; u.acc = acc; u.nblk = nblk; u.nrb = nrb; u.samples = samples; u.warmup = warmup; u.wstride = wstride;
+    u.part = part; u.acc = acc; u.nblk = wc.nblk; u.nrb = wc.nrb; u.samples = samples; u.warmup = warmup; u.wstride = wstride;
     u.burnIn = op->burnIn; u.kind = op->kind; u.taille = taille; u.npar = npar; u.params_move = params_move ? 1 : 0;
     u.fix_p0 = fixq[0] ? 1 : 0; u.fix_p1 = fixq[1] ? 1 : 0; u.fix_sigma = op->fix_sigma ? 1 : 0;
     u.parseval = 1.0 / ((double)M * N); u.dimX = (double)dimX; u.npix = (double)P;
@@ -374,72 +312,32 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
         SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
     }
     const double *tp[3] = {u.par, u.par + t2 * batch, u.par + 2 * t2 * batch};
-    double2 *up[3] = {Hs, D1s, D2s};
-    auto spectra = [&]() -> int { return psf_spectrum_sets(ctx, fp, tp, taille, up, npar > 1 ? 3 : 2); };
+    double2 *up[3] = {wc.Hs, D1s, D2s};
+    auto spectra = [&]() -> int { return psf_spectrum_sets(ctx, wc.fp, tp, taille, up, npar > 1 ? 3 : 2); };
     SBTV_TRY(spectra());
-    {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, yd, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(spec_unpack(ctx, fp, S, Ys));
-    }
-    if (x0d) {
-        if (x0d != X) SBTV_HIP(ctx, hipMemcpyAsync(X, x0d, sizeof(double) * ccnt, hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-        SBTV_TRY(wav_analysis(ctx, wp, yd, X, batch));                       // op.X0 = WT(y)  (run_deblur_synthesis_L1.m:153)
-    }
-    const dim3 grid(nblk, batch);
-    const double inv_scale = 1.0 / ((double)fp.n1 * N), gam = op->gamma, lamb = op->lambda, sq2g = sqrt(2 * gam);
-    RowsArgs ra{};
-    ra.dir_fwd = 1;
-    ra.H = Hs;
-    ra.Y = Ys;
-    ra.acc = acc;
+    SBTV_TRY(wav_chain_start(ctx, wc));
     // S = column spectrum of W X, then the row pass without store: ||B W X - y||^2 and <dB/dp_q W X, B W X - y> -> acc
     auto residual_pass = [&]() -> int {
-        SBTV_TRY(wav_synthesis(ctx, wp, X, img, batch));
-        SBTV_TRY(fft_cols_fwd(ctx, fp, img, nullptr, S));
-        ra.dir_inv = 0;
-        ra.op = OP_GRAD;
-        ra.D1 = D1s;
-        ra.D2 = D2s;
-        return fft_rows(ctx, fp, S, nullptr, ra);
-    };
-    // G = W' B'(B W X - y) from the column spectrum in S, with the current H
-    auto gradient_pass = [&]() -> int {
-        ra.dir_inv = 1;
-        ra.op = OP_GRADF;
-        ra.D1 = nullptr;
-        ra.D2 = nullptr;
-        SBTV_TRY(fft_rows(ctx, fp, S, S, ra));
-        SBTV_TRY(fft_cols_inv(ctx, fp, S, img, inv_scale));
-        return wav_analysis(ctx, wp, img, G, batch);
+        SBTV_TRY(wav_chain_spectrum(ctx, wc));
+        return wav_chain_rows(ctx, wc, OP_GRAD, acc, D1s, D2s);
     };
     auto update = [&](int phase, int ii, double delta) -> int {
-        hipLaunchKernelGGL(wav_sb_update_kernel, dim3(batch), dim3(WBB), 0, ctx->stream, u, phase, ii, delta);
+        hipLaunchKernelGGL(wav_sb_update_kernel, dim3(batch), dim3(WAV_EWB), 0, ctx->stream, u, phase, ii, delta);
         SBTV_HIP(ctx, hipGetLastError());
         return 0;
     };
     // the start state: its spectrum for the first gradient pass, logpi(1) (:166)
     SBTV_TRY(residual_pass());
-    hipLaunchKernelGGL(wav_sb_l1_kernel, grid, dim3(WBB), 0, ctx->stream, (const double *)X, dimX, part);
+    SBTV_TRY(wav_abs_sum(ctx, wc, part));
     SBTV_TRY(update(WB_PH_START, 1, 0.0));
     ctx->calls += batch;
+    // the lagging theta and sigma2(ii-1) of chain b, where the update kernel keeps them
+    const WavStepPar sp{&u.chain->th_prev, &u.chain->sig2, (int)(sizeof(WavSbChain) / sizeof(double))};
     // MYULA step number `step` of the call (warm-up steps first, as the noise array is laid out) and its update
     auto iteration = [&](size_t step, int phase, int ii) -> int {
-        SBTV_TRY(gradient_pass());
-        const double *zd = nullptr;
-        if (noise_host) {
-            SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * ccnt, sizeof(double) * ccnt, hipMemcpyHostToDevice, ctx->stream));
-            zd = Z;
-        } else if (noise) {
-            zd = noise + step * ccnt;
-        }
+        SBTV_TRY(wav_chain_rows(ctx, wc, OP_GRADF, acc));                     // G from the column spectrum in S, with the current H
         const RngArgs r{op->seed, (unsigned)step, (unsigned)op->chain_offset, nullptr};
-        hipLaunchKernelGGL(wav_sb_step_kernel, grid, dim3(WBB), 0, ctx->stream, X, (const double *)G, zd,
-                           (const WavSbChain *)u.chain, gam, lamb, sq2g, dimX, r, part);
-        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_TRY(wav_chain_step(ctx, wc, sp, op->gamma, op->lambda, r, part));
         SBTV_TRY(residual_pass());
         // delta(ii) of :111
         const double delta = phase == WB_PH_MAIN ? op->d_scale * (pow((double)ii, -op->d_exp) / (double)dimX) : 0.0;

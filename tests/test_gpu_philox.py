@@ -1,6 +1,7 @@
-"""GPU: the device generator philox_normal_pair (csrc/sbtv_internal.h) at each of its six call sites against the NumPy
-restatement tests/philox_restatement.py, which tests/test_philox_cpu.py anchors to the known answers of Philox4x32-10.  The
-contract of include/sbtv.h: pair q of chain b in step s draws counter (q, s, chain_offset + b) with key seed, and fills doubles
+"""GPU: the device generator philox_normal_pair (csrc/sbtv_internal.h) at each of its four call sites (the wavelet step kernel
+through both of its instantiations and from each of its three drivers) against the NumPy restatement
+tests/philox_restatement.py, which tests/test_philox_cpu.py anchors to the known answers of Philox4x32-10.  The contract of
+include/sbtv.h: pair q of chain b in step s draws counter (q, s, chain_offset + b) with key seed, and fills doubles
 2q, 2q + 1 of the chain's state.
 
 (a), (b) One step with the generator and the same step with injected zeros give the normals back:
@@ -13,9 +14,10 @@ A wrong counter word is off by O(1) on almost every element.  Worst ratio to the
     fused epilogue 1024 x 2048 and 2048 x 1024          0.161
     myula_step_kernel 64 x 32 / 100 x 90                0.179 / 0.170
     myula_plain_kernel 64 x 32                          0.103
-    wav_myula_kernel 34 x 30 / 512 x 256                0.139 / 0.112
-    wav_myula_fixed_kernel / wav_myula_moments_kernel   0.139 / 0.139
-    wav_sb_step_kernel, all fixed / sigma2 free         0.139 / 0.141
+    wav_step_kernel (csrc/wavelet_chain.hip; measured on the three kernels it replaced):
+      SAPG_wavelet 34 x 30 / 512 x 256                  0.139 / 0.112
+      myula_wavelet, <false> / <true> (moments)         0.139 / 0.139
+      SAPG_wavelet_semiblind, all fixed / sigma2 free   0.139 / 0.141
     seed = 5 / chain_offset = 0                         0.139 / 0.141
 no element over the bar in any case.
 
@@ -154,8 +156,9 @@ def _sapg_wavelet(ctx, p, y, noise=None, seed=SEED, offset=OFFSET, **opkw):
 
 @pytest.mark.parametrize("name", ["34x30", "512x256"])
 def test_one_step_normals_sapg_wavelet(ctx, name):
-    """wav_myula_kernel.  34 x 30 Haar levels 3: 7140 coefficients per chain, the last workgroup part full.  512 x 256 Haar
-    levels 4: 655 360 pairs per chain against 2048 workgroups of 256 lanes, the grid-stride loop."""
+    """wav_step_kernel<false> with theta and sigma2 read from the chain block of SAPG_wavelet.  34 x 30 Haar levels 3: 7140
+    coefficients per chain, the last workgroup part full.  512 x 256 Haar levels 4: 655 360 pairs per chain against 2048
+    workgroups of 256 lanes, the grid-stride loop."""
     p = wsc.problem("c") if name == "34x30" else wpc.problem("e")
     assert (p["y"].shape[1:], p["levels"]) == {"34x30": ((34, 30), 3), "512x256": ((512, 256), 4)}[name]
     y = _two(p["y"])
@@ -174,7 +177,8 @@ def _myula_wavelet(ctx, p, y, samples, noise=None, posterior=None, theta=0.03, s
 
 @pytest.mark.parametrize("coefficients", [False, True], ids=["fixed", "moments"])
 def test_one_step_normals_myula_wavelet(ctx, coefficients):
-    """wav_myula_fixed_kernel, and wav_myula_moments_kernel with the coefficient moments requested, 34 x 30."""
+    """wav_step_kernel<false> with theta and sigma2 read from myula_wavelet's parameter array, and wav_step_kernel<true> with
+    the coefficient moments requested, 34 x 30."""
     p = wsc.problem("c")
     y = _two(p["y"])
     post = dict(coefficients=True) if coefficients else None
@@ -195,8 +199,8 @@ def _sigma_free(op):
 
 @pytest.mark.parametrize("free", [False, True], ids=["all-fixed", "sigma2-free"])
 def test_one_step_normals_semiblind(ctx, free):
-    """wav_sb_step_kernel on case D (34 x 30 Moffat): every parameter fixed, and alpha and sigma2 free (sigma2(1) the midpoint
-    of its bounds)."""
+    """wav_step_kernel<false> with theta and sigma2 read from the chain block of SAPG_wavelet_semiblind, case D (34 x 30
+    Moffat): every parameter fixed, and alpha and sigma2 free (sigma2(1) the midpoint of its bounds)."""
     p = wbc.problem("D")
     op0 = p["ops"][0]
     y = _two(p["y"])
