@@ -429,6 +429,16 @@ struct AdmmCommon {
     bool spectral = false;
 };
 
+// U = fft2(in + add) in the layout of H, by way of the packed spectrum S
+int admm_spectrum(sbtv_ctx *ctx, const AdmmCommon &c, const double *in, const double *add, double2 *S, double2 *U) {
+    RowsArgs a{};
+    a.dir_fwd = 1;
+    a.op = OP_NONE;
+    SBTV_TRY(fft_cols_fwd(ctx, c.fp, in, add, S));
+    SBTV_TRY(fft_rows(ctx, c.fp, S, S, a));
+    return spec_unpack(ctx, c.fp, S, U);
+}
+
 int admm_common(sbtv_ctx *ctx, int M, int N, const double *taps, int taille, const double *yd, AdmmCommon *c) {
     if (((size_t)M * N) & 1)
         return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
@@ -443,14 +453,7 @@ int admm_common(sbtv_ctx *ctx, int M, int N, const double *taps, int taille, con
     c->inv_scale = 1.0 / ((double)c->fp.n1 * N);
     c->parseval = 1.0 / ((double)M * N);
     SBTV_TRY(psf_spectrum(ctx, c->fp, c->taps_d, taille, c->Hs));
-    if (yd) {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.op = OP_NONE;
-        SBTV_TRY(fft_cols_fwd(ctx, c->fp, yd, nullptr, c->S));
-        SBTV_TRY(fft_rows(ctx, c->fp, c->S, c->S, a));
-        SBTV_TRY(spec_unpack(ctx, c->fp, c->S, c->Ys));
-    }
+    if (yd) SBTV_TRY(admm_spectrum(ctx, *c, yd, nullptr, c->S, c->Ys));
     return 0;
 }
 
@@ -466,6 +469,35 @@ int admm_apply(sbtv_ctx *ctx, const AdmmCommon &c, int op, const double *in, dou
     return fft_cols_inv(ctx, c.fp, c.S, out, c.inv_scale);
 }
 
+// out = real(ifft2((conj(H) Y + mu fft2(in + add)) / (|H|^2 + mu))), the row pass OP_SALSA (mu: device); its residual sum
+// against Y goes to acc, and c.S is left holding N times the column transform of `out`
+int admm_solve(sbtv_ctx *ctx, const AdmmCommon &c, const double *in, const double *add, const double2 *Y, const double *mu,
+               double *acc, double *out) {
+    RowsArgs a{};
+    a.dir_fwd = 1;
+    a.dir_inv = 1;
+    a.op = OP_SALSA;
+    a.H = c.Hs;
+    a.Y = Y;
+    a.mu = mu;
+    a.acc = acc;
+    SBTV_TRY(fft_cols_fwd(ctx, c.fp, in, add, c.S));
+    SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
+    return fft_cols_inv(ctx, c.fp, c.S, out, c.inv_scale);
+}
+
+// acc = the partial sums of ||H fft2(x) - fft2(y)||^2 (OP_RESID: nothing is stored)
+int admm_resid(sbtv_ctx *ctx, const AdmmCommon &c, const double *x, double *acc) {
+    RowsArgs a{};
+    a.dir_fwd = 1;
+    a.op = OP_RESID;
+    a.H = c.Hs;
+    a.Y = c.Ys;
+    a.acc = acc;
+    SBTV_TRY(fft_cols_fwd(ctx, c.fp, x, nullptr, c.S));
+    return fft_rows(ctx, c.fp, c.S, nullptr, a);
+}
+
 int admm_init_x(sbtv_ctx *ctx, const AdmmCommon &c, int initialization, const double *yd, const double *xi, double *x) {
     if (initialization == 0) {
         SBTV_HIP(ctx, hipMemsetAsync(x, 0, sizeof(double) * c.P, ctx->stream));   // AT(zeros) == 0
@@ -477,15 +509,17 @@ int admm_init_x(sbtv_ctx *ctx, const AdmmCommon &c, int initialization, const do
     return 0;
 }
 
+// x_init_name: what the caller's start array is called in its message; tv: the entry point runs a TV prox of TViters iterations
 int check_common(sbtv_ctx *ctx, const char *who, const double *y, const double *taps, const sbtv_salsa_opts *opts,
-                 const double *x_init, int M, int N, int batch, int taille) {
+                 const double *x_init, int M, int N, int batch, int taille, const char *x_init_name = "x_init", bool tv = true) {
     if (!y || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": missing required argument");
     if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
     if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
     if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
         return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
-    if (opts->initialization == 33333 && !x_init) return fail(ctx, SBTV_ERR_INIT, "Initialization = array but x_init is NULL");
-    if (opts->TViters <= 0) return fail(ctx, SBTV_ERR_MAXITER, std::string(who) + ": TViters must be positive");
+    if (opts->initialization == 33333 && !x_init)
+        return fail(ctx, SBTV_ERR_INIT, std::string("Initialization = array but ") + x_init_name + " is NULL");
+    if (tv && opts->TViters <= 0) return fail(ctx, SBTV_ERR_MAXITER, std::string(who) + ": TViters must be positive");
     if (opts->maxiter < 1) return fail(ctx, SBTV_ERR_MAXITER, std::string(who) + ": maxiter must be positive");
     if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
     return 0;
@@ -500,28 +534,144 @@ inline bool csalsa_spectral_wanted() {
     return on;
 }
 
-// One warm-started TV prox of an outer iteration.  Optimistic: `nlaunch` counts the optimistic launches made on this plan
-// so far (the kernels read dual buffer cur ^ parity); the step sums of the K iterations go to stepsums[0..K).
-inline int admm_prox(sbtv_ctx *ctx, const ProxPlan &pp, const double *g, int K, double *f, bool spec, long long *nlaunch,
-                     double *stepsums, const double *lam_dev, double tol, double tau) {
-    if (!spec) {
-        SBTV_TRY(prox_reset(ctx, pp, lam_dev, 1.0, K, tol, tau, true, nullptr));
-        return prox_iterate(ctx, pp, g, K, f);
-    }
-    SBTV_TRY(prox_iterate(ctx, pp, g, K, f, false, 1, (int)(*nlaunch & 1), nullptr));
-    *nlaunch += prox_launches(pp, K);
-    return reduce_partials(ctx, pp.partials, K, pp.fnblk, stepsums);
+// the four doubles of "admm.par" (each driver says what they are), on the device before anything is enqueued that reads them
+int upload_par(sbtv_ctx *ctx, double *par, const double (&h)[4]) {
+    SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
-// Per-iteration scalars travel through two pinned slots; an event per slot tells the host (which runs one iteration
-// ahead) when slot `outer & 1` holds the scalars of iteration `outer`.
-struct AdmmSlots {
+// The warm-started TV prox of an outer iteration: a plan (of one image, or of CoRAL's two), its threshold(s) `lam` on the
+// device and K iterations per prox.
+struct AdmmProx {
+    ProxPlan pp;
+    const double *lam = nullptr;
+    int K = 0;
+    double tol = 0.0, tau = 0.0;
+    long long nlaunch = 0;       // optimistic launches so far: the kernels read dual buffer cur ^ (nlaunch & 1)
+
+    int plan(sbtv_ctx *ctx, int M, int N, int batch, const char *tag, int iters, const sbtv_salsa_opts *opts) {
+        K = iters;
+        tol = opts->chambolle_tol;
+        tau = opts->chambolle_tau;
+        return prox_plan(ctx, M, N, batch, &pp, tag);
+    }
+    // arms the control block(s); fresh: before the first prox, on zero duals
+    int arm(sbtv_ctx *ctx, bool fresh) { return prox_reset(ctx, pp, lam, 1.0, K, tol, tau, !fresh, nullptr); }
+    // f = prox(g).  Exact: re-armed, the kernels apply the stop rule.  Optimistic: all K iterations back to back on the
+    // control block as `arm` left it, and the step sums of the K iterations (of image b at stepsums + b FSTRIDE) for the
+    // host's rule: reduced at once, or with a job list together with the other sums of the iteration
+    int run(sbtv_ctx *ctx, const double *g, double *f, bool optimistic, double *stepsums, RedJobs *jb) {
+        if (!optimistic) {
+            SBTV_TRY(arm(ctx, false));
+            return prox_iterate(ctx, pp, g, K, f);
+        }
+        SBTV_TRY(prox_iterate(ctx, pp, g, K, f, false, 1, (int)(nlaunch & 1), nullptr));
+        nlaunch += prox_launches(pp, K);
+        const int nvec = (pp.batch - 1) * FSTRIDE + K;
+        if (!jb) return reduce_partials(ctx, pp.partials, nvec, pp.fnblk, stepsums);
+        jb->add(pp.partials, nvec, pp.fnblk, stepsums);
+        return 0;
+    }
+    // the host's rule on the step sums of an optimistic prox (SOLVE_RESTART_EXACT: it fired early)
+    int check(sbtv_ctx *ctx, const double *stepsums) { return spec_stop_rule(ctx, pp, stepsums, K, tol); }
+};
+
+// What a solve carries through its pipelined loop.  Per-iteration scalars travel through two pinned slots; an event per
+// slot tells the host (which runs one iteration ahead) when the slot of an iteration holds its scalars.  Beside them: the
+// clock of `times`, the operator counts, the Chambolle iterations of sbtv_last_timing.
+struct AdmmRun {
+    static constexpr int SLOT = 96;                // doubles per slot; the last two take the iteration counts of exact proxes
+    sbtv_ctx *ctx = nullptr;
+    double *hs = nullptr;                          // the two slots
     hipEvent_t ev[2] = {nullptr, nullptr};
-    ~AdmmSlots() {
+    long long opt_iters[2] = {0, 0};
+    std::chrono::steady_clock::time_point t0;
+    int numA = 0, numAt = 0;
+    long long prox_iters = 0;
+    int *numA_out = nullptr, *numAt_out = nullptr, *n_outer_out = nullptr;
+
+    ~AdmmRun() {
         for (auto e : ev)
             if (e) (void)hipEventDestroy(e);
     }
+    int open(sbtv_ctx *c, int *numA_o, int *numAt_o, int *n_outer_o) {
+        ctx = c;
+        numA_out = numA_o;
+        numAt_out = numAt_o;
+        n_outer_out = n_outer_o;
+        void *pz = nullptr;
+        SBTV_TRY(pinned_get(ctx, sizeof(double) * 2 * SLOT, &pz));
+        hs = static_cast<double *>(pz);
+        for (auto &e : ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return 0;
+    }
+    // the loop begins: sbtv_last_timing and `times` count from here
+    int start() {
+        t0 = std::chrono::steady_clock::now();
+        SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        return 0;
+    }
+    // before the loop: the first n doubles of `sums`, read back through slot 0
+    int fetch(const double *sums, int n, const double **h) {
+        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *h = hs;
+        return 0;
+    }
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    // end of enqueue(outer): the first n doubles of `sums` into the iteration's slot.  Its Chambolle iterations are `iters` if
+    // its proxes were optimistic; exact ones hand the control blocks that count theirs (k0, k1: device)
+    int publish(int outer, const double *sums, int n, long long iters, const ProxCtrl *k0 = nullptr,
+                const ProxCtrl *k1 = nullptr) {
+        double *hsl = hs + (outer & 1) * SLOT;
+        int *kh = reinterpret_cast<int *>(hsl + SLOT - 2);
+        kh[0] = kh[2] = 0;
+        opt_iters[outer & 1] = iters;
+        SBTV_HIP(ctx, hipGetLastError());
+        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (k0) SBTV_HIP(ctx, hipMemcpyAsync(kh, &k0->k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (k1) SBTV_HIP(ctx, hipMemcpyAsync(kh + 2, &k1->k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipEventRecord(ev[outer & 1], ctx->stream));
+        return 0;
+    }
+    // head of process(outer): waits for the iteration's slot, books its Chambolle iterations
+    int wait(int outer, const double **hsl) {
+        *hsl = hs + (outer & 1) * SLOT;
+        SBTV_HIP(ctx, hipEventSynchronize(ev[outer & 1]));
+        const int *kh = reinterpret_cast<const int *>(*hsl + SLOT - 2);
+        prox_iters += opt_iters[outer & 1] + kh[0] + kh[2];
+        return 0;
+    }
+    // after the loop: its device time (sbtv_last_timing), the result x (null: the caller fetches its own), the counters
+    int finish(size_t P, int last, const double *x, double *x_out) {
+        SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
+        if (x) {
+            SBTV_HIP(ctx, hipMemcpyAsync(x_out, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        if (numA_out) *numA_out = numA;
+        if (numAt_out) *numAt_out = numAt;
+        if (n_outer_out) *n_outer_out = last;
+        return 0;
+    }
 };
+
+// The stop rule of SALSA_v2.m:453-472 (CoRAL_v2.m:435-453 is the same rule), from the second iteration on: the relative
+// change of the objective f (criterion 1), ||x - xprev|| / ||x|| from their squares num and den (2), f itself (3)
+inline bool salsa_stop(int stopcriterion, int outer, double f, double obj_prev, double num, double den, double tolA) {
+    if (outer <= 1) return false;                                        // :453
+    double crit;
+    if (stopcriterion == 1)
+        crit = fabs(f - obj_prev) / obj_prev;                            // :456
+    else if (stopcriterion == 2)
+        crit = fabs(sqrt(num) / sqrt(den));                              // :460
+    else
+        crit = f;                                                        // :464
+    return crit < tolA;                                                  // :472
+}
 
 // ------------------------------------------------------------------------------------------------
 int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, double mu1, double mu2,
@@ -540,8 +690,9 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         c.spectral = sp;
     }
     const bool spectral = c.spectral;
-    ProxPlan pp;
-    SBTV_TRY(prox_plan(ctx, M, N, 1, &pp));
+    const int K = opts->TViters;
+    AdmmProx prox;
+    SBTV_TRY(prox.plan(ctx, M, N, 1, "prox", K, opts));
     const size_t P = c.P;
     const int nb = ad_blocks(P);
     double *xbuf[2], *u, *bu, *v, *bv, *w, *Ax, *g, *par, *partials, *sums, *acc;
@@ -564,37 +715,29 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
     double *cst = nullptr, *rs = nullptr;
     SBTV_TRY(ws_get_t(ctx, "admm.cs", (size_t)8, &cst));
     SBTV_TRY(ws_get_t(ctx, "admm.rs", (size_t)4, &rs));
-    double *hs = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 128, &pz));
-        hs = static_cast<double *>(pz);
-    }
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
+    const double *hs = nullptr;
     const int maxiter = opts->maxiter;
     if (!(epsilon != 0.0)) epsilon = sqrt((double)P + 8 * sqrt((double)P)) * sigma;              // :413
-    auto upload_par = [&]() -> int {
-        const double h[4] = {mu1, mu2, 1.0 / mu1, 0.0};
-        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return 0;
-    };
-    SBTV_TRY(upload_par());
-    int h_numA = 0, h_numAt = 1;                                         // ATy (:301)
+    SBTV_TRY(upload_par(ctx, par, {mu1, mu2, 1.0 / mu1, 0.0}));
+    run.numAt = 1;                                                       // ATy (:301)
     ctx->calls += 2;                                                     // AT(y), invLS(ATy, mu1) (:301,310)
     double *x = xbuf[0];
     SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
     if (opts->initialization == 0) ctx->calls += 1;
-    if (opts->initialization == 2) h_numAt += 1;                         // :385
+    if (opts->initialization == 2) run.numAt += 1;                       // :385
     SBTV_HIP(ctx, hipMemsetAsync(u, 0, sizeof(double) * P, ctx->stream));   // :404-408
     SBTV_HIP(ctx, hipMemsetAsync(bu, 0, sizeof(double) * P, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(v, 0, sizeof(double) * P, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(bv, 0, sizeof(double) * P, ctx->stream));
-    SBTV_TRY(prox_zero_duals(ctx, pp));                                  // :440-441
-    SBTV_TRY(prox_reset(ctx, pp, par + 2, 1.0, opts->TViters, opts->chambolle_tol, opts->chambolle_tau, false, nullptr));
+    prox.lam = par + 2;                                                  // 1 / mu1
+    SBTV_TRY(prox_zero_duals(ctx, prox.pp));                             // :440-441
+    SBTV_TRY(prox.arm(ctx, true));
 
     // state before the loop (:416-448): Ax, criterion(1), objective(1) = TV(x), mses(1), distances
     SBTV_TRY(admm_apply(ctx, c, OP_MUL_H, x, Ax));
-    h_numA += 2;                                                         // :421,445
+    run.numA += 2;                                                       // :421,445
     ctx->calls += 2;
     {
         // v = 0, bv = 0, u = 0: the update kernel on scratch multipliers gives the three norms without side effects
@@ -609,8 +752,7 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
                            (const double *)nullptr, sums + 8, 1.0, partials, P);
         SBTV_TRY(reduce_partials(ctx, partials, 6, nb, sums));
         SBTV_TRY(tvnorm_dev(ctx, x, M, N, 1, sums + 6));
-        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SBTV_TRY(run.fetch(sums, 8, &hs));
         // before the loop v = 0, so distance1(1) = ||Ax-y-v|| = ||Ax-y|| (:447); hs[1] is not that (v=ve there)
         if (criterion) criterion[0] = sqrt(hs[0]);
         if (distance1) distance1[0] = sqrt(hs[0]);
@@ -620,16 +762,14 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         if (times) times[0] = 0.0;
     }
     double crit_prev = sqrt(hs[0]), obj_prev = hs[6];
-    const auto t0 = std::chrono::steady_clock::now();
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    SBTV_TRY(run.start());
     // optimistic prox launches need a fixed threshold (the control block is armed once) and the tile kernels
-    const int K = opts->TViters;
-    const bool spec = spec_wanted && delta == 1.0 && prox_spec_ok(pp, g, u, K);
+    const bool spec = spec_wanted && delta == 1.0 && prox_spec_ok(prox.pp, g, u, K);
     const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
-    long long nlaunch = 0, prox_iters = 0;
-    AdmmSlots slots;
-    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    double *hslot[2] = {hs, hs + 64};
+    // end of an enqueue: the sums (with the step sums of an optimistic prox) or the iteration count of an exact prox
+    auto publish = [&](int outer) {
+        return run.publish(outer, sums, 16 + (spec ? K : 0), spec ? K : 0, spec ? nullptr : prox.pp.ctrl);
+    };
     const bool tv_fused = fft_cols_tv_ok(c.fp);
     const int ntv = tv_fused ? fft_cols_blocks(c.fp) : 0;
     double *tvp = nullptr;
@@ -673,24 +813,12 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         hipLaunchKernelGGL(csalsa_scal_kernel, dim3(1), dim3(256), 0, ctx->stream, acc, fft_rows_blocks(c.fp), cst, epsilon,
                            c.parseval, sums);
         RedJobs jb;
-        if (!spec) {
-            SBTV_TRY(admm_prox(ctx, pp, g, K, u, false, &nlaunch, sums + 16, par + 2, opts->chambolle_tol, opts->chambolle_tau));
-        } else {
-            // (admm_prox without its reduction: the step sums are reduced together with the sums of the last pass)
-            SBTV_TRY(prox_iterate(ctx, pp, g, K, u, false, 1, (int)(nlaunch & 1), nullptr));
-            nlaunch += prox_launches(pp, K);
-            jb.add(pp.partials, K, pp.fnblk, sums + 16);
-        }
+        SBTV_TRY(prox.run(ctx, g, u, spec, sums + 16, &jb));             // step sums: reduced with the sums of the last pass
         hipLaunchKernelGGL(csalsa_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, xn, u, bu, td,
                            (opts->stopcriterion == 2) ? xprev : (const double *)nullptr, partials, (unsigned)M, (unsigned)N, P);
         jb.add(partials, 5, nb, sums + 2);
         SBTV_TRY(reduce_jobs(ctx, jb));
-        SBTV_HIP(ctx, hipGetLastError());
-        double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * (16 + (spec ? K : 0)), hipMemcpyDeviceToHost, ctx->stream));
-        if (!spec) SBTV_HIP(ctx, hipMemcpyAsync(hsl + 8, pp.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
-        return 0;
+        return publish(outer);
     };
     auto enqueue = [&](int outer) -> int {                               // :461
         if (spectral) return enqueue_spectral(outer);
@@ -700,30 +828,11 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         // r = mu1 (u+bu) + mu2 AT(y+v+bv) ; x = invLS(r, mu1)   (:467-471), all in one spectral pass:
         //   X = (conj(H) W + mu1 S) / (|H|^2 + mu1),  W = fft2(mu2 (y+v+bv)),  S = fft2(u+bu)
         hipLaunchKernelGGL(csalsa_w_kernel, dim3(nb), dim3(AB), 0, ctx->stream, yd, v, bv, par, w, P);
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.op = OP_NONE;
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, w, nullptr, c.S));
-            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-            SBTV_TRY(spec_unpack(ctx, c.fp, c.S, Ws));
-        }
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.dir_inv = 1;
-            a.op = OP_SALSA;
-            a.H = c.Hs;
-            a.Y = Ws;
-            a.mu = par;                                                  // mu1
-            a.acc = acc;                                                 // residual sum of OP_SALSA, not used here
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, u, bu, c.S));
-            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xn, c.inv_scale));
-        }
+        SBTV_TRY(admm_spectrum(ctx, c, w, nullptr, c.S, Ws));
+        SBTV_TRY(admm_solve(ctx, c, u, bu, Ws, par, acc, xn));           // mu1; the residual sum in acc is not used here
         // u = prox_{TV/mu1}(x - bu), warm-started duals (:476)
         hipLaunchKernelGGL(ad_sub_kernel, dim3(nb), dim3(AB), 0, ctx->stream, xn, bu, g, P);
-        SBTV_TRY(admm_prox(ctx, pp, g, K, u, spec, &nlaunch, sums + 16, par + 2, opts->chambolle_tol, opts->chambolle_tau));
+        SBTV_TRY(prox.run(ctx, g, u, spec, sums + 16, nullptr));
         // Ax (the forward column pass of x also leaves the periodic-TV partials of phi(x) = TVnorm(x), :498), projection on
         // the epsilon ball, multipliers, traces (:481-501)
         {
@@ -743,23 +852,17 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         SBTV_TRY(reduce_partials(ctx, partials, 6, nb, sums));
         if (tv_fused) SBTV_TRY(reduce_partials(ctx, tvp, 1, ntv, sums + 6));
         else SBTV_TRY(tvnorm_dev(ctx, xn, M, N, 1, sums + 6));
-        SBTV_HIP(ctx, hipGetLastError());
-        double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * (16 + (spec ? K : 0)), hipMemcpyDeviceToHost, ctx->stream));
-        if (!spec) SBTV_HIP(ctx, hipMemcpyAsync(hsl + 8, pp.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
-        return 0;
+        return publish(outer);
     };
     bool stop = false;
     // host side of iteration `outer`: traces (:494-501) and the stop rule (:517-541)
     auto process = [&](int outer) -> int {
-        const int k = outer - 1;
-        const double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
-        if (spec) SBTV_TRY(spec_stop_rule(ctx, pp, hsl + 16, K, opts->chambolle_tol));
-        prox_iters += spec ? K : *reinterpret_cast<const int *>(hsl + 8);
-        h_numAt += 1;
-        h_numA += 1;
+        const int k = outer - 1;                                         // the traces start at the first iteration
+        const double *hsl;
+        SBTV_TRY(run.wait(outer, &hsl));
+        if (spec) SBTV_TRY(prox.check(ctx, hsl + 16));
+        run.numAt += 1;
+        run.numA += 1;
         ctx->calls += 3;                                                 // AT, invLS, A
         const double crit = sqrt(hsl[0]), obj = hsl[6];
         if (criterion) criterion[k] = crit;                              // :494
@@ -767,11 +870,11 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         if (distance2) distance2[k] = sqrt(hsl[2]);                      // :497
         if (objective) objective[k] = obj;                               // :498
         if (mses && td) mses[k] = hsl[3] / (double)P;                    // :501
-        if (times) times[k] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (times) times[k] = run.seconds();
         if (delta != 1.0) {                                              // :517-518
             mu1 *= delta;
             mu2 *= delta;
-            SBTV_TRY(upload_par());
+            SBTV_TRY(upload_par(ctx, par, {mu1, mu2, 1.0 / mu1, 0.0}));
         }
         double sc;
         if (opts->stopcriterion == 1)
@@ -785,17 +888,9 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         stop = (sc < opts->tolA && crit <= epsilon);                     // :529,535,541
         return 0;
     };
-    int last = 1;
+    int last = 1;                                                        // the state before the loop is iteration 1 (:416-448)
     SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
-    SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[(last - 1) & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (numA) *numA = h_numA;
-    if (numAt) *numAt = h_numAt;
-    if (n_outer) *n_outer = last;
-    return 0;
+    return run.finish(P, last, xbuf[(last - 1) & 1], x_out_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -813,9 +908,10 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
         return !(e && e[0] == '0');
     }();
     const bool batched = env_batch && opts->TViters == TViters2;
-    ProxPlan pu, pv;
-    SBTV_TRY(prox_plan(ctx, M, N, batched ? 2 : 1, &pu, batched ? "prox.pair" : "prox"));
-    if (!batched) SBTV_TRY(prox_plan(ctx, M, N, 1, &pv, "prox2"));
+    const int K1 = opts->TViters, K2 = TViters2;
+    AdmmProx pu, pv;                                                     // batched: pu is the plan of both images
+    SBTV_TRY(pu.plan(ctx, M, N, batched ? 2 : 1, batched ? "prox.pair" : "prox", K1, opts));
+    if (!batched) SBTV_TRY(pv.plan(ctx, M, N, 1, "prox2", K2, opts));
     const size_t P = c.P;
     const int nb = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
     const bool tv_in_s = !(M & 1) && P < ((size_t)1 << 31);             // TV(u), TV(v) ride in the pass that forms s
@@ -834,19 +930,13 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
     SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)8 * nb, &partials));
     SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0..6] post sums, [8] resid2, [9] TV(u), [10] TV(v), [16..], [48..] step sums
     SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
-    double *hs = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 192, &pz));
-        hs = static_cast<double *>(pz);
-    }
-    {
-        const double h[4] = {mu_ls, tau1 / mu1, tau2 / mu2, 0.0};        // thresholds :356,361
-        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
+    SBTV_TRY(upload_par(ctx, par, {mu_ls, tau1 / mu1, tau2 / mu2, 0.0}));   // thresholds :356,361
+    pu.lam = par + 1;
+    pv.lam = par + 2;
     const int maxiter = opts->maxiter;
-    int h_numA = 0, h_numAt = 2;                                         // ATy twice (:189,219)
+    run.numAt = 2;                                                       // ATy twice (:189,219)
     ctx->calls += 3;                                                     // AT(y), invLS(ATy), AT(y)
     double *x = xbuf[0];
     SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
@@ -856,23 +946,17 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
         SBTV_HIP(ctx, hipMemcpyAsync(dst, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(g1, 0, sizeof(double) * P, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(g2, 0, sizeof(double) * P, ctx->stream));
-    SBTV_TRY(prox_zero_duals(ctx, pu));                                  // :384-392
-    SBTV_TRY(prox_reset(ctx, pu, par + 1, 1.0, opts->TViters, opts->chambolle_tol, opts->chambolle_tau, false, nullptr));
+    SBTV_TRY(prox_zero_duals(ctx, pu.pp));                               // :384-392
+    SBTV_TRY(pu.arm(ctx, true));
     if (!batched) {
-        SBTV_TRY(prox_zero_duals(ctx, pv));
-        SBTV_TRY(prox_reset(ctx, pv, par + 2, 1.0, TViters2, opts->chambolle_tol, opts->chambolle_tau, false, nullptr));
+        SBTV_TRY(prox_zero_duals(ctx, pv.pp));
+        SBTV_TRY(pv.arm(ctx, true));
     }
 
     // initial objective (:366-368)
+    double obj_prev;
     {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.op = OP_RESID;
-        a.H = c.Hs;
-        a.Y = c.Ys;
-        a.acc = acc;
-        SBTV_TRY(fft_cols_fwd(ctx, c.fp, x, nullptr, c.S));
-        SBTV_TRY(fft_rows(ctx, c.fp, c.S, nullptr, a));
+        SBTV_TRY(admm_resid(ctx, c, x, acc));
         SBTV_TRY(reduce_partials(ctx, acc, 1, nrb, sums + 8));
         SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
         SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 8, ctx->stream));
@@ -882,27 +966,19 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
             SBTV_TRY(pair_sums(ctx, x, td, P, 1, o4));
             SBTV_HIP(ctx, hipMemcpyAsync(sums, o4, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         }
-        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        h_numA += 1;
+        const double *hs;
+        SBTV_TRY(run.fetch(sums, 16, &hs));
+        run.numA += 1;
         ctx->calls += 1;
-        const double f0 = 0.5 * (hs[8] * c.parseval) + tau1 * hs[9] + tau2 * hs[9];   // u = v = x
-        if (objective) objective[0] = f0;
+        obj_prev = 0.5 * (hs[8] * c.parseval) + tau1 * hs[9] + tau2 * hs[9];   // u = v = x
+        if (objective) objective[0] = obj_prev;
         if (times) times[0] = 0.0;
         if (mses && td) mses[0] = hs[0] / (double)P;                     // :381
-        hs[15] = f0;
     }
-    double obj_prev = hs[15];
-    const auto t0 = std::chrono::steady_clock::now();
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    const int K1 = opts->TViters, K2 = TViters2;
-    const bool spec = spec_wanted && prox_spec_ok(pu, g1, u, K1) &&
-                      (batched || prox_spec_ok(pv, g2, v, K2));
+    SBTV_TRY(run.start());
+    const bool spec = spec_wanted && prox_spec_ok(pu.pp, g1, u, K1) &&
+                      (batched || prox_spec_ok(pv.pp, g2, v, K2));
     const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
-    long long nl_u = 0, nl_v = 0, prox_iters = 0;
-    AdmmSlots slots;
-    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    double *hslot[2] = {hs, hs + 96};
     auto enqueue = [&](int outer) -> int {                               // :394
         double *xn = xbuf[outer & 1];
         const double *xprev = xbuf[(outer & 1) ^ 1];
@@ -911,23 +987,17 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
         const bool sp = spec && outer >= 2;
         RedJobs jb;
         if (spec && outer == 2) {
-            SBTV_TRY(prox_reset(ctx, pu, par + 1, 1.0, K1, opts->chambolle_tol, opts->chambolle_tau, true, nullptr));
-            if (!batched) SBTV_TRY(prox_reset(ctx, pv, par + 2, 1.0, K2, opts->chambolle_tol, opts->chambolle_tau, true, nullptr));
+            SBTV_TRY(pu.arm(ctx, false));
+            if (!batched) SBTV_TRY(pv.arm(ctx, false));
         }
         if (batched) {
-            // both images in one plan: the step sums of image b land at sums + 16 + b FSTRIDE (= sums + 48 for v)
+            // both images in one plan: the step sums of image b land at sums + 16 + b FSTRIDE (= sums + 48 for v), reduced
+            // at the end of the iteration
             static_assert(FSTRIDE == 32, "the step sums of the second prox are read at sums + 48");
-            if (!sp) {
-                SBTV_TRY(prox_reset(ctx, pu, par + 1, 1.0, K1, opts->chambolle_tol, opts->chambolle_tau, true, nullptr));
-                SBTV_TRY(prox_iterate(ctx, pu, g1, K1, u));
-            } else {
-                SBTV_TRY(prox_iterate(ctx, pu, g1, K1, u, false, 1, (int)(nl_u & 1), nullptr));
-                nl_u += prox_launches(pu, K1);
-                jb.add(pu.partials, FSTRIDE + K1, pu.fnblk, sums + 16);      // reduced at the end of the iteration
-            }
+            SBTV_TRY(pu.run(ctx, g1, u, sp, sums + 16, &jb));
         } else {
-            SBTV_TRY(admm_prox(ctx, pu, g1, K1, u, sp, &nl_u, sums + 16, par + 1, opts->chambolle_tol, opts->chambolle_tau));
-            SBTV_TRY(admm_prox(ctx, pv, g2, K2, v, sp, &nl_v, sums + 48, par + 2, opts->chambolle_tol, opts->chambolle_tau));
+            SBTV_TRY(pu.run(ctx, g1, u, sp, sums + 16, nullptr));
+            SBTV_TRY(pv.run(ctx, g2, v, sp, sums + 48, nullptr));
         }
         // r = ATy + mu1 (u+bu) + mu2 (v+bv) ; x = invLS(r)   (:411-413)  + residual energy (:423, Parseval)
         if (tv_in_s) {
@@ -938,19 +1008,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
             hipLaunchKernelGGL(coral_s_kernel<false>, dim3(nb), dim3(AB), 0, ctx->stream, u, bu, v, bv, mu1, mu2, mu_ls, s, tvpart,
                                (unsigned)M, (unsigned)N, P);
         }
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.dir_inv = 1;
-            a.op = OP_SALSA;
-            a.H = c.Hs;
-            a.Y = c.Ys;
-            a.mu = par;                                                  // mu_ls
-            a.acc = acc;
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, s, nullptr, c.S));
-            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xn, c.inv_scale));
-        }
+        SBTV_TRY(admm_solve(ctx, c, s, nullptr, c.Ys, par, acc, xn));    // mu_ls
         hipLaunchKernelGGL(coral_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, xn,
                            (opts->stopcriterion == 2) ? xprev : (const double *)nullptr, u, v, bu, bv, g1, g2, td, partials, P);
         jb.add(partials, 7, nb, sums);
@@ -960,28 +1018,19 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
             SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
             SBTV_TRY(tvnorm_dev(ctx, v, M, N, 1, sums + 10));
         }
-        SBTV_HIP(ctx, hipGetLastError());
-        double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * (sp ? 80 : 12), hipMemcpyDeviceToHost, ctx->stream));
-        if (!sp) {
-            SBTV_HIP(ctx, hipMemcpyAsync(hsl + 12, pu.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            SBTV_HIP(ctx, hipMemcpyAsync(hsl + 13, batched ? pu.ctrl + 1 : pv.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
-        return 0;
+        if (sp) return run.publish(outer, sums, 80, K1 + K2);
+        return run.publish(outer, sums, 12, 0, pu.pp.ctrl, batched ? pu.pp.ctrl + 1 : pv.pp.ctrl);
     };
     bool stop = false;
     auto process = [&](int outer) -> int {
-        const double *hsl = hslot[outer & 1];
+        const double *hsl;
         const bool sp = spec && outer >= 2;
-        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
+        SBTV_TRY(run.wait(outer, &hsl));
         if (sp) {     // per plan: batched, the step sums of v are those of the plan's second image (sums + 48)
-            SBTV_TRY(spec_stop_rule(ctx, pu, hsl + 16, K1, opts->chambolle_tol));
-            if (!batched) SBTV_TRY(spec_stop_rule(ctx, pv, hsl + 48, K2, opts->chambolle_tol));
+            SBTV_TRY(pu.check(ctx, hsl + 16));
+            if (!batched) SBTV_TRY(pv.check(ctx, hsl + 48));
         }
-        prox_iters += sp ? (long long)(K1 + K2)
-                         : (long long)(*reinterpret_cast<const int *>(hsl + 12) + *reinterpret_cast<const int *>(hsl + 13));
-        h_numA += 1;
+        run.numA += 1;
         ctx->calls += 2;                                                 // invLS, A
         const double f = 0.5 * (hsl[8] * c.parseval) + tau1 * hsl[9] + tau2 * hsl[10];      // :425
         if (objective) objective[outer] = f;
@@ -990,31 +1039,14 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
             distance[(size_t)(outer - 1) * 2] = sqrt(hsl[1]) / sqrt(hsl[3] + hsl[4]);       // :432
             distance[(size_t)(outer - 1) * 2 + 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[5]);   // :433
         }
-        if (times) times[outer] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (outer > 1) {                                                 // :435
-            double crit;
-            if (opts->stopcriterion == 1)
-                crit = fabs(f - obj_prev) / obj_prev;                    // :441
-            else if (opts->stopcriterion == 2)
-                crit = fabs(sqrt(hsl[6]) / sqrt(hsl[3]));                // :445
-            else
-                crit = f;                                                // :448
-            stop = crit < opts->tolA;                                    // :453
-        }
+        if (times) times[outer] = run.seconds();
+        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[6], hsl[3], opts->tolA);
         obj_prev = f;
         return 0;
     };
     int last = 0;
     SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
-    SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (numA) *numA = h_numA;
-    if (numAt) *numAt = h_numAt;
-    if (n_outer) *n_outer = last;
-    return 0;
+    return run.finish(P, last, xbuf[last & 1], x_out_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1034,8 +1066,9 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
                bool spec_wanted) {
     AdmmCommon c;
     SBTV_TRY(admm_common(ctx, M, N, taps, taille, nullptr, &c));
-    ProxPlan pp;
-    SBTV_TRY(prox_plan(ctx, M, N, 1, &pp));
+    const int K = opts->TViters;
+    AdmmProx prox;
+    SBTV_TRY(prox.plan(ctx, M, N, 1, "prox", K, opts));
     const size_t P = c.P;
     const int nb = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
     const bool tv_in_post = !(M & 1) && P < ((size_t)1 << 31);          // TV(u) rides in the element-wise pass
@@ -1056,17 +1089,10 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
     SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));         // residual sum of OP_SALSA (against W: not used)
     SBTV_TRY(ws_get_t(ctx, "admm.W", c.fp.u_img, &Ws));
     SBTV_TRY(ws_get_t(ctx, "admm.S2", c.fp.s_img, &S2));
-    double *hs = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 192, &pz));
-        hs = static_cast<double *>(pz);
-    }
-    {
-        const double h[4] = {mu1 / mu2, tau / mu1, 0.0, 0.0};
-        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
+    SBTV_TRY(upload_par(ctx, par, {mu1 / mu2, tau / mu1, 0.0, 0.0}));
+    prox.lam = par + 1;
     // the inverse column pass of H X takes the spectrum the row pass of X left: N times the column transform of x (the
     // chirp-z path keeps whole 2-D spectra, its "row pass" is point-wise)
     const double bx_scale = c.fp.generic ? c.inv_scale : c.inv_scale / (double)N;
@@ -1079,12 +1105,11 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
                                (const double *)u, yd, md, bu, v, bv, g, td, mu2, partials, (unsigned)M, (unsigned)N, P);
     };
     const int maxiter = opts->maxiter;
-    int h_numA = 0, h_numAt = 0;
     double *x = xbuf[0];
     if (opts->initialization == 2) {                                     // x = B'(m .* y)
         hipLaunchKernelGGL(masked_my_kernel, dim3(nb), dim3(AB), 0, ctx->stream, md, yd, g, P);
         SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, g, x));
-        h_numAt += 1;
+        run.numAt += 1;
         ctx->calls += 1;
     } else {
         SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
@@ -1092,38 +1117,31 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
     // Bx = B x ; u = x ; v = Bx ; bu = bv = 0 ; zero duals.  The element-wise pass on that state leaves bu = bv = 0, the
     // first prox input g = x, the first v and the sums of objective(1) / mses(1)
     SBTV_TRY(admm_apply(ctx, c, OP_MUL_H, x, Bx));
-    h_numA += 1;
+    run.numA += 1;
     ctx->calls += 1;
     SBTV_HIP(ctx, hipMemcpyAsync(u, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipMemcpyAsync(v, Bx, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(bu, 0, sizeof(double) * P, ctx->stream));
     SBTV_HIP(ctx, hipMemsetAsync(bv, 0, sizeof(double) * P, ctx->stream));
-    SBTV_TRY(prox_zero_duals(ctx, pp));
-    SBTV_TRY(prox_reset(ctx, pp, par + 1, 1.0, opts->TViters, opts->chambolle_tol, opts->chambolle_tau, false, nullptr));
+    SBTV_TRY(prox_zero_duals(ctx, prox.pp));
+    SBTV_TRY(prox.arm(ctx, true));
+    double obj_prev;
     {
         SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
         post(x, nullptr);
         SBTV_TRY(reduce_partials(ctx, partials, nq, nb, sums));
         if (!tv_in_post) SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
         SBTV_HIP(ctx, hipGetLastError());
-        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const double f0 = 0.5 * hs[0] + tau * hs[9];
-        if (objective) objective[0] = f0;
+        const double *hs;
+        SBTV_TRY(run.fetch(sums, 16, &hs));
+        obj_prev = 0.5 * hs[0] + tau * hs[9];
+        if (objective) objective[0] = obj_prev;
         if (times) times[0] = 0.0;
         if (mses && td) mses[0] = hs[7] / (double)P;
-        hs[15] = f0;
     }
-    double obj_prev = hs[15];
-    const auto t0 = std::chrono::steady_clock::now();
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    const int K = opts->TViters;
-    const bool spec = spec_wanted && prox_spec_ok(pp, g, u, K);
+    SBTV_TRY(run.start());
+    const bool spec = spec_wanted && prox_spec_ok(prox.pp, g, u, K);
     const int lag = (spec && (opts->speculate & 1)) ? 1 : 0;
-    long long nlaunch = 0, prox_iters = 0;
-    AdmmSlots slots;
-    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    double *hslot[2] = {hs, hs + 96};
     auto enqueue = [&](int outer) -> int {
         double *xn = xbuf[outer & 1];
         const double *xprev = xbuf[(outer & 1) ^ 1];
@@ -1131,38 +1149,12 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
         // gives a zero prox input and the rule stops at k = 1); the control block is re-armed for the optimistic launches
         const bool sp = spec && outer >= 2;
         RedJobs jb;
-        if (spec && outer == 2)
-            SBTV_TRY(prox_reset(ctx, pp, par + 1, 1.0, K, opts->chambolle_tol, opts->chambolle_tau, true, nullptr));
-        if (!sp) {
-            SBTV_TRY(admm_prox(ctx, pp, g, K, u, false, &nlaunch, sums + 16, par + 1, opts->chambolle_tol, opts->chambolle_tau));
-        } else {
-            SBTV_TRY(prox_iterate(ctx, pp, g, K, u, false, 1, (int)(nlaunch & 1), nullptr));
-            nlaunch += prox_launches(pp, K);
-            jb.add(pp.partials, K, pp.fnblk, sums + 16);                 // reduced at the end of the iteration
-        }
+        if (spec && outer == 2) SBTV_TRY(prox.arm(ctx, false));
+        SBTV_TRY(prox.run(ctx, g, u, sp, sums + 16, &jb));               // step sums: reduced at the end of the iteration
         // W = fft2(v + bv) (v was formed by the previous element-wise pass)
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.op = OP_NONE;
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, v, bv, S2));
-            SBTV_TRY(fft_rows(ctx, c.fp, S2, S2, a));
-            SBTV_TRY(spec_unpack(ctx, c.fp, S2, Ws));
-        }
-        // X = (conj(H) W + r fft2(u + bu)) / (|H|^2 + r) ; x = real(ifft2(X))
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.dir_inv = 1;
-            a.op = OP_SALSA;
-            a.H = c.Hs;
-            a.Y = Ws;
-            a.mu = par;                                                  // r = mu1 / mu2
-            a.acc = acc;
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, u, bu, c.S));
-            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xn, c.inv_scale));
-        }
+        SBTV_TRY(admm_spectrum(ctx, c, v, bv, S2, Ws));
+        // X = (conj(H) W + r fft2(u + bu)) / (|H|^2 + r), r = mu1 / mu2 ; x = real(ifft2(X))
+        SBTV_TRY(admm_solve(ctx, c, u, bu, Ws, par, acc, xn));
         // Bx = real(ifft2(H X)) from the column-transformed x the row pass left in S
         {
             RowsArgs a{};
@@ -1177,23 +1169,16 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
         jb.add(partials, nq, nb, sums);
         SBTV_TRY(reduce_jobs(ctx, jb));
         if (!tv_in_post) SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
-        SBTV_HIP(ctx, hipGetLastError());
-        double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * (sp ? 16 + K : 12), hipMemcpyDeviceToHost, ctx->stream));
-        if (!sp) SBTV_HIP(ctx, hipMemcpyAsync(hsl + 12, pp.ctrl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipEventRecord(slots.ev[outer & 1], ctx->stream));
-        return 0;
+        return run.publish(outer, sums, sp ? 16 + K : 12, sp ? K : 0, sp ? nullptr : prox.pp.ctrl);
     };
     bool stop = false;
     // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
     auto process = [&](int outer) -> int {
-        const double *hsl = hslot[outer & 1];
-        const bool sp = spec && outer >= 2;
-        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
-        if (sp) SBTV_TRY(spec_stop_rule(ctx, pp, hsl + 16, K, opts->chambolle_tol));
-        prox_iters += sp ? (long long)K : (long long)*reinterpret_cast<const int *>(hsl + 12);
-        h_numA += 1;                                                     // H .* X
-        h_numAt += 1;                                                    // conj(H) .* fft2(v + bv)
+        const double *hsl;
+        SBTV_TRY(run.wait(outer, &hsl));
+        if (spec && outer >= 2) SBTV_TRY(prox.check(ctx, hsl + 16));
+        run.numA += 1;                                                   // H .* X
+        run.numAt += 1;                                                  // conj(H) .* fft2(v + bv)
         ctx->calls += 2;
         const double f = 0.5 * hsl[0] + tau * hsl[9];
         if (objective) objective[outer] = f;
@@ -1202,31 +1187,14 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
             distance[(size_t)(outer - 1) * 2] = sqrt(hsl[1]) / sqrt(hsl[3] + hsl[4]);
             distance[(size_t)(outer - 1) * 2 + 1] = sqrt(hsl[2]) / sqrt(hsl[5] + hsl[6]);
         }
-        if (times) times[outer] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (outer > 1) {                                                 // :453
-            double crit;
-            if (opts->stopcriterion == 1)
-                crit = fabs(f - obj_prev) / obj_prev;                    // :456
-            else if (opts->stopcriterion == 2)
-                crit = fabs(sqrt(hsl[8]) / sqrt(hsl[3]));                // :460
-            else
-                crit = f;                                                // :464
-            stop = crit < opts->tolA;                                    // :472
-        }
+        if (times) times[outer] = run.seconds();
+        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[8], hsl[3], opts->tolA);
         obj_prev = f;
         return 0;
     };
     int last = 0;
     SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
-    SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xbuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (numA) *numA = h_numA;
-    if (numAt) *numAt = h_numAt;
-    if (n_outer) *n_outer = last;
-    return 0;
+    return run.finish(P, last, xbuf[last & 1], x_out_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1263,20 +1231,12 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
     SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..1] prox sums, [2..5] post sums, nb each
     SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0] |u|, [1] u^2, [2..5] post sums, [8] resid2
     SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
-    double *hs = nullptr;
-    {
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 192, &pz));
-        hs = static_cast<double *>(pz);
-    }
-    {
-        const double h[4] = {mu, 0.0, 0.0, 0.0};
-        SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
+    SBTV_TRY(upload_par(ctx, par, {mu, 0.0, 0.0, 0.0}));
     const double T = tau / mu;                                           // :394
     const int maxiter = opts->maxiter;
-    int h_numA = 0, h_numAt = 1;                                         // ATy (:288)
+    run.numAt = 1;                                                       // ATy (:288)
     ctx->calls += 2;                                                     // AT(y), invLS(ATy)
     // the start xw as the state (s, we) = (xw, 0): bu = -we = 0 (:367-393)
     double *s0 = sbuf[0];
@@ -1291,16 +1251,10 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
     }
     SBTV_HIP(ctx, hipMemsetAsync(wbuf[0], 0, sizeof(double) * C, ctx->stream));
     // initial objective (:399-401): resid = y - B W xw
+    double obj_prev;
     {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.op = OP_RESID;
-        a.H = c.Hs;
-        a.Y = c.Ys;
-        a.acc = acc;
         SBTV_TRY(wav_synthesis(ctx, wp, s0, xibuf[0], 1));
-        SBTV_TRY(fft_cols_fwd(ctx, c.fp, xibuf[0], nullptr, c.S));
-        SBTV_TRY(fft_rows(ctx, c.fp, c.S, nullptr, a));
+        SBTV_TRY(admm_resid(ctx, c, xibuf[0], acc));
         SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
         hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)s0, td, partials, C);
         RedJobs jb;
@@ -1308,42 +1262,24 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
         jb.add(acc, 1, nrb, sums + 8);
         SBTV_TRY(reduce_jobs(ctx, jb));
         SBTV_HIP(ctx, hipGetLastError());
-        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        h_numA += 1;
+        const double *hs;
+        SBTV_TRY(run.fetch(sums, 16, &hs));
+        run.numA += 1;
         ctx->calls += 1;
-        const double f0 = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
-        if (objective) objective[0] = f0;
+        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
+        if (objective) objective[0] = obj_prev;
         if (times) times[0] = 0.0;
         if (mses && td) mses[0] = hs[1] / (double)C;                     // :414
-        hs[15] = f0;
     }
-    double obj_prev = hs[15];
-    const auto t0 = std::chrono::steady_clock::now();
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    SBTV_TRY(run.start());
     const int lag = (opts->speculate & 1) ? 1 : 0;
-    AdmmSlots slots;
-    for (auto &e : slots.ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    double *hslot[2] = {hs, hs + 96};
     auto enqueue = [&](int outer) -> int {                               // :423
         const int o = outer & 1, p = o ^ 1;
         double *sn = sbuf[o], *wn = wbuf[o], *xi = xibuf[o];
         const double *sp = sbuf[p], *we = wbuf[p];
         hipLaunchKernelGGL(wav_prox_kernel, dim3(nb), dim3(AB), 0, ctx->stream, sp, we, sn, T, partials, C);      // :432
         SBTV_TRY(wav_synthesis(ctx, wp, sn, z, 1));
-        {                                                                // :434-436
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            a.dir_inv = 1;
-            a.op = OP_SALSA;
-            a.H = c.Hs;
-            a.Y = c.Ys;
-            a.mu = par;
-            a.acc = acc;
-            SBTV_TRY(fft_cols_fwd(ctx, c.fp, z, nullptr, c.S));
-            SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-            SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, xi, c.inv_scale));
-        }
+        SBTV_TRY(admm_solve(ctx, c, z, nullptr, c.Ys, par, acc, xi));    // :434-436
         hipLaunchKernelGGL(ad_sub_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xi, (const double *)z, d, P);
         SBTV_TRY(wav_analysis(ctx, wp, d, wn, 1));
         hipLaunchKernelGGL(wav_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sn, (const double *)wn, we,
@@ -1352,51 +1288,71 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
         jb.add(partials, 6, nb, sums);
         jb.add(acc, 1, nrb, sums + 8);
         SBTV_TRY(reduce_jobs(ctx, jb));
-        SBTV_HIP(ctx, hipGetLastError());
-        SBTV_HIP(ctx, hipMemcpyAsync(hslot[o], sums, sizeof(double) * 12, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipEventRecord(slots.ev[o], ctx->stream));
-        return 0;
+        return run.publish(outer, sums, 12, 0);
     };
     bool stop = false;
     // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
     auto process = [&](int outer) -> int {
-        const double *hsl = hslot[outer & 1];
-        SBTV_HIP(ctx, hipEventSynchronize(slots.ev[outer & 1]));
-        h_numA += 1;                                                     // :443
+        const double *hsl;
+        SBTV_TRY(run.wait(outer, &hsl));
+        run.numA += 1;                                                   // :443
         ctx->calls += 2;                                                 // invLS, A
         const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :444
         if (objective) objective[outer] = f;
         if (mses && td) mses[outer] = hsl[4] / (double)C;                // :446-449
         if (distance) distance[outer - 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[1]);   // :451
-        if (times) times[outer] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (outer > 1) {                                                 // :453
-            double crit;
-            if (opts->stopcriterion == 1)
-                crit = fabs(f - obj_prev) / obj_prev;                    // :458
-            else if (opts->stopcriterion == 2)
-                crit = fabs(sqrt(hsl[5]) / sqrt(hsl[3]));                // :462
-            else
-                crit = f;                                                // :465
-            stop = crit < opts->tolA;                                    // :472
-        }
+        if (times) times[outer] = run.seconds();
+        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[5], hsl[3], opts->tolA);
         obj_prev = f;
         return 0;
     };
     int last = 0;
     SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SBTV_TRY(loop_timing(ctx, 0.0, 0, 1, P));
+    SBTV_TRY(run.finish(P, last, nullptr, nullptr));                     // the result: xw = s + we, and the image xi
     hipLaunchKernelGGL(wav_sum_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sbuf[last & 1],
                        (const double *)wbuf[last & 1], xw_out_dev, C);
     SBTV_HIP(ctx, hipGetLastError());
     if (x_out_dev)
         SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xibuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (numA) *numA = h_numA;
-    if (numAt) *numAt = h_numAt;
-    if (n_outer) *n_outer = last;
     return 0;
+}
+
+// item b of a batch as its solver sees it (device pointers)
+struct AdmmItem {
+    const double *y, *mask, *tru, *x_init;
+    double *x;
+};
+
+// What sbtv_CSALSA_v2, sbtv_CoRAL_v2 and sbtv_SALSA_masked do once their arguments are checked.  Independent images go to
+// the lanes of this context (`sharded`, group.hip) when it has them.  Else the arrays are staged and the images solved one
+// after another by one(b, item, spec): optimistic prox launches first (unless bit 1 of `speculate` asks for exact ones),
+// exact ones if the rule fired early.
+template <class Sharded, class One>
+int admm_batch(sbtv_ctx *ctx, int M, int N, int batch, const sbtv_salsa_opts *opts, const double *y, const double *mask,
+               const double *true_x, const double *x_init, double *x_out, int flags, Sharded &&sharded, One &&one) {
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
+    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {
+        LaneCall lc(ctx, lg);
+        return lc.done(sharded(lg), batch);
+    }
+    const size_t P = (size_t)M * N, cnt = P * batch;
+    const double *yd = nullptr, *md = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "admm.in.mask", mask, cnt, flags, &md));
+    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
+    double *xo = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
+    for (int b = 0; b < batch; ++b) {
+        const size_t o = (size_t)b * P;
+        const AdmmItem it{yd + o, off(md, o), off(td, o), off(xi, o), xo + o};
+        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) { return one(b, it, spec); }));
+    }
+    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return canary_epilogue(ctx, 0);
 }
 
 }  // namespace
@@ -1417,37 +1373,21 @@ int sbtv_CSALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, cons
     for (int b = 0; b < batch; ++b)
         if (!(mu1[b] > 0.0) || !(mu2[b] > 0.0))
             return fail(ctx, SBTV_ERR_MISSING_LS, "(A^T A + mu I)^(-1) must be specified: mu1, mu2 must be > 0");
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
-        LaneCall lc(ctx, lg);
-        return lc.done(csalsa_sharded(lg, y, M, N, batch, taps, taille, mu1, mu2, sigma, epsilon, continuationfactor, opts,
-                                      true_x, x_init, x_out, objective, distance1, distance2, criterion, times, mses, numA,
-                                      numAt, n_outer, flags), batch);
-    }
-    const size_t P = (size_t)M * N, cnt = P * batch;
-    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
-    double *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const int mi = opts->maxiter;
-    for (int b = 0; b < batch; ++b) {
-        const size_t o = (size_t)b * P, r = (size_t)b * mi;
-        // optimistic prox launches first (unless bit 1 of `speculate` asks for exact ones); exact ones if the rule fired early
-        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
-            return csalsa_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, mu1[b], mu2[b], sigma[b],
-                              epsilon ? epsilon[b] : 0.0, continuationfactor, opts, td ? td + o : nullptr,
-                              xi ? xi + o : nullptr, xo + o, objective ? objective + r : nullptr,
-                              distance1 ? distance1 + r : nullptr, distance2 ? distance2 + r : nullptr,
-                              criterion ? criterion + r : nullptr, times ? times + r : nullptr, mses ? mses + r : nullptr,
-                              numA ? numA + b : nullptr, numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
-        }));
-    }
-    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
+    const size_t t2 = (size_t)taille * taille;
+    return admm_batch(
+        ctx, M, N, batch, opts, y, nullptr, true_x, x_init, x_out, flags,
+        [&](sbtv_group *lg) {
+            return csalsa_sharded(lg, y, M, N, batch, taps, taille, mu1, mu2, sigma, epsilon, continuationfactor, opts, true_x,
+                                  x_init, x_out, objective, distance1, distance2, criterion, times, mses, numA, numAt,
+                                  n_outer, flags);
+        },
+        [&](int b, const AdmmItem &it, bool spec) {
+            const size_t r = (size_t)b * opts->maxiter;                  // every trace row has maxiter entries
+            return csalsa_one(ctx, it.y, M, N, taps + b * t2, taille, mu1[b], mu2[b], sigma[b], epsilon ? epsilon[b] : 0.0,
+                              continuationfactor, opts, it.tru, it.x_init, it.x, off(objective, r), off(distance1, r),
+                              off(distance2, r), off(criterion, r), off(times, r), off(mses, r), off(numA, b), off(numAt, b),
+                              off(n_outer, b), spec);
+        });
 }
 
 int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
@@ -1462,35 +1402,19 @@ int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const
     for (int b = 0; b < batch; ++b)
         if (!(mu1[b] > 0.0) || !(mu2[b] > 0.0) || (mu_ls && !(mu_ls[b] > 0.0)))
             return fail(ctx, SBTV_ERR_MISSING_LS, "(A^T A + mu I)^(-1) must be specified: mu1, mu2 must be > 0");
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
-        LaneCall lc(ctx, lg);
-        return lc.done(coral_sharded(lg, y, M, N, batch, taps, taille, tau1, tau2, mu1, mu2, mu_ls, TViters2, opts, true_x,
-                                     x_init, x_out, objective, distance, times, mses, numA, numAt, n_outer, flags), batch);
-    }
-    const size_t P = (size_t)M * N, cnt = P * batch;
-    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
-    double *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const int mi = opts->maxiter;
-    for (int b = 0; b < batch; ++b) {
-        const size_t o = (size_t)b * P;
-        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
-            return coral_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, tau1[b], tau2[b], mu1[b], mu2[b],
-                             mu_ls ? mu_ls[b] : mu1[b] + mu2[b], TViters2, opts, td ? td + o : nullptr, xi ? xi + o : nullptr,
-                             xo + o, objective ? objective + (size_t)b * (mi + 1) : nullptr,
-                             distance ? distance + (size_t)b * mi * 2 : nullptr, times ? times + (size_t)b * (mi + 1) : nullptr,
-                             mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
-                             numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
-        }));
-    }
-    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
+    const size_t t2 = (size_t)taille * taille, mi = (size_t)opts->maxiter;
+    return admm_batch(
+        ctx, M, N, batch, opts, y, nullptr, true_x, x_init, x_out, flags,
+        [&](sbtv_group *lg) {
+            return coral_sharded(lg, y, M, N, batch, taps, taille, tau1, tau2, mu1, mu2, mu_ls, TViters2, opts, true_x, x_init,
+                                 x_out, objective, distance, times, mses, numA, numAt, n_outer, flags);
+        },
+        [&](int b, const AdmmItem &it, bool spec) {
+            return coral_one(ctx, it.y, M, N, taps + b * t2, taille, tau1[b], tau2[b], mu1[b], mu2[b],
+                             mu_ls ? mu_ls[b] : mu1[b] + mu2[b], TViters2, opts, it.tru, it.x_init, it.x,
+                             off(objective, b * (mi + 1)), off(distance, b * mi * 2), off(times, b * (mi + 1)),
+                             off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b), spec);
+        });
 }
 
 int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch, const double *taps,
@@ -1510,35 +1434,18 @@ int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
         for (size_t i = 0; i < cnt; ++i)
             if (!(mask[i] >= 0.0) || std::isinf(mask[i]))
                 return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: the mask must be finite and non-negative");
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
-        LaneCall lc(ctx, lg);
-        return lc.done(masked_sharded(lg, y, mask, M, N, batch, taps, taille, tau, mu1, mu2, opts, true_x, x_init, x_out,
-                                      objective, distance, times, mses, numA, numAt, n_outer, flags), batch);
-    }
-    const double *yd = nullptr, *md = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "admm.in.mask", mask, cnt, flags, &md));
-    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
-    double *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const int mi = opts->maxiter;
-    for (int b = 0; b < batch; ++b) {
-        const size_t o = (size_t)b * P;
-        SBTV_TRY(solve_with_exact_repeat(ctx, !(opts->speculate & 2), [&](bool spec) {
-            return masked_one(ctx, yd + o, md + o, M, N, taps + (size_t)b * taille * taille, taille, tau[b], mu1[b], mu2[b],
-                              opts, td ? td + o : nullptr, xi ? xi + o : nullptr, xo + o,
-                              objective ? objective + (size_t)b * (mi + 1) : nullptr,
-                              distance ? distance + (size_t)b * mi * 2 : nullptr, times ? times + (size_t)b * (mi + 1) : nullptr,
-                              mses ? mses + (size_t)b * (mi + 1) : nullptr, numA ? numA + b : nullptr,
-                              numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr, spec);
-        }));
-    }
-    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
+    const size_t t2 = (size_t)taille * taille, mi = (size_t)opts->maxiter;
+    return admm_batch(
+        ctx, M, N, batch, opts, y, mask, true_x, x_init, x_out, flags,
+        [&](sbtv_group *lg) {
+            return masked_sharded(lg, y, mask, M, N, batch, taps, taille, tau, mu1, mu2, opts, true_x, x_init, x_out, objective,
+                                  distance, times, mses, numA, numAt, n_outer, flags);
+        },
+        [&](int b, const AdmmItem &it, bool spec) {
+            return masked_one(ctx, it.y, it.mask, M, N, taps + b * t2, taille, tau[b], mu1[b], mu2[b], opts, it.tru, it.x_init,
+                              it.x, off(objective, b * (mi + 1)), off(distance, b * mi * 2), off(times, b * (mi + 1)),
+                              off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b), spec);
+        });
 }
 
 int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
@@ -1547,14 +1454,7 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
                        double *x_out, double *objective, double *distance, double *times, double *mses, int *numA,
                        int *numAt, int *n_outer, int flags) {
     if (!ctx) return SBTV_ERR_BADARG;
-    if (!y || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: missing required argument");
-    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
-    if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
-        return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
-    if (opts->initialization == 33333 && !xw_init) return fail(ctx, SBTV_ERR_INIT, "Initialization = array but xw_init is NULL");
-    if (opts->maxiter < 1) return fail(ctx, SBTV_ERR_MAXITER, "SALSA_wavelet: maxiter must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_common(ctx, "SALSA_wavelet", y, taps, opts, xw_init, M, N, batch, taille, "xw_init", false));   // no TV prox
     if (!tau || !mu || !xw_out) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: missing required argument");
     WavPlan wp;
     SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
@@ -1572,15 +1472,11 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
     double *xwo = nullptr, *xo = nullptr;
     SBTV_TRY(stage_out_buf(ctx, "wav.out.xw", xw_out, ccnt, flags, &xwo));
     if (x_out) SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const int mi = opts->maxiter;
-    for (int b = 0; b < batch; ++b) {
-        const size_t o = (size_t)b * P, oc = (size_t)b * C;
-        SBTV_TRY(wavelet_one(ctx, yd + o, M, N, taps + (size_t)b * taille * taille, taille, wp, tau[b], mu[b], opts,
-                             td ? td + oc : nullptr, xi ? xi + oc : nullptr, xwo + oc, xo ? xo + o : nullptr,
-                             objective ? objective + (size_t)b * (mi + 1) : nullptr, distance ? distance + (size_t)b * mi : nullptr,
-                             times ? times + (size_t)b * (mi + 1) : nullptr, mses ? mses + (size_t)b * (mi + 1) : nullptr,
-                             numA ? numA + b : nullptr, numAt ? numAt + b : nullptr, n_outer ? n_outer + b : nullptr));
-    }
+    const size_t mi = (size_t)opts->maxiter;
+    for (size_t b = 0; b < (size_t)batch; ++b)
+        SBTV_TRY(wavelet_one(ctx, yd + b * P, M, N, taps + b * taille * taille, taille, wp, tau[b], mu[b], opts, off(td, b * C),
+                             off(xi, b * C), xwo + b * C, off(xo, b * P), off(objective, b * (mi + 1)), off(distance, b * mi),
+                             off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
     SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
     if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));

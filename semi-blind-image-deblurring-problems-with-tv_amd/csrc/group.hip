@@ -353,8 +353,17 @@ static inline int active_shards(sbtv_group *g, int n_items) {
     g->rv.reset(ns);
     return ns;
 }
-template <class T>
-static inline T *off(T *p, size_t o) { return p ? p + o : p; }
+// The independent items of a call dealt to the active shards in contiguous blocks: fn(shard's context, first item, item
+// count) on one host thread per shard
+template <class F>
+static int for_shards(sbtv_group *g, int n_items, F fn) {
+    const int ns = active_shards(g, n_items);
+    return run_shards(g, ns, [&](int r) -> int {
+        int lo, hi;
+        block_of(n_items, ns, r, &lo, &hi);
+        return fn(g->ctxs[r], (size_t)lo, hi - lo);
+    });
+}
 
 int salsa_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, const double *taps, int taille,
                   const double *tau, const double *mu, const sbtv_salsa_opts *opts, const double *true_x,
@@ -364,13 +373,9 @@ int salsa_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, con
     if (!y || !tau || !mu || !opts || n_items < 1 || M < 2 || N < 2)
         return gfail(g, SBTV_ERR_BADARG, "SALSA_v2_sharded: missing required argument");
     if (!taps) return gfail(g, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    const int ns = active_shards(g, n_items);
     const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)(opts->maxiter > 0 ? opts->maxiter : 0);
-    return run_shards(g, ns, [&](int r) -> int {
-        int lo, hi;
-        block_of(n_items, ns, r, &lo, &hi);
-        const size_t b = (size_t)lo;
-        return sbtv_SALSA_v2(g->ctxs[r], y + b * P, M, N, hi - lo, taps + b * t2, taille, tau + b, mu + b, opts,
+    return for_shards(g, n_items, [&](sbtv_ctx *ctx, size_t b, int n) -> int {
+        return sbtv_SALSA_v2(ctx, y + b * P, M, N, n, taps + b * t2, taille, tau + b, mu + b, opts,
                              off(true_x, b * P), off(x_init, b * P), off(x_out, b * P), off(objective, b * (K + 1)),
                              off(distance, b * K), off(times, b * (K + 1)), off(mses, b * (K + 1)), off(numA, b),
                              off(numAt, b), off(n_outer, b), flags);
@@ -436,13 +441,9 @@ int fista_sharded(sbtv_group *g, const double *bimg, int M, int N, int n_items, 
     if (!g) return SBTV_ERR_BADARG;
     if (!bimg || !taps || !tau || !true_x || n_items < 1 || maxiters < 1 || M < 2 || N < 2)
         return gfail(g, SBTV_ERR_BADARG, "fista_tv_sharded: bad arguments (b, taps, tau, true are required)");
-    const int ns = active_shards(g, n_items);
     const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)maxiters;
-    return run_shards(g, ns, [&](int r) -> int {
-        int lo, hi;
-        block_of(n_items, ns, r, &lo, &hi);
-        const size_t b = (size_t)lo;
-        return sbtv_fista_tv(g->ctxs[r], bimg + b * P, M, N, hi - lo, taps + b * t2, taille, tau + b, L, prox_iters,
+    return for_shards(g, n_items, [&](sbtv_ctx *ctx, size_t b, int n) -> int {
+        return sbtv_fista_tv(ctx, bimg + b * P, M, N, n, taps + b * t2, taille, tau + b, L, prox_iters,
                              stopcriterion, tolerance, maxiters, zero_start, true_x + b * P, off(x_out, b * P),
                              off(objective, b * K), off(mses, b * K), off(n_iter, b), flags);
     });
@@ -457,13 +458,9 @@ int csalsa_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, co
     if (!g) return SBTV_ERR_BADARG;
     if (!y || !taps || !mu1 || !mu2 || !sigma || !opts || n_items < 1 || M < 2 || N < 2)
         return gfail(g, SBTV_ERR_BADARG, "CSALSA_v2_sharded: missing required argument");
-    const int ns = active_shards(g, n_items);
     const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)(opts->maxiter > 0 ? opts->maxiter : 0);
-    return run_shards(g, ns, [&](int r) -> int {
-        int lo, hi;
-        block_of(n_items, ns, r, &lo, &hi);
-        const size_t b = (size_t)lo;
-        return sbtv_CSALSA_v2(g->ctxs[r], y + b * P, M, N, hi - lo, taps + b * t2, taille, mu1 + b, mu2 + b, sigma + b,
+    return for_shards(g, n_items, [&](sbtv_ctx *ctx, size_t b, int n) -> int {
+        return sbtv_CSALSA_v2(ctx, y + b * P, M, N, n, taps + b * t2, taille, mu1 + b, mu2 + b, sigma + b,
                               off(epsilon, b), continuationfactor, opts, off(true_x, b * P), off(x_init, b * P),
                               off(x_out, b * P), off(objective, b * K), off(distance1, b * K), off(distance2, b * K),
                               off(criterion, b * K), off(times, b * K), off(mses, b * K), off(numA, b), off(numAt, b),
@@ -480,13 +477,9 @@ int coral_sharded(sbtv_group *g, const double *y, int M, int N, int n_items, con
     if (!g) return SBTV_ERR_BADARG;
     if (!y || !taps || !tau1 || !tau2 || !mu1 || !mu2 || !opts || n_items < 1 || M < 2 || N < 2)
         return gfail(g, SBTV_ERR_BADARG, "CoRAL_v2_sharded: missing required argument");
-    const int ns = active_shards(g, n_items);
     const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)(opts->maxiter > 0 ? opts->maxiter : 0);
-    return run_shards(g, ns, [&](int r) -> int {
-        int lo, hi;
-        block_of(n_items, ns, r, &lo, &hi);
-        const size_t b = (size_t)lo;
-        return sbtv_CoRAL_v2(g->ctxs[r], y + b * P, M, N, hi - lo, taps + b * t2, taille, tau1 + b, tau2 + b, mu1 + b,
+    return for_shards(g, n_items, [&](sbtv_ctx *ctx, size_t b, int n) -> int {
+        return sbtv_CoRAL_v2(ctx, y + b * P, M, N, n, taps + b * t2, taille, tau1 + b, tau2 + b, mu1 + b,
                              mu2 + b, off(mu_ls, b), TViters2, opts, off(true_x, b * P), off(x_init, b * P),
                              off(x_out, b * P), off(objective, b * (K + 1)), off(distance, b * K * 2),
                              off(times, b * (K + 1)), off(mses, b * (K + 1)), off(numA, b), off(numAt, b),
@@ -502,13 +495,9 @@ int masked_sharded(sbtv_group *g, const double *y, const double *mask, int M, in
     if (!g) return SBTV_ERR_BADARG;
     if (!y || !mask || !taps || !tau || !mu1 || !mu2 || !opts || n_items < 1 || M < 2 || N < 2)
         return gfail(g, SBTV_ERR_BADARG, "SALSA_masked_sharded: missing required argument");
-    const int ns = active_shards(g, n_items);
     const size_t P = (size_t)M * N, t2 = (size_t)taille * taille, K = (size_t)(opts->maxiter > 0 ? opts->maxiter : 0);
-    return run_shards(g, ns, [&](int r) -> int {
-        int lo, hi;
-        block_of(n_items, ns, r, &lo, &hi);
-        const size_t b = (size_t)lo;
-        return sbtv_SALSA_masked(g->ctxs[r], y + b * P, mask + b * P, M, N, hi - lo, taps + b * t2, taille, tau + b, mu1 + b,
+    return for_shards(g, n_items, [&](sbtv_ctx *ctx, size_t b, int n) -> int {
+        return sbtv_SALSA_masked(ctx, y + b * P, mask + b * P, M, N, n, taps + b * t2, taille, tau + b, mu1 + b,
                                  mu2 + b, opts, off(true_x, b * P), off(x_init, b * P), off(x_out, b * P),
                                  off(objective, b * (K + 1)), off(distance, b * K * 2), off(times, b * (K + 1)),
                                  off(mses, b * (K + 1)), off(numA, b), off(numAt, b), off(n_outer, b), flags);

@@ -202,6 +202,9 @@ inline int pinned_get(sbtv_ctx *ctx, size_t bytes, T **host, T **dev) {
     *dev = static_cast<T *>(d);
     return 0;
 }
+// item o of an optional per-item array: p + o, and null stays null
+template <class T>
+inline T *off(T *p, size_t o) { return p ? p + o : p; }
 // do the arrays [a, a + n) and [b, b + n) overlap (null: no)
 inline bool overlaps(const double *a, const double *b, size_t n) { return a && b && a < b + n && b < a + n; }
 // end of a C-ABI call: with SBTV_CANARY=1 verify every guard band (one tiny kernel + a sync), else return rc

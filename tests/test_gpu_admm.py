@@ -253,6 +253,54 @@ def test_coral_split_equals_salsa_fixed_point(ctx, cman256):
     assert o.PSNR(xs, xc) > 45.0
 
 
+def test_item_of_a_batch_equals_its_single_call_bit_for_bit():
+    """Item b of a batch of three on a one-stream context (set_lanes(1): the images are solved one after another by the entry
+    point's own loop) against the single call of item b: x, every trace but times, numA, numAt, and with the trace lengths
+    the stopping iteration.  The three problems stop at different iterations, all before MAXITERA (the oracle: C-SALSA after
+    18, 36 and 39, CoRAL after 10, 12 and 34), so that an offset or a stop decision shared between items cannot hide."""
+    import sbtv
+    import sbtv_oracle as o
+    K = 60
+    xs = np.stack([synth_image(64, 64, 20 + b) for b in range(3)])
+    sts = [o.demo_setup("gaussian", xs[b], np.random.default_rng(b).standard_normal(xs[b].shape), evMax=1.0,
+                        true_params=(0.4, 0.3)) for b in range(3)]
+    ys = np.stack([st["y"] for st in sts])
+    A = sbtv.BlurOperator(sbtv.Gaussian_psf(7, 0.4, 0.3))
+    sig = [f * st["sigma"] for f, st in zip((1.0, 1.5, 2.5), sts)]
+    taus = [0.03 * st["sigma"] ** 2 * f for f, st in zip((1, 4, 16), sts)]
+
+    def cs(c, y, s, x):
+        return sbtv.csalsa(y, A, 1.0, 1.0, s, "AT", A.T, "LS", A.invLS, "TVINITIALIZATION", 1, "TVITERS", 10, "TRUE_X", x,
+                           "MAXITERA", K, "STOPCRITERION", 3, "TOLERANCEA", 1e-3, "VERBOSE", 0, ctx=c)
+
+    def co(c, y, t, x):
+        t1, t2 = ([0.4 * v for v in t], [0.6 * v for v in t]) if isinstance(t, list) else (0.4 * t, 0.6 * t)
+        return sbtv.CoRAL(y, A, t1, t2, "MU1", 0.003, "MU2", 0.004, "AT", A.T, "LS", A.LS(0.007), "TVINITIALIZATION1", 1,
+                          "TVITERS1", 10, "TVINITIALIZATION2", 1, "TVITERS2", 10, "TRUE_X", x, "MAXITERA", K,
+                          "STOPCRITERION", 1, "TOLERANCEA", 3e-4, "VERBOSE", 0, ctx=c)
+
+    c = sbtv.Context(0)
+    try:
+        c.set_lanes(1)
+        for fn, par, names, extra in (
+                (cs, sig, ("x", "numA", "numAt", "objective", "distance1", "distance2", "criterion", "times", "mses"), 0),
+                (co, taus, ("x", "numA", "numAt", "objective", "distance", "times", "mses"), 1)):
+            both = fn(c, ys, par, xs)
+            assert len(both) == len(names)
+            n_outer = [len(both[3][b]) - extra for b in range(3)]
+            print(fn.__name__, "n_outer", n_outer)
+            assert len(set(n_outer)) > 1 and max(n_outer) < K, n_outer
+            for b in range(3):
+                one = fn(c, ys[b], par[b], xs[b])
+                for q, name in enumerate(names):
+                    if name == "times":
+                        assert len(both[q][b]) == len(one[q])
+                        continue
+                    np.testing.assert_array_equal(both[q][b], one[q], err_msg=f"{fn.__name__}: {name} of item {b}")
+    finally:
+        c.close()
+
+
 def test_admm_error_paths(ctx):
     import sbtv
     x = synth_image(32, 32, 1)

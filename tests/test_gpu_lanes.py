@@ -178,12 +178,26 @@ def test_csalsa_and_coral_lanes_and_sharded_are_bit_equal_to_one_stream(ctx1, ct
     co = lambda c: sbtv.CoRAL(ys, A, [0.4 * t for t in taus], [0.6 * t for t in taus], "MU1", 0.003, "MU2", 0.004,
                               "AT", A.T, "LS", A.LS(0.007), "TVINITIALIZATION1", 1, "TVITERS1", 10, "TVINITIALIZATION2", 1,
                               "TVITERS2", 10, "TRUE_X", xs, "MAXITERA", 40, "TOLERANCEA", 1e-4, "STOPCRITERION", 1, ctx=c)
+    # what each returns, in order; C-SALSA rows have up to maxiter entries, CoRAL's objective and mses one more, its
+    # distance two per iteration
+    names = {cs: ("x", "numA", "numAt", "objective", "distance1", "distance2", "criterion", "times", "mses"),
+             co: ("x", "numA", "numAt", "objective", "distance", "times", "mses")}
     for fn in (cs, co):
         one, two, shd = fn(ctx1), fn(ctx2), fn(group2)
+        assert len(one) == len(names[fn])
         for got in (two, shd):
             np.testing.assert_array_equal(got[0], one[0])
-            for b in range(3):
-                np.testing.assert_array_equal(got[3][b], one[3][b])      # objective traces
+            for q, name in enumerate(names[fn]):
+                if name in ("x", "times"):
+                    continue
+                for b in range(3):
+                    np.testing.assert_array_equal(got[q][b], one[q][b], err_msg=f"{name} of image {b}")
+        for b in range(3):
+            n = len(one[3][b])                                           # every trace is as long as the run was
+            want = {"distance": 2 * (n - 1)} if fn is co else {}
+            for q, name in enumerate(names[fn]):
+                if name not in ("x", "numA", "numAt"):
+                    assert np.asarray(one[q][b]).size == want.get(name, n), (name, b)
 
 
 def test_lanes_stress_alternating_batches_and_entry_points(ctx1, ctx2):

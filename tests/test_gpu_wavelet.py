@@ -133,6 +133,64 @@ def test_refusals(ctx):
     assert e.value.code == -7
     with pytest.raises(sbtv.SbtvError):                                   # levels far beyond any shift width
         sbtv.mrdwt_TI2D(x, d4, 80, ctx=ctx)
+    # the checks SALSA_wavelet shares with the TV front-ends, through the bare binding (the keyword interface answers some of
+    # them itself): code and message
+    def bad_stop(so):
+        so.stopcriterion = 4
+
+    def array_start(so):
+        so.initialization = 33333
+
+    def no_iterations(so):
+        so.maxiter = 0
+    for edit, kw, code, text in ((bad_stop, {}, -6, "Unknown stopping criterion"),
+                                 (array_start, {}, -7, "Initialization = array but xw_init is NULL"),
+                                 (no_iterations, {}, -3, "SALSA_wavelet: maxiter must be positive"),
+                                 (None, {"y": np.ones((6, 6))}, -10, "Mask does not fit inside array")):
+        with pytest.raises(sbtv.SbtvError) as e:
+            _raw_solve(ctx, p, op, edit, **kw)
+        assert (e.value.code, e.value.msg) == (code, text)
+    with pytest.raises(sbtv.SbtvError) as e:                              # MAXITERA 0 through the keyword interface too
+        sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", p["mu"], "WAVELET", p["h"], "AT", op.T, "LEVELS", 4, "MAXITERA", 0, ctx=ctx)
+    assert (e.value.code, e.value.msg) == (-3, "SALSA_wavelet: maxiter must be positive")
+
+    # there is no TV prox in this solver: TViters = 0 (which the TV front-ends refuse) is accepted and changes nothing
+    def no_tv(so):
+        so.TViters = 0
+    xw0, obj0 = _raw_solve(ctx, p, op, no_tv)
+    xw5, obj5 = _raw_solve(ctx, p, op, None)
+    assert obj0[0] > obj0[-1] > 0
+    np.testing.assert_array_equal(obj0, obj5)
+    np.testing.assert_array_equal(xw0, xw5)
+    got = sbtv.SALSA_wavelet(p["y"], op, p["tau"], "MU", p["mu"], "WAVELET", p["h"], "TOLERANCEA", 0.0, *common, ctx=ctx)
+    np.testing.assert_array_equal(obj0, got[4])
+
+
+def _raw_solve(ctx, p, op, edit, y=None):
+    """sbtv_SALSA_wavelet through the bare binding on problem p (levels 4, three iterations, criterion 1 with tolerance 0):
+    `edit` changes the options after their defaults.  Returns (xw as the C-ABI stores it, objective)."""
+    import ctypes as C
+    from sbtv import _lib as L
+    y = p["y"] if y is None else y
+    M, N = y.shape
+    K, nbands = 3, 10
+    so = L.sbtv_salsa_opts()
+    ctx.lib.sbtv_salsa_opts_default(C.byref(so))
+    so.stopcriterion, so.maxiter, so.tolA, so.initialization = 1, K, 0.0, 0
+    if edit:
+        edit(so)
+    ycm = np.ascontiguousarray(y.T, dtype=np.float64)
+    h = np.ascontiguousarray(p["h"], dtype=np.float64)
+    taps = op._cm(1)
+    tau, mu = L.dvec(p["tau"], 1), L.dvec(p["mu"], 1)
+    xw = np.zeros(nbands * M * N)
+    objective, distance, times = np.zeros(K + 1), np.zeros(K), np.zeros(K + 1)
+    numA, numAt, nout = (C.c_int * 1)(), (C.c_int * 1)(), (C.c_int * 1)()
+    ctx.check(ctx.lib.sbtv_SALSA_wavelet(ctx.h, L.vptr(ycm), M, N, 1, L.vptr(taps), op.taille, L.vptr(h), h.size, 4, tau[1], mu[1],
+                                         C.byref(so), None, None, L.vptr(xw), None, L.vptr(objective), L.vptr(distance),
+                                         L.vptr(times), None, numA, numAt, nout, L.SBTV_HOST_PTRS))
+    assert nout[0] == K
+    return xw, objective
 
 
 def _solve(ctx, p, **kw):
