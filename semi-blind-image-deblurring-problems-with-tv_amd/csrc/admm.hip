@@ -419,109 +419,16 @@ inline int ad_blocks(size_t P) {
     return nb < 1 ? 1 : (int)nb;
 }
 
-// everything one single-image solve shares: plans, spectra of the PSF and of y
-struct AdmmCommon {
-    FftPlan fp;
-    size_t P;
-    double2 *S, *Hs, *Ys;
-    double *taps_d;
-    double inv_scale, parseval;
-    bool spectral = false;
-};
-
-// U = fft2(in + add) in the layout of H, by way of the packed spectrum S
-int admm_spectrum(sbtv_ctx *ctx, const AdmmCommon &c, const double *in, const double *add, double2 *S, double2 *U) {
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    a.op = OP_NONE;
-    SBTV_TRY(fft_cols_fwd(ctx, c.fp, in, add, S));
-    SBTV_TRY(fft_rows(ctx, c.fp, S, S, a));
-    return spec_unpack(ctx, c.fp, S, U);
-}
-
-int admm_common(sbtv_ctx *ctx, int M, int N, const double *taps, int taille, const double *yd, AdmmCommon *c) {
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
-    SBTV_TRY(fft_plan(ctx, M, N, 1, &c->fp));
-    c->P = (size_t)M * N;
-    SBTV_TRY(ws_get_t(ctx, "admm.S", c->fp.s_img, &c->S));
-    SBTV_TRY(ws_get_t(ctx, "admm.H", c->fp.u_img, &c->Hs));
-    SBTV_TRY(ws_get_t(ctx, "admm.Y", c->fp.u_img, &c->Ys));
-    SBTV_TRY(ws_get_t(ctx, "admm.taps", (size_t)taille * taille, &c->taps_d));
-    SBTV_HIP(ctx, hipMemcpyAsync(c->taps_d, taps, sizeof(double) * taille * taille, hipMemcpyHostToDevice, ctx->stream));
+// everything one single-image solve shares: the operator layer "admm" with the spectra of the PSF and (yd given) of y
+int admm_common(sbtv_ctx *ctx, int M, int N, const double *taps, int taille, const double *yd, BlurOp *c) {
+    SBTV_TRY(check_even_pixels(ctx, M, N));
+    SBTV_TRY(op_open(ctx, "admm", M, N, 1, "Y", c));
+    double *taps_d = nullptr;
+    SBTV_TRY(ws_get_t(ctx, "admm.taps", (size_t)taille * taille, &taps_d));
+    SBTV_HIP(ctx, hipMemcpyAsync(taps_d, taps, sizeof(double) * taille * taille, hipMemcpyHostToDevice, ctx->stream));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    c->inv_scale = 1.0 / ((double)c->fp.n1 * N);
-    c->parseval = 1.0 / ((double)M * N);
-    SBTV_TRY(psf_spectrum(ctx, c->fp, c->taps_d, taille, c->Hs));
-    if (yd) SBTV_TRY(admm_spectrum(ctx, *c, yd, nullptr, c->S, c->Ys));
-    return 0;
-}
-
-// out = real(ifft2(op(H) .* fft2(in)))
-int admm_apply(sbtv_ctx *ctx, const AdmmCommon &c, int op, const double *in, double *out) {
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    a.dir_inv = 1;
-    a.op = op;
-    a.H = c.Hs;
-    SBTV_TRY(fft_cols_fwd(ctx, c.fp, in, nullptr, c.S));
-    SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-    return fft_cols_inv(ctx, c.fp, c.S, out, c.inv_scale);
-}
-
-// out = real(ifft2((conj(H) Y + mu fft2(in + add)) / (|H|^2 + mu))), the row pass OP_SALSA (mu: device); its residual sum
-// against Y goes to acc, and c.S is left holding N times the column transform of `out`
-int admm_solve(sbtv_ctx *ctx, const AdmmCommon &c, const double *in, const double *add, const double2 *Y, const double *mu,
-               double *acc, double *out) {
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    a.dir_inv = 1;
-    a.op = OP_SALSA;
-    a.H = c.Hs;
-    a.Y = Y;
-    a.mu = mu;
-    a.acc = acc;
-    SBTV_TRY(fft_cols_fwd(ctx, c.fp, in, add, c.S));
-    SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-    return fft_cols_inv(ctx, c.fp, c.S, out, c.inv_scale);
-}
-
-// acc = the partial sums of ||H fft2(x) - fft2(y)||^2 (OP_RESID: nothing is stored)
-int admm_resid(sbtv_ctx *ctx, const AdmmCommon &c, const double *x, double *acc) {
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    a.op = OP_RESID;
-    a.H = c.Hs;
-    a.Y = c.Ys;
-    a.acc = acc;
-    SBTV_TRY(fft_cols_fwd(ctx, c.fp, x, nullptr, c.S));
-    return fft_rows(ctx, c.fp, c.S, nullptr, a);
-}
-
-int admm_init_x(sbtv_ctx *ctx, const AdmmCommon &c, int initialization, const double *yd, const double *xi, double *x) {
-    if (initialization == 0) {
-        SBTV_HIP(ctx, hipMemsetAsync(x, 0, sizeof(double) * c.P, ctx->stream));   // AT(zeros) == 0
-    } else if (initialization == 2) {
-        SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, yd, x));                            // x = ATy
-    } else {
-        SBTV_HIP(ctx, hipMemcpyAsync(x, xi, sizeof(double) * c.P, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    return 0;
-}
-
-// x_init_name: what the caller's start array is called in its message; tv: the entry point runs a TV prox of TViters iterations
-int check_common(sbtv_ctx *ctx, const char *who, const double *y, const double *taps, const sbtv_salsa_opts *opts,
-                 const double *x_init, int M, int N, int batch, int taille, const char *x_init_name = "x_init", bool tv = true) {
-    if (!y || !opts || batch < 1) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": missing required argument");
-    if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    if (opts->stopcriterion < 1 || opts->stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Unknown stopping criterion");
-    if (opts->initialization != 0 && opts->initialization != 2 && opts->initialization != 33333)
-        return fail(ctx, SBTV_ERR_INIT, "Unknown 'Initialization' option");
-    if (opts->initialization == 33333 && !x_init)
-        return fail(ctx, SBTV_ERR_INIT, std::string("Initialization = array but ") + x_init_name + " is NULL");
-    if (tv && opts->TViters <= 0) return fail(ctx, SBTV_ERR_MAXITER, std::string(who) + ": TViters must be positive");
-    if (opts->maxiter < 1) return fail(ctx, SBTV_ERR_MAXITER, std::string(who) + ": maxiter must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(psf_spectrum(ctx, c->fp, taps_d, taille, c->Hs));
+    if (yd) SBTV_TRY(op_spectrum(ctx, c->fp, yd, nullptr, c->S, c->Ys));
     return 0;
 }
 
@@ -581,9 +488,10 @@ struct AdmmProx {
 // slot tells the host (which runs one iteration ahead) when the slot of an iteration holds its scalars.  Beside them: the
 // clock of `times`, the operator counts, the Chambolle iterations of sbtv_last_timing.
 struct AdmmRun {
-    static constexpr int SLOT = 96;                // doubles per slot; the last two take the iteration counts of exact proxes
+    static constexpr int NSUM = 94;                // doubles per slot, then the iteration counts of up to two exact proxes
     sbtv_ctx *ctx = nullptr;
-    double *hs = nullptr;                          // the two slots
+    double *hs[2] = {nullptr, nullptr};            // the two slots (pinned): the sums ...
+    int *khs[2] = {nullptr, nullptr};              // ... and the counts, at [0] and [2]
     hipEvent_t ev[2] = {nullptr, nullptr};
     long long opt_iters[2] = {0, 0};
     std::chrono::steady_clock::time_point t0;
@@ -600,9 +508,19 @@ struct AdmmRun {
         numA_out = numA_o;
         numAt_out = numAt_o;
         n_outer_out = n_outer_o;
+        PinnedLayout lay;
+        PinnedField<double> fs[2];
+        PinnedField<int> fk[2];
+        for (int s = 0; s < 2; ++s) {
+            fs[s] = lay.add<double>(NSUM);
+            fk[s] = lay.add<int>(4);
+        }
         void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * 2 * SLOT, &pz));
-        hs = static_cast<double *>(pz);
+        SBTV_TRY(pinned_get(ctx, lay.bytes(), &pz));
+        for (int s = 0; s < 2; ++s) {
+            hs[s] = fs[s].at(pz);
+            khs[s] = fk[s].at(pz);
+        }
         for (auto &e : ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         return 0;
     }
@@ -614,9 +532,9 @@ struct AdmmRun {
     }
     // before the loop: the first n doubles of `sums`, read back through slot 0
     int fetch(const double *sums, int n, const double **h) {
-        SBTV_HIP(ctx, hipMemcpyAsync(hs, sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        SBTV_HIP(ctx, hipMemcpyAsync(hs[0], sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        *h = hs;
+        *h = hs[0];
         return 0;
     }
     double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
@@ -624,8 +542,8 @@ struct AdmmRun {
     // its proxes were optimistic; exact ones hand the control blocks that count theirs (k0, k1: device)
     int publish(int outer, const double *sums, int n, long long iters, const ProxCtrl *k0 = nullptr,
                 const ProxCtrl *k1 = nullptr) {
-        double *hsl = hs + (outer & 1) * SLOT;
-        int *kh = reinterpret_cast<int *>(hsl + SLOT - 2);
+        double *hsl = hs[outer & 1];
+        int *kh = khs[outer & 1];
         kh[0] = kh[2] = 0;
         opt_iters[outer & 1] = iters;
         SBTV_HIP(ctx, hipGetLastError());
@@ -637,9 +555,9 @@ struct AdmmRun {
     }
     // head of process(outer): waits for the iteration's slot, books its Chambolle iterations
     int wait(int outer, const double **hsl) {
-        *hsl = hs + (outer & 1) * SLOT;
+        *hsl = hs[outer & 1];
         SBTV_HIP(ctx, hipEventSynchronize(ev[outer & 1]));
-        const int *kh = reinterpret_cast<const int *>(*hsl + SLOT - 2);
+        const int *kh = khs[outer & 1];
         prox_iters += opt_iters[outer & 1] + kh[0] + kh[2];
         return 0;
     }
@@ -659,26 +577,13 @@ struct AdmmRun {
     }
 };
 
-// The stop rule of SALSA_v2.m:453-472 (CoRAL_v2.m:435-453 is the same rule), from the second iteration on: the relative
-// change of the objective f (criterion 1), ||x - xprev|| / ||x|| from their squares num and den (2), f itself (3)
-inline bool salsa_stop(int stopcriterion, int outer, double f, double obj_prev, double num, double den, double tolA) {
-    if (outer <= 1) return false;                                        // :453
-    double crit;
-    if (stopcriterion == 1)
-        crit = fabs(f - obj_prev) / obj_prev;                            // :456
-    else if (stopcriterion == 2)
-        crit = fabs(sqrt(num) / sqrt(den));                              // :460
-    else
-        crit = f;                                                        // :464
-    return crit < tolA;                                                  // :472
-}
-
 // ------------------------------------------------------------------------------------------------
 int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, double mu1, double mu2,
                double sigma, double epsilon, double delta, const sbtv_salsa_opts *opts, const double *td,
                const double *xi, double *x_out_dev, double *objective, double *distance1, double *distance2,
                double *criterion, double *times, double *mses, int *numA, int *numAt, int *n_outer, bool spec_wanted) {
-    AdmmCommon c;
+    BlurOp c;
+    bool spectral = false;
     {
         FftPlan chk;
         SBTV_TRY(fft_plan(ctx, M, N, 1, &chk));
@@ -687,9 +592,8 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         const bool sp = delta == 1.0 && csalsa_spectral_wanted() && fft_rows_csalsa_ok(chk) && !(M & 1) &&
                         (size_t)M * N < ((size_t)1 << 31);
         SBTV_TRY(admm_common(ctx, M, N, taps, taille, sp ? yd : nullptr, &c));
-        c.spectral = sp;
+        spectral = sp;
     }
-    const bool spectral = c.spectral;
     const int K = opts->TViters;
     AdmmProx prox;
     SBTV_TRY(prox.plan(ctx, M, N, 1, "prox", K, opts));
@@ -724,7 +628,7 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
     run.numAt = 1;                                                       // ATy (:301)
     ctx->calls += 2;                                                     // AT(y), invLS(ATy, mu1) (:301,310)
     double *x = xbuf[0];
-    SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
+    SBTV_TRY(op_init_x(ctx, c, opts->initialization, yd, xi, x));
     if (opts->initialization == 0) ctx->calls += 1;
     if (opts->initialization == 2) run.numAt += 1;                       // :385
     SBTV_HIP(ctx, hipMemsetAsync(u, 0, sizeof(double) * P, ctx->stream));   // :404-408
@@ -736,7 +640,7 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
     SBTV_TRY(prox.arm(ctx, true));
 
     // state before the loop (:416-448): Ax, criterion(1), objective(1) = TV(x), mses(1), distances
-    SBTV_TRY(admm_apply(ctx, c, OP_MUL_H, x, Ax));
+    SBTV_TRY(op_apply(ctx, c, OP_MUL_H, x, Ax));
     run.numA += 2;                                                       // :421,445
     ctx->calls += 2;
     {
@@ -828,8 +732,8 @@ int csalsa_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps
         // r = mu1 (u+bu) + mu2 AT(y+v+bv) ; x = invLS(r, mu1)   (:467-471), all in one spectral pass:
         //   X = (conj(H) W + mu1 S) / (|H|^2 + mu1),  W = fft2(mu2 (y+v+bv)),  S = fft2(u+bu)
         hipLaunchKernelGGL(csalsa_w_kernel, dim3(nb), dim3(AB), 0, ctx->stream, yd, v, bv, par, w, P);
-        SBTV_TRY(admm_spectrum(ctx, c, w, nullptr, c.S, Ws));
-        SBTV_TRY(admm_solve(ctx, c, u, bu, Ws, par, acc, xn));           // mu1; the residual sum in acc is not used here
+        SBTV_TRY(op_spectrum(ctx, c.fp, w, nullptr, c.S, Ws));
+        SBTV_TRY(op_solve(ctx, c, u, bu, Ws, par, acc, xn));           // mu1; the residual sum in acc is not used here
         // u = prox_{TV/mu1}(x - bu), warm-started duals (:476)
         hipLaunchKernelGGL(ad_sub_kernel, dim3(nb), dim3(AB), 0, ctx->stream, xn, bu, g, P);
         SBTV_TRY(prox.run(ctx, g, u, spec, sums + 16, nullptr));
@@ -898,7 +802,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
               double mu1, double mu2, double mu_ls, int TViters2, const sbtv_salsa_opts *opts, const double *td,
               const double *xi, double *x_out_dev, double *objective, double *distance, double *times, double *mses,
               int *numA, int *numAt, int *n_outer, bool spec_wanted) {
-    AdmmCommon c;
+    BlurOp c;
     SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
     // The two TV proxes of an iteration are independent (:401,406).  With the same iteration count they run as ONE batch of
     // two images (own threshold, own duals, own stop rule per image: the batch semantics of the prox): two Chambolle
@@ -939,7 +843,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
     run.numAt = 2;                                                       // ATy twice (:189,219)
     ctx->calls += 3;                                                     // AT(y), invLS(ATy), AT(y)
     double *x = xbuf[0];
-    SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
+    SBTV_TRY(op_init_x(ctx, c, opts->initialization, yd, xi, x));
     if (opts->initialization == 0) ctx->calls += 1;
     // u = x ; bu = u ; v = x ; bv = v  (:353-359)  ->  first prox inputs x - bu = x - bv = 0
     for (double *dst : {u, bu, v, bv})
@@ -956,7 +860,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
     // initial objective (:366-368)
     double obj_prev;
     {
-        SBTV_TRY(admm_resid(ctx, c, x, acc));
+        SBTV_TRY(op_resid(ctx, c, x, acc));
         SBTV_TRY(reduce_partials(ctx, acc, 1, nrb, sums + 8));
         SBTV_TRY(tvnorm_dev(ctx, u, M, N, 1, sums + 9));
         SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 8, ctx->stream));
@@ -1008,7 +912,7 @@ int coral_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps,
             hipLaunchKernelGGL(coral_s_kernel<false>, dim3(nb), dim3(AB), 0, ctx->stream, u, bu, v, bv, mu1, mu2, mu_ls, s, tvpart,
                                (unsigned)M, (unsigned)N, P);
         }
-        SBTV_TRY(admm_solve(ctx, c, s, nullptr, c.Ys, par, acc, xn));    // mu_ls
+        SBTV_TRY(op_solve(ctx, c, s, nullptr, c.Ys, par, acc, xn));    // mu_ls
         hipLaunchKernelGGL(coral_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, xn,
                            (opts->stopcriterion == 2) ? xprev : (const double *)nullptr, u, v, bu, bv, g1, g2, td, partials, P);
         jb.add(partials, 7, nb, sums);
@@ -1064,7 +968,7 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
                double mu1, double mu2, const sbtv_salsa_opts *opts, const double *td, const double *xi, double *x_out_dev,
                double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer,
                bool spec_wanted) {
-    AdmmCommon c;
+    BlurOp c;
     SBTV_TRY(admm_common(ctx, M, N, taps, taille, nullptr, &c));
     const int K = opts->TViters;
     AdmmProx prox;
@@ -1108,15 +1012,15 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
     double *x = xbuf[0];
     if (opts->initialization == 2) {                                     // x = B'(m .* y)
         hipLaunchKernelGGL(masked_my_kernel, dim3(nb), dim3(AB), 0, ctx->stream, md, yd, g, P);
-        SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, g, x));
+        SBTV_TRY(op_apply(ctx, c, OP_MUL_HC, g, x));
         run.numAt += 1;
         ctx->calls += 1;
     } else {
-        SBTV_TRY(admm_init_x(ctx, c, opts->initialization, yd, xi, x));
+        SBTV_TRY(op_init_x(ctx, c, opts->initialization, yd, xi, x));
     }
     // Bx = B x ; u = x ; v = Bx ; bu = bv = 0 ; zero duals.  The element-wise pass on that state leaves bu = bv = 0, the
     // first prox input g = x, the first v and the sums of objective(1) / mses(1)
-    SBTV_TRY(admm_apply(ctx, c, OP_MUL_H, x, Bx));
+    SBTV_TRY(op_apply(ctx, c, OP_MUL_H, x, Bx));
     run.numA += 1;
     ctx->calls += 1;
     SBTV_HIP(ctx, hipMemcpyAsync(u, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1152,9 +1056,9 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
         if (spec && outer == 2) SBTV_TRY(prox.arm(ctx, false));
         SBTV_TRY(prox.run(ctx, g, u, sp, sums + 16, &jb));               // step sums: reduced at the end of the iteration
         // W = fft2(v + bv) (v was formed by the previous element-wise pass)
-        SBTV_TRY(admm_spectrum(ctx, c, v, bv, S2, Ws));
+        SBTV_TRY(op_spectrum(ctx, c.fp, v, bv, S2, Ws));
         // X = (conj(H) W + r fft2(u + bu)) / (|H|^2 + r), r = mu1 / mu2 ; x = real(ifft2(X))
-        SBTV_TRY(admm_solve(ctx, c, u, bu, Ws, par, acc, xn));
+        SBTV_TRY(op_solve(ctx, c, u, bu, Ws, par, acc, xn));
         // Bx = real(ifft2(H X)) from the column-transformed x the row pass left in S
         {
             RowsArgs a{};
@@ -1214,7 +1118,7 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
                 double mu, const sbtv_salsa_opts *opts, const double *td, const double *xwi, double *xw_out_dev,
                 double *x_out_dev, double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
                 int *n_outer) {
-    AdmmCommon c;
+    BlurOp c;
     SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
     const size_t P = c.P, C = P * wp.bands();
     const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
@@ -1244,7 +1148,7 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
         SBTV_HIP(ctx, hipMemsetAsync(s0, 0, sizeof(double) * C, ctx->stream));
         ctx->calls += 1;
     } else if (opts->initialization == 2) {                              // xw = W' B' y
-        SBTV_TRY(admm_apply(ctx, c, OP_MUL_HC, yd, d));
+        SBTV_TRY(op_apply(ctx, c, OP_MUL_HC, yd, d));
         SBTV_TRY(wav_analysis(ctx, wp, d, s0, 1));
     } else {
         SBTV_HIP(ctx, hipMemcpyAsync(s0, xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1254,7 +1158,7 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
     double obj_prev;
     {
         SBTV_TRY(wav_synthesis(ctx, wp, s0, xibuf[0], 1));
-        SBTV_TRY(admm_resid(ctx, c, xibuf[0], acc));
+        SBTV_TRY(op_resid(ctx, c, xibuf[0], acc));
         SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
         hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)s0, td, partials, C);
         RedJobs jb;
@@ -1279,7 +1183,7 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
         const double *sp = sbuf[p], *we = wbuf[p];
         hipLaunchKernelGGL(wav_prox_kernel, dim3(nb), dim3(AB), 0, ctx->stream, sp, we, sn, T, partials, C);      // :432
         SBTV_TRY(wav_synthesis(ctx, wp, sn, z, 1));
-        SBTV_TRY(admm_solve(ctx, c, z, nullptr, c.Ys, par, acc, xi));    // :434-436
+        SBTV_TRY(op_solve(ctx, c, z, nullptr, c.Ys, par, acc, xi));    // :434-436
         hipLaunchKernelGGL(ad_sub_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xi, (const double *)z, d, P);
         SBTV_TRY(wav_analysis(ctx, wp, d, wn, 1));
         hipLaunchKernelGGL(wav_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sn, (const double *)wn, we,
@@ -1427,8 +1331,7 @@ int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
     if (!tau || !mu1 || !mu2) return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: missing required argument");
     for (int b = 0; b < batch; ++b)
         if (!(mu1[b] > 0.0) || !(mu2[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_masked: mu1, mu2 must be > 0");
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     const size_t P = (size_t)M * N, cnt = P * batch;
     if (!(flags & SBTV_DEVICE_PTRS))
         for (size_t i = 0; i < cnt; ++i)
@@ -1460,8 +1363,7 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
     SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
     for (int b = 0; b < batch; ++b)
         if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: mu must be > 0");
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
     { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
     const size_t P = (size_t)M * N, C = P * wp.bands(), cnt = P * batch, ccnt = C * batch;

@@ -1416,12 +1416,11 @@ int sbtv_A_wrapper(sbtv_ctx *ctx, const double *taps, int taille, const double *
         default: return fail(ctx, SBTV_ERR_MODE, "The value of parameter mode must be 1 or 2 (or 3, 9).");
     }
     if (!taps || !x || !out || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "A_wrapper: bad arguments");
-    if (taille < 1 || taille > 15 || taille > M || taille > N)
-        return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     if (mode == 9 && !mu) return fail(ctx, SBTV_ERR_MISSING_LS, "A_wrapper: mode 9 (invLS) needs mu");
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    FftPlan pl;
-    SBTV_TRY(fft_plan(ctx, M, N, batch, &pl));
+    BlurOp bop;
+    SBTV_TRY(op_open(ctx, "op", M, N, batch, nullptr, &bop));
     const size_t cnt = (size_t)M * N * batch;
     const double *xd = nullptr;
     double *outd = nullptr;
@@ -1435,19 +1434,8 @@ int sbtv_A_wrapper(sbtv_ctx *ctx, const double *taps, int taille, const double *
         SBTV_TRY(ws_get_t(ctx, "op.mu", (size_t)batch, &mu_d));
         SBTV_HIP(ctx, hipMemcpyAsync(mu_d, mu, sizeof(double) * batch, hipMemcpyHostToDevice, ctx->stream));
     }
-    double2 *Hs = nullptr, *S = nullptr;
-    SBTV_TRY(ws_get_t(ctx, "op.H", (size_t)batch * pl.u_img, &Hs));
-    SBTV_TRY(ws_get_t(ctx, "op.S", (size_t)batch * pl.s_img, &S));
-    SBTV_TRY(psf_spectrum(ctx, pl, taps_d, taille, Hs));
-    SBTV_TRY(fft_cols_fwd(ctx, pl, xd, nullptr, S));
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    a.dir_inv = 1;
-    a.op = op;
-    a.H = Hs;
-    a.mu = mu_d;
-    SBTV_TRY(fft_rows(ctx, pl, S, S, a));
-    SBTV_TRY(fft_cols_inv(ctx, pl, S, outd, 1.0 / ((double)pl.n1 * N)));
+    SBTV_TRY(psf_spectrum(ctx, bop.fp, taps_d, taille, bop.Hs));
+    SBTV_TRY(op_apply(ctx, bop, op, xd, outd, mu_d));
     ctx->calls += batch;
     SBTV_TRY(stage_out_copy(ctx, out, outd, cnt, flags));
     if (!(flags & SBTV_DEVICE_PTRS)) SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1626,8 +1614,7 @@ int sbtv_diag_spectral_pass(sbtv_ctx *ctx, const sbtv_diag_pass *a) {
     if ((op == OP_INVLS || op == OP_SALSA || cs) && !a->mu) return fail(ctx, SBTV_ERR_MISSING_LS, "diag_spectral_pass: the operator needs mu");
     if (cs && (!a->cs || !a->e0 || (a->shared_spec && batch > 1)))
         return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: OP_CSALSA needs cs and e0, and one state per image");
-    if (op != OP_NONE && (a->taille < 1 || a->taille > 15 || a->taille > M || a->taille > N))
-        return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    if (op != OP_NONE) SBTV_TRY(check_psf_fits(ctx, a->taille, M, N));
     const bool book = epi == 1 || epi == 4;
     if (book && (!a->u || !a->bu || !a->g_out || !a->sums)) return fail(ctx, SBTV_ERR_BADARG, "diag_spectral_pass: bookkeeping needs u, bu, g_out, sums");
     if (epi == 4 && (!a->bu_in || a->xprev)) return fail(ctx, SBTV_ERR_BADARG, "fft_cols_inv_post: skip_x needs a separate bu_in and no xprev");

@@ -87,25 +87,21 @@ int sbtv_max_eigenval(sbtv_ctx *ctx, const double *taps, int taille, const doubl
                       int max_iter, double *val_out, int *iters, int flags) {
     if (!ctx) return SBTV_ERR_BADARG;
     if (!taps || !x0 || !val_out) return fail(ctx, SBTV_ERR_BADARG, "max_eigenval: bad arguments");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
-    FftPlan fp;
-    SBTV_TRY(fft_plan(ctx, M, N, 1, &fp));
-    const size_t P = (size_t)M * N;
+    SBTV_TRY(check_even_pixels(ctx, M, N));
+    BlurOp op;
+    SBTV_TRY(op_open(ctx, "ev", M, N, 1, nullptr, &op));
+    const size_t P = op.P;
     const double *x0d = nullptr;
     SBTV_TRY(stage_in(ctx, "ev.x0", x0, P, flags, &x0d));
     double *x = nullptr, *taps_d = nullptr, *o4 = nullptr;
-    double2 *S = nullptr, *Hs = nullptr;
     SBTV_TRY(ws_get_t(ctx, "ev.x", P, &x));
     SBTV_TRY(ws_get_t(ctx, "ev.taps", (size_t)taille * taille, &taps_d));
     SBTV_TRY(ws_get_t(ctx, "ev.o4", 4, &o4));
-    SBTV_TRY(ws_get_t(ctx, "ev.S", fp.s_img, &S));
-    SBTV_TRY(ws_get_t(ctx, "ev.H", fp.u_img, &Hs));
     SBTV_HIP(ctx, hipMemcpyAsync(taps_d, taps, sizeof(double) * taille * taille, hipMemcpyHostToDevice, ctx->stream));
     SBTV_HIP(ctx, hipMemcpyAsync(x, x0d, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
+    SBTV_TRY(psf_spectrum(ctx, op.fp, taps_d, taille, op.Hs));
     double h4[4];
     auto norm_x = [&](double *nrm) -> int {
         SBTV_TRY(pair_sums(ctx, x, nullptr, P, 1, o4));
@@ -119,16 +115,8 @@ int sbtv_max_eigenval(sbtv_ctx *ctx, const double *taps, int taille, const doubl
     SBTV_TRY(launch_scale(ctx, x, 1.0 / nrm, P));              // x = x / norm(x(:))          (:5)
     double init_val = 1.0, val = 1.0;
     int k = 0;
-    const double inv_scale = 1.0 / ((double)fp.n1 * N);
     for (k = 1; k <= max_iter; ++k) {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.dir_inv = 1;
-        a.op = OP_ATA;                                          // y = A(x); x = At(y)        (:9-10)
-        a.H = Hs;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, x, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(fft_cols_inv(ctx, fp, S, x, inv_scale));
+        SBTV_TRY(op_apply(ctx, op, OP_ATA, x, x));              // y = A(x); x = At(y)        (:9-10)
         SBTV_TRY(norm_x(&val));                                 // val = norm(x(:))            (:11)
         const double rel_var = fabs(val - init_val) / init_val;
         if (rel_var < tol) break;                               //                            (:16-18)
@@ -150,11 +138,13 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
                        const double *tau, double L, int prox_iters, int stopcriterion, double tolerance, int maxiters,
                        int zero_start, const double *td, double *x_out, double *objective, double *mses, int *n_iter,
                        int flags, bool spec_wanted) {
-    FftPlan fp;
-    SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
+    BlurOp op;                                          // its observation spectrum: "fista.B"
+    SBTV_TRY(op_open(ctx, "fista", M, N, batch, "B", &op));
+    const FftPlan &fp = op.fp;
+    double2 *const S = op.S;
     ProxPlan pp;
     SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
-    const size_t P = (size_t)M * N, cnt = P * batch;
+    const size_t P = op.P, cnt = P * batch;
     // x is double-buffered by iteration parity: the host evaluates the stopping rule one iteration late while the next
     // iteration already runs, and the iterate of a stopping iteration must still be intact then
     double *xb[2] = {nullptr, nullptr}, *y = nullptr, *grad = nullptr, *xfinal = nullptr;
@@ -164,10 +154,6 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
     SBTV_TRY(ws_get_t(ctx, "fista.y", cnt, &y));
     SBTV_TRY(ws_get_t(ctx, "fista.grad", cnt, &grad));
     SBTV_TRY(stage_out_buf(ctx, "fista.xfinal", x_out, cnt, flags, &xfinal));
-    double2 *S = nullptr, *Hs = nullptr, *Bs = nullptr;
-    SBTV_TRY(ws_get_t(ctx, "fista.S", (size_t)batch * fp.s_img, &S));
-    SBTV_TRY(ws_get_t(ctx, "fista.H", (size_t)batch * fp.u_img, &Hs));
-    SBTV_TRY(ws_get_t(ctx, "fista.B", (size_t)batch * fp.u_img, &Bs));
     const size_t npar = (size_t)batch * taille * taille + 2 * (size_t)batch;
     double *par = nullptr;
     SBTV_TRY(ws_get_t(ctx, "fista.par", npar, &par));
@@ -191,34 +177,20 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
     // then their completion tags, then the frozen flags for upload; host / device view
     constexpr int FT = 8 + FSTRIDE;
     const size_t slot_n = (size_t)FT * batch;
-    double *scal_base_h = nullptr, *scal_base_hd = nullptr;
-    SBTV_TRY(pinned_get(ctx, sizeof(double) * 4 * slot_n + sizeof(int) * batch, &scal_base_h, &scal_base_hd));
-    for (size_t i = 0; i < 2 * slot_n; ++i) scal_base_h[2 * slot_n + i] = 0.0;      // tags: no iteration yet
-    int *frozen_h = reinterpret_cast<int *>(scal_base_h + 4 * slot_n);
+    PinnedLayout lay;
+    const auto f_scal = lay.add<double>(2 * slot_n), f_tags = lay.add<double>(2 * slot_n);
+    const auto f_frozen = lay.add<int>((size_t)batch);
+    void *ph = nullptr, *pd = nullptr;
+    SBTV_TRY(pinned_get(ctx, lay.bytes(), &ph, &pd));
+    double *scal_base_h = f_scal.at(ph), *scal_base_hd = f_scal.at(pd);
+    double *tags_base_h = f_tags.at(ph), *tags_base_hd = f_tags.at(pd);
+    int *frozen_h = f_frozen.at(ph);
+    for (size_t i = 0; i < f_tags.count; ++i) tags_base_h[i] = 0.0;               // tags: no iteration yet
     for (int b = 0; b < batch; ++b) frozen_h[b] = 0;
-    double *tags_base_h = scal_base_h + 2 * slot_n, *tags_base_hd = scal_base_hd + 2 * slot_n;
-    const double inv_scale = 1.0 / ((double)fp.n1 * N), parseval = 1.0 / ((double)M * N);
-    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
-    {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, bd, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(spec_unpack(ctx, fp, S, Bs));
-    }
+    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, op.Hs));
+    SBTV_TRY(op_spectrum(ctx, fp, bd, nullptr, S, op.Ys));
     // x = AT(b) (my_fista.m:7) or zeros (my_deblur_fista.m:21)
-    if (zero_start) {
-        SBTV_HIP(ctx, hipMemsetAsync(x, 0, sizeof(double) * cnt, ctx->stream));
-    } else {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.dir_inv = 1;
-        a.op = OP_MUL_HC;
-        a.H = Hs;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, bd, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(fft_cols_inv(ctx, fp, S, x, inv_scale));
-    }
+    SBTV_TRY(op_init_x(ctx, op, zero_start ? 0 : 2, bd, nullptr, x));
     SBTV_HIP(ctx, hipMemcpyAsync(y, x, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
 
     // objective(k) = 0.5*||A x - b||^2 + tau*Phi(x) ; mses(k)   (:14-15, :31-33)
@@ -234,13 +206,6 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
     bool prox_was_spec = false;
     // objective / sums of iterate `xk` of iteration k -> pinned slot k & 1, tagged with k
     auto objective_of_x = [&](const double *xk, int k, const int *frozen, const double *mom_partials) -> int {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        a.op = OP_RESID;
-        a.H = Hs;
-        a.Y = Bs;
-        a.acc = acc;
-        a.frozen = frozen;
         // TVnorm(x) rides on the forward column pass over the same image (no TV launch of its own)
         double *tvp = nullptr;
         int ntv = 0;
@@ -248,8 +213,7 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
             ntv = fft_cols_blocks(fp);
             SBTV_TRY(ws_get_t(ctx, "fista.tvc", (size_t)batch * ntv, &tvp));
         }
-        SBTV_TRY(fft_cols_fwd_f(ctx, fp, xk, nullptr, S, frozen, tvp));
-        SBTV_TRY(fft_rows(ctx, fp, S, nullptr, a));
+        SBTV_TRY(op_resid(ctx, op, xk, acc, frozen, tvp));
         if (!tvp) SBTV_TRY(tvnorm_partials(ctx, xk, M, N, batch, &tvp, &ntv));
         const int slot = k & 1;
         hipLaunchKernelGGL(fista_collect_kernel, dim3(prox_was_spec ? 7 + prox_iters : 7, batch), dim3(256), 0, ctx->stream,
@@ -269,7 +233,7 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double *sc = scal_base_h + slot_n;       // slot of iteration 1
         for (int b = 0; b < batch; ++b) {
-            const double f0 = 0.5 * (sc[(size_t)b * 3] * parseval) + tau[b] * sc[6 * (size_t)batch + b];
+            const double f0 = 0.5 * (sc[(size_t)b * 3] * op.parseval) + tau[b] * sc[6 * (size_t)batch + b];
             obj_prev[b] = f0;
             if (objective) objective[(size_t)b * maxiters] = f0;
             if (mses) mses[(size_t)b * maxiters] = h4[(size_t)b * 4] / (double)P;
@@ -302,8 +266,8 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
             a.dir_fwd = 1;
             a.dir_inv = 1;
             a.op = OP_GRADF;
-            a.H = Hs;
-            a.Y = Bs;
+            a.H = op.Hs;
+            a.Y = op.Ys;
             a.acc = acc;
             a.frozen = frozen_d;
             SBTV_TRY(fft_cols_fwd_f(ctx, fp, y, nullptr, S, frozen_d));
@@ -311,9 +275,9 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
             if (fused_step) {
                 // the gradient never reaches memory: the inverse column pass applies the step to y from its registers
                 // (optimistic prox launches do not consult the control blocks: armed once before the loop)
-                SBTV_TRY(fft_cols_inv_step(ctx, fp, S, y, inv_scale, 1.0 / L, frozen_d));
+                SBTV_TRY(fft_cols_inv_step(ctx, fp, S, y, op.inv_scale, 1.0 / L, frozen_d));
             } else {
-                SBTV_TRY(fft_cols_inv_f(ctx, fp, S, grad, inv_scale, frozen_d));
+                SBTV_TRY(fft_cols_inv_f(ctx, fp, S, grad, op.inv_scale, frozen_d));
                 // the gradient-step kernel also re-arms the control blocks of the cold-start prox that follows
                 const ProxArm arm{pp.ctrl, lam_d, prox_iters, CHAMBOLLE_TOL, CHAMBOLLE_TAU, frozen_d};
                 if (batch <= 256) {
@@ -344,7 +308,7 @@ static int fista_solve(sbtv_ctx *ctx, const double *bd, int M, int N, int batch,
         bool changed = false;
         for (int b = 0; b < batch; ++b) {
             if (frozen[b]) continue;
-            const double f = 0.5 * (sc[(size_t)b * 3] * parseval) + tau[b] * sc[6 * (size_t)batch + b];
+            const double f = 0.5 * (sc[(size_t)b * 3] * op.parseval) + tau[b] * sc[6 * (size_t)batch + b];
             const double *mom = sc + 3 * (size_t)batch + (size_t)b * 3;
             if (objective) objective[(size_t)b * maxiters + (k - 1)] = f;
             if (mses) mses[(size_t)b * maxiters + (k - 1)] = mom[0] / (double)P;
@@ -392,10 +356,9 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *bimg, int M, int N, int batch, co
         return fail(ctx, SBTV_ERR_BADARG, "fista_tv: bad arguments (b, taps, tau, true are required)");
     if (stopcriterion < 1 || stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Invalid stopping criterion!");
     if (prox_iters <= 0) return fail(ctx, SBTV_ERR_MAXITER, "fista_tv: prox_iters must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     if (sbtv_group *lg = lanes_group(ctx, batch, false)) {       // independent images: two lanes of this context (group.hip)
         LaneCall lc(ctx, lg);
         return lc.done(fista_sharded(lg, bimg, M, N, batch, taps, taille, tau, L, prox_iters, stopcriterion, tolerance, maxiters,

@@ -288,20 +288,18 @@ static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
         chain_offset < 0)
         return fail(ctx, SBTV_ERR_BADARG, "myula: bad arguments");
     if (chambolleit <= 0) return fail(ctx, SBTV_ERR_MAXITER, "myula: chambolleit must be positive");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
-    FftPlan fp;
-    SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
+    SBTV_TRY(check_even_pixels(ctx, M, N));
+    BlurOp bop;
+    SBTV_TRY(op_open(ctx, "myula", M, N, batch, "Y", &bop));
     ProxPlan pp;
     SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
-    const size_t P = (size_t)M * N, cnt = P * batch, spec = fp.u_img;
+    const size_t P = bop.P, cnt = P * batch;
     const double *yd = nullptr;
     SBTV_TRY(stage_in(ctx, "myula.y", y, cnt, flags, &yd));
     const bool noise_host = noise && !(flags & SBTV_DEVICE_PTRS);
     double *X = nullptr, *prox = nullptr, *grad = nullptr, *Z = nullptr, *par = nullptr, *acc = nullptr;
-    double2 *S = nullptr, *Hs = nullptr, *Ys = nullptr;
     double *pm_mean = nullptr, *pm_m2 = nullptr;          // running mean / M2 of the samples [batch][P]
     if (mom) {
         SBTV_TRY(ws_get_t(ctx, "myula.pm_mean", cnt, &pm_mean));
@@ -311,10 +309,7 @@ static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     SBTV_TRY(ws_get_t(ctx, "myula.prox", cnt, &prox));
     SBTV_TRY(ws_get_t(ctx, "myula.grad", cnt, &grad));
     if (noise_host) SBTV_TRY(ws_get_t(ctx, "myula.Z", cnt, &Z));
-    SBTV_TRY(ws_get_t(ctx, "myula.S", (size_t)batch * fp.s_img, &S));
-    SBTV_TRY(ws_get_t(ctx, "myula.H", spec * batch, &Hs));
-    SBTV_TRY(ws_get_t(ctx, "myula.Y", spec * batch, &Ys));
-    SBTV_TRY(ws_get_t(ctx, "myula.acc", (size_t)batch * 3 * fft_rows_blocks(fp), &acc));
+    SBTV_TRY(ws_get_t(ctx, "myula.acc", (size_t)batch * 3 * fft_rows_blocks(bop.fp), &acc));
     const size_t t2 = (size_t)taille * taille, npar = t2 * batch + 2 * (size_t)batch;
     SBTV_TRY(ws_get_t(ctx, "myula.par", npar, &par));      // [taps | lambda*theta | sigma2]
     double *taps_d = par, *lam_d = par + t2 * batch, *sig_d = lam_d + batch;
@@ -325,32 +320,16 @@ static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
         hpar[t2 * batch + batch + b] = sigma2[b];
     }
     SBTV_HIP(ctx, hipMemcpyAsync(par, hpar.data(), sizeof(double) * npar, hipMemcpyHostToDevice, ctx->stream));
-    SBTV_TRY(psf_spectrum(ctx, fp, taps_d, taille, Hs));
-    {
-        RowsArgs a{};
-        a.dir_fwd = 1;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, yd, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(spec_unpack(ctx, fp, S, Ys));
-    }
+    SBTV_TRY(psf_spectrum(ctx, bop.fp, taps_d, taille, bop.Hs));
+    SBTV_TRY(op_spectrum(ctx, bop.fp, yd, nullptr, bop.S, bop.Ys));
     SBTV_HIP(ctx, hipMemcpyAsync(X, yd, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));   // x = op.y  (:3,11)
     if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));            // iteration 1 = y
-    const double inv_scale = 1.0 / ((double)fp.n1 * N);
     SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, nullptr));
     const ProxArm arm{pp.ctrl, lam_d, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, nullptr};
     for (int ii = 2; ii <= samples - 1; ++ii) {             // :13
         const size_t step = (size_t)(ii - 2);
         SBTV_TRY(prox_iterate(ctx, pp, X, chambolleit, prox, true));                         // :15
-        RowsArgs a{};                                       // gradF = AT(A x - y) / sigma2   (run_deblur_tv.m:131)
-        a.dir_fwd = 1;
-        a.dir_inv = 1;
-        a.op = OP_GRADF;
-        a.H = Hs;
-        a.Y = Ys;
-        a.acc = acc;
-        SBTV_TRY(fft_cols_fwd(ctx, fp, X, nullptr, S));
-        SBTV_TRY(fft_rows(ctx, fp, S, S, a));
-        SBTV_TRY(fft_cols_inv(ctx, fp, S, grad, inv_scale));
+        SBTV_TRY(op_gradf(ctx, bop, X, acc, grad));         // gradF = AT(A x - y) / sigma2   (run_deblur_tv.m:131)
         const double *zd = nullptr;
         if (noise_host) {
             SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * cnt, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
@@ -718,8 +697,13 @@ struct SapgRun {
         step_d = sig_d + batch;
         nrb = fft_rows_blocks(fp);
         SBTV_TRY(ws_get_t(ctx, "sapg.acc", (size_t)batch * 3 * nrb, &acc));
-        SBTV_TRY(pinned_get(ctx, sizeof(double) * (4 * batch + 3 * t2 * nspec + 2 * batch + 1), &scal_h, &scal_out));
-        par_h = scal_h + 4 * (size_t)batch;
+        PinnedLayout lay;
+        const auto f_scal = lay.add<double>(4 * (size_t)batch), f_par = lay.add<double>(npar_all);
+        void *ph = nullptr, *pd = nullptr;
+        SBTV_TRY(pinned_get(ctx, lay.bytes(), &ph, &pd));
+        scal_h = f_scal.at(ph);
+        scal_out = f_scal.at(pd);
+        par_h = f_par.at(ph);
         ntvc = fft_cols_tv_ok(fp) ? fft_cols_blocks(fp) : 0;
         if (ntvc) SBTV_TRY(ws_get_t(ctx, "sapg.tvc", (size_t)batch * ntvc, &tvc));
         inv_scale = 1.0 / ((double)fp.n1 * N);
@@ -777,13 +761,7 @@ struct SapgRun {
         graphs_ok = (noise == nullptr) && graph_wanted(cnt) && !(mom && !dev_loop) && !in_stream();
 
         // ---- Y spectrum (one per spectrum set)
-        {
-            RowsArgs a{};
-            a.dir_fwd = 1;
-            SBTV_TRY(fft_cols_fwd(ctx, fps, yd, nullptr, S1));
-            SBTV_TRY(fft_rows(ctx, fps, S1, S1, a));
-            SBTV_TRY(spec_unpack(ctx, fps, S1, Ys));
-        }
+        SBTV_TRY(op_spectrum(ctx, fps, yd, nullptr, S1, Ys));
         // X0 = y by default (SAPG_algorithm_Guassian.m:10-12)
         if (x0d) {
             SBTV_HIP(ctx, hipMemcpyAsync(X, x0d, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1047,7 +1025,7 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     if (!y || !op || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: bad arguments");
     if (op->kind < 0 || op->kind > 2) return fail(ctx, SBTV_ERR_PSF, "SAPG_algorithm: unknown PSF kind");
     const int taille = op->psf_size;
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     if (op->samples < 2 || op->warmup < 0 || op->burnIn < 1 || op->burnIn > op->samples)
         return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: need samples >= 2, 1 <= burnIn <= samples");
     if (op->chambolleit <= 0) return fail(ctx, SBTV_ERR_MAXITER, "SAPG_algorithm: chambolleit must be positive");
@@ -1055,8 +1033,7 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
     if (op->iter_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: iter_offset must be >= 0");
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
     const int shared = op->share_gradients ? 1 : 0;
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     // independent chains (SAPG_algorithm_moffat.m:143-173: every chain has its own state) -> two lanes of this context;
     // shared-gradient chains only in lanes_mode 2 (their per-iteration exchange couples the two streams).  Not when the
     // caller reduces across processes itself, forces the host loop, or injects device-resident noise (re-packed per lane).

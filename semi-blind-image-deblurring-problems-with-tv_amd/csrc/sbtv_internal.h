@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/sbtv.h"
+#include "pinned_layout.h"
 
 namespace sbtv {
 
@@ -700,6 +701,57 @@ int fft_cols_fwd_f(sbtv_ctx *ctx, const FftPlan &pl, const double *x, const doub
 bool fft_cols_tv_ok(const FftPlan &pl);
 int fft_cols_inv_f(sbtv_ctx *ctx, const FftPlan &pl, const double2 *S, double *x, double scale, const int *frozen);
 
+// ----------------------------- blur-operator layer of the drivers (operator.hip) ---------
+// What a solve shares about its operator A = ifft2(H . fft2): the plan of `batch` images of P pixels, the packed work
+// spectrum S, the spectra of the PSF (Hs, filled by the caller: psf_spectrum) and of the observation (Ys), the scale of
+// the inverse column pass and the Parseval factor of the residual sums.
+struct BlurOp {
+    FftPlan fp;
+    int batch;
+    size_t P;
+    double2 *S, *Hs, *Ys;
+    double inv_scale, parseval;
+};
+// plan + the workspaces "<prefix>.S", "<prefix>.H" and "<prefix>.<y_name>" (y_name null: no observation spectrum)
+int op_open(sbtv_ctx *ctx, const char *prefix, int M, int N, int batch, const char *y_name, BlurOp *op);
+// U = fft2(in + add) in the layout of H, by way of the packed spectrum S (any plan: SAPG has one per spectrum set)
+int op_spectrum(sbtv_ctx *ctx, const FftPlan &fp, const double *in, const double *add, double2 *S, double2 *U);
+// out = real(ifft2(op(H) .* fft2(in))): OP_MUL_H, OP_MUL_HC, OP_ATA, and OP_INVLS with mu (device, per image)
+int op_apply(sbtv_ctx *ctx, const BlurOp &c, int op, const double *in, double *out, const double *mu = nullptr);
+// out = real(ifft2((conj(H) Y + mu fft2(in + add)) / (|H|^2 + mu))), the row pass OP_SALSA (mu: device); its residual sum
+// against Y goes to acc, and c.S is left holding N times the column transform of `out`
+int op_solve(sbtv_ctx *ctx, const BlurOp &c, const double *in, const double *add, const double2 *Y, const double *mu,
+             double *acc, double *out);
+// acc = the partial sums of ||H fft2(x) - Ys||^2 (OP_RESID: nothing is stored); images with frozen[b] set are skipped;
+// tvp: the TV partials of x ride on the forward column pass (sizes of fft_cols_tv_ok)
+int op_resid(sbtv_ctx *ctx, const BlurOp &c, const double *x, double *acc, const int *frozen = nullptr, double *tvp = nullptr);
+// grad = AT(A x - y) (OP_GRADF), ||A x - y||^2 partial sums to acc
+int op_gradf(sbtv_ctx *ctx, const BlurOp &c, const double *x, double *acc, double *grad);
+// the start image by `initialization` of sbtv_salsa_opts: 0 zeros, 2 AT(y), else the caller's xi
+int op_init_x(sbtv_ctx *ctx, const BlurOp &c, int initialization, const double *yd, const double *xi, double *x);
+
+// ---- argument checks the entry points share
+int check_psf_fits(sbtv_ctx *ctx, int taille, int M, int N);       // SBTV_ERR_PSF "Mask does not fit inside array"
+int check_even_pixels(sbtv_ctx *ctx, int M, int N);                // SBTV_ERR_SIZE: the element-wise passes move two per lane
+// x_init_name: what the caller's start array is called in its message; tv: the entry point runs a TV prox of TViters
+// iterations; maxiter_positive = false: maxiter = 0 is a valid call (sbtv_SALSA_v2 returns the start image)
+int check_common(sbtv_ctx *ctx, const char *who, const double *y, const double *taps, const sbtv_salsa_opts *opts,
+                 const double *x_init, int M, int N, int batch, int taille, const char *x_init_name = "x_init", bool tv = true,
+                 bool maxiter_positive = true);
+// The stop rule of SALSA_v2.m:453-472 (CoRAL_v2.m:435-453 is the same rule), from the second iteration on: the relative
+// change of the objective f (criterion 1), ||x - xprev|| / ||x|| from their squares num and den (2), f itself (3)
+inline bool salsa_stop(int stopcriterion, int outer, double f, double obj_prev, double num, double den, double tolA) {
+    if (outer <= 1) return false;                                        // :453
+    double crit;
+    if (stopcriterion == 1)
+        crit = fabs(f - obj_prev) / obj_prev;                            // :456
+    else if (stopcriterion == 2)
+        crit = fabs(sqrt(num) / sqrt(den));                              // :460
+    else
+        crit = f;                                                        // :464
+    return crit < tolA;                                                  // :472
+}
+
 // ----------------------------- redundant wavelet frame (wavelet.hip) ---------
 // one checked transform: image size, filter length K, J = levels - 1 decomposition steps, h0 / sqrt 2 and h1 / sqrt 2
 struct WavPlan {
@@ -778,14 +830,12 @@ __device__ __forceinline__ WavThetaStep wav_theta_step(double eta, double th_cur
 // two halves of an operator pass and the step, enqueued on the context's stream.  Device pointers, but `noise`.
 struct WavChain {
     WavPlan wp;
-    FftPlan fp;
+    BlurOp op;                   // operator layer "<prefix>": column spectrum of W X in op.S; op.Hs is filled by the caller
     int batch, nblk, nrb;        // element-wise workgroups per chain (wav_ew_blocks), row blocks per image (fft_rows_blocks)
     size_t P, cnt, dimX, ccnt;   // M N, P batch, (3J+1) P, dimX batch
     const double *yd, *x0d;      // y; the caller's start state or null (W'y)
     const double *noise;         // injected normals [step][batch][dimX] (host unless Z is null) or null: Philox
     double *X, *G, *img, *Z;     // state, gradient, image, staging of one step of host noise
-    double2 *S, *Hs, *Ys;        // column spectrum of W X; spectra of the PSF (filled by the caller) and of y
-    double inv_scale;
 };
 // plan, staging of y / xw0 and the workspaces "<prefix>.y", .G, .X, .img, .Z, .S, .H, .Y
 int wav_chain_buffers(sbtv_ctx *ctx, const char *prefix, const WavPlan &wp, int batch, const double *y, const double *xw0,

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(WAV_EWB) void wav_step_kernel(double *__restrict__ 
 int wav_chain_buffers(sbtv_ctx *ctx, const char *prefix, const WavPlan &wp, int batch, const double *y, const double *xw0,
                       const double *noise, double *xw_last, int flags, WavChain *c) {
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    SBTV_TRY(fft_plan(ctx, wp.M, wp.N, batch, &c->fp));
+    SBTV_TRY(op_open(ctx, prefix, wp.M, wp.N, batch, "Y", &c->op));
     c->wp = wp;
     c->batch = batch;
     c->P = (size_t)wp.M * wp.N;
@@ -88,29 +88,21 @@ int wav_chain_buffers(sbtv_ctx *ctx, const char *prefix, const WavPlan &wp, int 
     c->dimX = c->P * wp.bands();
     c->ccnt = c->dimX * batch;
     c->nblk = wav_ew_blocks(c->dimX);
-    c->nrb = fft_rows_blocks(c->fp);
-    c->inv_scale = 1.0 / ((double)c->fp.n1 * wp.N);
+    c->nrb = fft_rows_blocks(c->op.fp);
     c->noise = noise;
     c->Z = nullptr;
     const std::string p(prefix);
-    const size_t spec = c->fp.u_img * batch;
     SBTV_TRY(stage_in(ctx, (p + ".y").c_str(), y, c->cnt, flags, &c->yd));
     SBTV_TRY(stage_in(ctx, (p + ".G").c_str(), xw0, c->ccnt, flags, &c->x0d));     // staged where the gradient goes later
     SBTV_TRY(stage_out_buf(ctx, (p + ".X").c_str(), xw_last, c->ccnt, flags, &c->X));
     SBTV_TRY(ws_get_t(ctx, (p + ".G").c_str(), c->ccnt, &c->G));
     SBTV_TRY(ws_get_t(ctx, (p + ".img").c_str(), c->cnt, &c->img));
     if (noise && !(flags & SBTV_DEVICE_PTRS)) SBTV_TRY(ws_get_t(ctx, (p + ".Z").c_str(), c->ccnt, &c->Z));
-    SBTV_TRY(ws_get_t(ctx, (p + ".S").c_str(), (size_t)batch * c->fp.s_img, &c->S));
-    SBTV_TRY(ws_get_t(ctx, (p + ".H").c_str(), spec, &c->Hs));
-    return ws_get_t(ctx, (p + ".Y").c_str(), spec, &c->Ys);
+    return 0;
 }
 
 int wav_chain_start(sbtv_ctx *ctx, const WavChain &c) {
-    RowsArgs a{};
-    a.dir_fwd = 1;
-    SBTV_TRY(fft_cols_fwd(ctx, c.fp, c.yd, nullptr, c.S));
-    SBTV_TRY(fft_rows(ctx, c.fp, c.S, c.S, a));
-    SBTV_TRY(spec_unpack(ctx, c.fp, c.S, c.Ys));
+    SBTV_TRY(op_spectrum(ctx, c.op.fp, c.yd, nullptr, c.op.S, c.op.Ys));
     if (!c.x0d) return wav_analysis(ctx, c.wp, c.yd, c.X, c.batch);
     if (c.x0d != c.X) SBTV_HIP(ctx, hipMemcpyAsync(c.X, c.x0d, sizeof(double) * c.ccnt, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
@@ -118,7 +110,7 @@ int wav_chain_start(sbtv_ctx *ctx, const WavChain &c) {
 
 int wav_chain_spectrum(sbtv_ctx *ctx, const WavChain &c, const MomArgs *mom) {
     SBTV_TRY(wav_synthesis(ctx, c.wp, c.X, c.img, c.batch, mom && mom->k > 0 ? mom : nullptr));
-    return fft_cols_fwd(ctx, c.fp, c.img, nullptr, c.S);
+    return fft_cols_fwd(ctx, c.op.fp, c.img, nullptr, c.op.S);
 }
 
 int wav_chain_rows(sbtv_ctx *ctx, const WavChain &c, int op, double *acc, const double2 *D1, const double2 *D2) {
@@ -126,14 +118,14 @@ int wav_chain_rows(sbtv_ctx *ctx, const WavChain &c, int op, double *acc, const 
     ra.dir_fwd = 1;
     ra.dir_inv = op == OP_GRADF;
     ra.op = op;
-    ra.H = c.Hs;
-    ra.Y = c.Ys;
+    ra.H = c.op.Hs;
+    ra.Y = c.op.Ys;
     ra.D1 = op == OP_GRAD ? D1 : nullptr;
     ra.D2 = op == OP_GRAD ? D2 : nullptr;
     ra.acc = acc;
-    SBTV_TRY(fft_rows(ctx, c.fp, c.S, ra.dir_inv ? c.S : nullptr, ra));
+    SBTV_TRY(fft_rows(ctx, c.op.fp, c.op.S, ra.dir_inv ? c.op.S : nullptr, ra));
     if (!ra.dir_inv) return 0;
-    SBTV_TRY(fft_cols_inv(ctx, c.fp, c.S, c.img, c.inv_scale));
+    SBTV_TRY(fft_cols_inv(ctx, c.op.fp, c.op.S, c.img, c.op.inv_scale));
     return wav_analysis(ctx, c.wp, c.img, c.G, c.batch);
 }
 

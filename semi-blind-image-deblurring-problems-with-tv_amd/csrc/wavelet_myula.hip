@@ -88,7 +88,7 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
     if (!y || !op || !theta || !sigma2 || batch < 1)
         return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: missing required argument (y, op, theta, sigma2, batch >= 1)");
     if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     WavPlan wp;
     SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
     if (op->samples < 2) return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: need samples >= 2");
@@ -98,8 +98,7 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
         if (!positive_finite(theta[b]) || !positive_finite(sigma2[b]))
             return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: every theta[b] and sigma2[b] must be finite and > 0");
     if (op->chain_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: chain_offset must be >= 0");
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     const int samples = op->samples;
     const size_t P = (size_t)M * N, cnt = P * batch, dimX = P * wp.bands(), ccnt = dimX * batch;
     const bool dev = (flags & SBTV_DEVICE_PTRS) != 0;
@@ -178,7 +177,7 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
         SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));                    // the staging vector goes out of scope
     }
-    SBTV_TRY(psf_spectrum(ctx, wc.fp, taps_d, taille, wc.Hs));
+    SBTV_TRY(psf_spectrum(ctx, wc.op.fp, taps_d, taille, wc.op.Hs));
     SBTV_TRY(wav_chain_start(ctx, wc));
     // the traces of `slots` ring slots, the first of them iteration ii0
     auto trace = [&](int slots, int ii0, int has_r, int has_g) -> int {

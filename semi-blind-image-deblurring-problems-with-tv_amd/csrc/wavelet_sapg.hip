@@ -115,7 +115,7 @@ int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     if (!ctx) return SBTV_ERR_BADARG;
     if (!y || !op || !theta_eb || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet: missing required argument");
     if (!taps) return fail(ctx, SBTV_ERR_MISSING_AT, "The function handle for transpose of A is missing");
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     WavPlan wp;
     SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
     if (op->samples < 2 || op->warmup < 0 || op->burnIn < 1 || op->burnIn > op->samples)
@@ -125,8 +125,7 @@ int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     if (!(op->min_th > 0.0) || !(op->min_th <= op->th_init) || !(op->th_init <= op->max_th))
         return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet: need 0 < min_th <= th_init <= max_th");
     if (op->chain_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet: chain_offset must be >= 0");
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     WavChain wc;
     SBTV_TRY(wav_chain_buffers(ctx, "wsapg", wp, batch, y, xw0, noise, xw_last, flags, &wc));
     const int samples = op->samples, warmup = op->warmup, wsteps = warmup > 0 ? warmup - 1 : 0, wstride = warmup > 0 ? warmup : 1;
@@ -155,7 +154,7 @@ int sbtv_SAPG_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
         SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));                    // the staging vector goes out of scope
     }
-    SBTV_TRY(psf_spectrum(ctx, wc.fp, taps_d, taille, wc.Hs));
+    SBTV_TRY(psf_spectrum(ctx, wc.op.fp, taps_d, taille, wc.op.Hs));
     SBTV_TRY(wav_chain_start(ctx, wc));
     auto update = [&](int phase, int ii, double delta) -> int {
         hipLaunchKernelGGL(wav_sapg_update_kernel, dim3(batch), dim3(WAV_EWB), 0, ctx->stream, u, phase, ii, delta);

@@ -212,7 +212,7 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
     if (!y || !op || !eb || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet_semiblind: missing required argument");
     if (op->kind < 0 || op->kind > 2) return fail(ctx, SBTV_ERR_PSF, "SAPG_wavelet_semiblind: unknown PSF kind");
     const int taille = op->psf_size;
-    if (taille < 1 || taille > 15 || taille > M || taille > N) return fail(ctx, SBTV_ERR_PSF, "Mask does not fit inside array");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
     WavPlan wp;
     SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
     if (op->samples < 2 || op->warmup < 0 || op->burnIn < 1 || op->burnIn > op->samples)
@@ -242,8 +242,7 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
         return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet_semiblind: c_sigma must be finite and >= 0");
     if (!op->fix_sigma && (!(op->sigma2_min > 0.0) || !(op->sigma2_min <= op->sigma2) || !(op->sigma2 <= op->sigma2_max)))
         return fail(ctx, SBTV_ERR_BADARG, "SAPG_wavelet_semiblind: free sigma2 needs 0 < sigma2_min <= sigma2 <= sigma2_max");
-    if (((size_t)M * N) & 1)
-        return fail(ctx, SBTV_ERR_SIZE, "this entry point needs an even number of pixels (its element-wise passes move two per lane)");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
     const size_t t2 = (size_t)taille * taille;
     // taps and derivative taps of the start parameters, on the host (sbtv_psf_taps): [taps | d0 | d1], each [batch][t2]
     std::vector<double> par_h(3 * t2 * batch, 0.0);
@@ -267,7 +266,7 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
     WavChain wc;
     SBTV_TRY(wav_chain_buffers(ctx, "wsb", wp, batch, y, xw0, noise, xw_last, flags, &wc));
     const int samples = op->samples, warmup = op->warmup, wsteps = warmup > 0 ? warmup - 1 : 0, wstride = warmup > 0 ? warmup : 1;
-    const size_t P = wc.P, dimX = wc.dimX, ccnt = wc.ccnt, spec = wc.fp.u_img;
+    const size_t P = wc.P, dimX = wc.dimX, ccnt = wc.ccnt, spec = wc.op.fp.u_img;
     double *X = wc.X, *acc = nullptr, *part = nullptr, *tr_d = nullptr;
     double2 *D1s = nullptr, *D2s = nullptr;
     WavSbDev u{};
@@ -312,8 +311,8 @@ int sbtv_SAPG_wavelet_semiblind(sbtv_ctx *ctx, const double *y, int M, int N, in
         SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * trlen, ctx->stream));
     }
     const double *tp[3] = {u.par, u.par + t2 * batch, u.par + 2 * t2 * batch};
-    double2 *up[3] = {wc.Hs, D1s, D2s};
-    auto spectra = [&]() -> int { return psf_spectrum_sets(ctx, wc.fp, tp, taille, up, npar > 1 ? 3 : 2); };
+    double2 *up[3] = {wc.op.Hs, D1s, D2s};
+    auto spectra = [&]() -> int { return psf_spectrum_sets(ctx, wc.op.fp, tp, taille, up, npar > 1 ? 3 : 2); };
     SBTV_TRY(spectra());
     SBTV_TRY(wav_chain_start(ctx, wc));
     // S = column spectrum of W X, then the row pass without store: ||B W X - y||^2 and <dB/dp_q W X, B W X - y> -> acc

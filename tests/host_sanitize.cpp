@@ -6,8 +6,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
+#include "pinned_layout.h"
 #include "sbtv.h"
 
 static int fails = 0;
@@ -161,6 +163,50 @@ int main() {
                                     nullptr) == SBTV_ERR_BADARG);
         CHECK(sbtv_SALSA_v2_sharded_dev(nullptr, nullptr, 2, 2, 1, nullptr, 7, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == SBTV_ERR_BADARG);
+    }
+    // ---- the pinned-block layout helper: mixed field types in the order and with the counts of the drivers' blocks, for
+    // small, odd and large batches and the smallest and largest PSF.  Every field aligned, none overlapping its
+    // predecessor, the last one ending within bytes(); first and last element of every field are written into a heap
+    // block of exactly bytes() (ASan reports an overrun)
+    {
+        struct Scal8 { double v[8]; };
+        for (int batch : {1, 3, 257})
+            for (int taille : {1, 15}) {
+                const size_t npar = (size_t)batch * taille * taille + 2 * (size_t)batch;
+                sbtv::PinnedLayout lay;
+                const auto f_int0 = lay.add<int>(4);                              // an int field ahead of wider types
+                const auto f_scal = lay.add<Scal8>(2 * (size_t)batch);
+                const auto f_init = lay.add<Scal8>((size_t)batch);
+                const auto f_tags = lay.add<double>(3 * (size_t)batch * 40);
+                const auto f_odd = lay.add<int>((size_t)batch);                   // odd batch: the next double needs padding
+                const auto f_par = lay.add<double>(npar);
+                const auto f_frozen = lay.add<int>((size_t)batch);
+                std::vector<unsigned char> heap(lay.bytes());
+                void *base = heap.data();
+                size_t end = 0;
+                auto field = [&](auto f, size_t align) {
+                    using T = std::remove_pointer_t<decltype(f.at(base))>;
+                    CHECK(f.off % align == 0 && f.off >= end);
+                    CHECK(f.off - end < align);                                   // padding only up to the alignment
+                    end = f.off + sizeof(T) * f.count;
+                    CHECK(end <= lay.bytes());
+                    T *p = f.at(base);
+                    CHECK(reinterpret_cast<unsigned char *>(p) == heap.data() + f.off);
+                    std::memset(&p[0], 0x5a, sizeof(T));
+                    std::memset(&p[f.count - 1], 0xa5, sizeof(T));
+                };
+                field(f_int0, alignof(int));
+                field(f_scal, alignof(Scal8));
+                field(f_init, alignof(Scal8));
+                field(f_tags, alignof(double));
+                field(f_odd, alignof(int));
+                field(f_par, alignof(double));
+                field(f_frozen, alignof(int));
+                CHECK(end == lay.bytes());
+                // the device view: the same offsets from another base
+                std::vector<unsigned char> view(lay.bytes());
+                CHECK(reinterpret_cast<unsigned char *>(f_par.at(view.data())) == view.data() + f_par.off);
+            }
     }
     std::printf(fails ? "%d host checks FAILED\n" : "host sanitizer run: all checks passed\n", fails);
     return fails ? 1 : 0;

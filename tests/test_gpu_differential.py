@@ -243,3 +243,18 @@ def test_shortest_calls_device_resident(ctx):
                                 L.vptr(obj), None, None, None, None, None, nout, yi.flags), yi.flags)
     np.testing.assert_array_equal(sbtv.to_host(ti.t[0]), sbtv.to_host(ref[0]))
     np.testing.assert_array_equal(obj, ref[3])
+    # MAXITERA = 0 (the keyword interface and the other ADMM entries refuse it, the C-ABI of SALSA_v2 does not): no iteration
+    # runs, the call returns 0 with n_outer = 0, numA = numAt = 1 and objective(1) of the start image.  At this size (x stored
+    # by the loop) a device-resident x_out is left as the caller passed it: the iteration numbered MAXITERA counts as having
+    # written it.  Observed on the commit that split salsa_solve into SalsaRun, and on its parent.
+    so.maxiter, so.initialization = 0, 2
+    ref0 = sbtv.SALSA_v2(yd, A, tau, "MU", mu, "AT", A.T, "LS", A.LS(mu), "ToleranceA", -1.0, "MAXITERA", 1, "TVINITIALIZATION", 1,
+                         "TViters", 10, "INITIALIZATION", 2)
+    xo = L.Images(sbtv.to_device(np.full((M, N), -7.0)))
+    obj0 = np.full(1, -1.0)
+    na, nat, nout = (C.c_int * 1)(-5), (C.c_int * 1)(-5), (C.c_int * 1)(-5)
+    rc = c.lib.sbtv_SALSA_v2(c.h, yi.ptr, M, N, 1, L.vptr(taps), A.taille, tau_p, mu_p, C.byref(so), None, None, xo.ptr,
+                             L.vptr(obj0), None, None, None, na, nat, nout, yi.flags)
+    assert (rc, nout[0], na[0], nat[0]) == (0, 0, 1, 1)
+    np.testing.assert_array_equal(obj0, ref0[3][:1])
+    np.testing.assert_array_equal(sbtv.to_host(xo.t[0]), np.full((M, N), -7.0))
