@@ -670,6 +670,70 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                        double *coef_mean, double *coef_var,
                        int flags);
 
+/* ---- wavelet-l1 posterior at a fixed theta: SK-ROCK on the frame coefficients ------------------------------------------
+ * No entry of the reference.  The explicit stabilised sampler of Pereyra, Vargas Mieles, Zygalakis, "Accelerating proximal
+ * Markov chain Monte Carlo by using an explicit stabilised method", SIAM J. Imaging Sci. 2020, on the target of
+ * sbtv_myula_wavelet (the same Moreau-Yosida-smoothed posterior, the same W, W', B, soft, dimX, theta_b, sigma2_b, lambda):
+ * one step costs `stages` gradient evaluations and is stable for a step of about stages^2 (2 - 4 eta/3) / L where MYULA
+ * allows about 1 / L, so that at equal gradient work the chain travels much further.  The drift is
+ *     D(K) = (soft(K, lambda theta_b) - K)/lambda - G(K)/sigma2_b,    G(K) = W'B'(B W K - y)
+ * Coefficients (sbtv_skrock_coefficients: host, double), s = stages >= 2, damping eta > 0, T_j / U_j the Chebyshev
+ * polynomials of the first / second kind:
+ *     w0 = 1 + eta/s^2;   T_0 = 1, T_1 = w0, T_j = 2 w0 T_{j-1} - T_{j-2};   T_s'(w0) = s U_{s-1}(w0)
+ *     w1 = T_s(w0) / T_s'(w0)
+ *     mu_1 = w1/w0,  nu_1 = s w1/2,  kappa_1 = s w1/w0
+ *     j = 2..s:  mu_j = 2 w1 T_{j-1}/T_j,  nu_j = 2 w0 T_{j-1}/T_j,  kappa_j = 1 - nu_j
+ *     l_s = (s - 0.5)^2 (2 - 4 eta/3) - 1.5
+ * One step from X = X(ii-1) to X(ii), Z standard normal in the layout of X (the SAME Z three times), q = sqrt(2 delta):
+ *     P   = X + (nu_1 q) Z
+ *     K_1 = (X + (mu_1 delta) D(P)) + (kappa_1 q) Z,    K_0 = X
+ *     j = 2..s:  K_j = ((mu_j delta) D(K_{j-1}) + nu_j K_{j-1}) + kappa_j K_{j-2}
+ *     X(ii) = K_s
+ * evaluated as grouped here, no floating-point contraction.  X(1) = xw0 (NULL: W' y).  Traces, ii = 1..samples, no lag:
+ *     gx(ii)    = ||X(ii)||_1
+ *     logpi(ii) = -||y - B W X(ii)||^2 / (2 sigma2_b) - theta_b gx(ii)
+ * Stability: delta <= l_s / L, L = ||B||^2/sigma2 + 1/lambda (sbtv_skrock_max_step; ||B|| = 1 for a normalised non-negative
+ * PSF, and the frame is tight).  The entry does not police delta, as sbtv_myula_wavelet does not police gamma.  A delta near
+ * the bound biases the stiff directions of the target (their stationary variance shrinks); it is the caller's trade.
+ * What runs: one step is s gradient passes (synthesis, FFT triple with OP_GRADF, analysis), each followed by one
+ * element-wise stage kernel (32 B per coefficient; the first 24 B, the last 40 B: it also forms P of the next step), and one
+ * residual pass (synthesis, forward transform, row pass) on X(ii), which gives logpi(ii) and is where the image moments of
+ * sample ii are accumulated.  Two coefficient buffers and G.  Nothing is reduced per step: partial sums of up to 1024
+ * samples wait in a ring; one launch turns them into trace entries, one workgroup per chain and sample, every sum in a
+ * fixed order; one synchronisation per 1024 steps and one at the end.  Chains of a batch share every launch; chain b is
+ * computed bit for bit as alone.  The call counter advances by batch for sample 1 and by (2 stages + 1) batch per step.
+ * No lanes, no graph capture and no sharded variant.
+ *   noise: NULL (device Philox randn with the counters of sbtv_myula_wavelet: sample ii draws step ii - 2, so a seed names the
+ *          same normals in both samplers) or (samples-1) * batch * dimX doubles, step-major, as for sbtv_myula_wavelet
+ *   theta, sigma2, xw0, gx, logpi, xw_last, the moments (mo, post_*, coef_*: of the samples 1..samples) and
+ *   SBTV_DEVICE_PTRS: as for sbtv_myula_wavelet; no bit of the chain depends on what is accumulated.
+ * Refused before any GPU work: what sbtv_myula_wavelet refuses (gamma aside), with its codes; with SBTV_ERR_BADARG also
+ * stages < 2, delta <= 0, eta <= 0 and non-finite values. */
+typedef struct sbtv_skrock_wavelet_opts {
+    int    samples;            /* >= 2: sample 1 is the start state, samples-1 steps follow          */
+    int    stages;             /* s >= 2 gradient evaluations per step                               */
+    double lambda, delta, eta; /* Moreau-Yosida parameter, step (<= l_s/L), damping (e.g. 0.05)      */
+    unsigned long long seed;   /* Philox seed when noise == NULL                                     */
+    int    chain_offset;       /* chain b draws the Philox stream chain_offset + b                   */
+} sbtv_skrock_wavelet_opts;
+int sbtv_skrock_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                        const double *taps, int taille, const double *h, int hlen, int levels,
+                        const sbtv_skrock_wavelet_opts *op,
+                        const double *theta, const double *sigma2,
+                        const double *xw0, const double *noise,
+                        double *gx, double *logpi,
+                        double *xw_last,
+                        const sbtv_moments_opts *mo,
+                        double *post_mean, double *post_var, long long *post_count,
+                        double *coef_mean, double *coef_var,
+                        int flags);
+/* Host only.  The table above: mu, nu, kappa [stages] (entry j-1 is stage j), omega[2] = {w0, w1}, ls = l_s; any output
+ * may be NULL.  SBTV_ERR_BADARG: stages < 2, eta <= 0 or not finite. */
+int sbtv_skrock_coefficients(int stages, double eta, double *mu, double *nu, double *kappa, double *omega, double *ls);
+/* Host only.  delta_max = l_s / (normB2/sigma2 + 1/lambda), normB2 = ||B||^2.  SBTV_ERR_BADARG: stages < 2, eta, sigma2 or
+ * lambda <= 0, normB2 < 0, non-finite values, delta_max == NULL. */
+int sbtv_skrock_max_step(int stages, double eta, double sigma2, double lambda, double normB2, double *delta_max);
+
 /* ---- a-9: largest eigenvalue of A'A by power iteration --------------------
  * Replaces max_eigenval(A,At,params,im_size,tol,max_iter,verbose)
  * (utils/max_eigenval_Gaussian_Moffat.m:1-27, max_eigenval_Laplace.m:1-28).

@@ -861,6 +861,32 @@ struct WavStepPar {
 int wav_chain_step(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, double gam, double lamb, const RngArgs &rng,
                    double *part, const MomArgs *mom = nullptr);
 
+// ---- SK-ROCK on the same target (wavelet_skrock.hip drives; the element-wise kernels live in wavelet_chain.hip)
+// the drift of the Moreau-Yosida-smoothed posterior at one coefficient k with gradient g = (W'B'(B W K - y)) there:
+//     D = (soft(k, T) - k)/lamb - g/s2,   T = lamb theta;   no contraction anywhere in it
+__device__ __forceinline__ double wav_skrock_drift_nocontract(double k, double g, double T, double lamb, double s2) {
+#pragma clang fp contract(off)
+    return (wav_soft(k, T) - k) / lamb - g / s2;
+}
+// the scalars of one stage j of a step (include/sbtv.h, sbtv_skrock_wavelet); q = sqrt(2 delta)
+struct WavSkrockStage {
+    double mud;                  // mu_j delta
+    double nu, kappa;            // nu_j, kappa_j; the first stage: unused, kappa_1 q
+    double nu1q;                 // nu_1 q: the first stage forms P again with it, the last one forms P of the next step
+};
+// c.Z set: the staging buffer of host noise receives the normals of `step` (stream order)
+int wav_skrock_noise(sbtv_ctx *ctx, const WavChain &c, unsigned step);
+// P = X + (nu_1 q) Z with the normals of rng.step (injected, or Philox as in wav_chain_step): the first step of a call
+int wav_skrock_perturb(sbtv_ctx *ctx, const WavChain &c, const double *X, double *P, double nu1q, const RngArgs &rng);
+// One stage on every chain with G = c.G: U = K_{j-1}, V = K_{j-2}.
+//   first: V = X, U = P (not read: P is formed again from X and the normals of rng.step); K_1 is written over U.
+//   otherwise K_j is written over V.  last: K_j is the new sample: part [batch][nblk] receives the partial sums of
+//   ||X_new||_1, mom with k > 0 accumulates it as sample k, and with next_p the normals of rng.step + 1 give
+//   P_next = X_new + (nu_1 q) Z_next, written over U.
+int wav_skrock_stage(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, double lamb, double *U, double *V,
+                     const WavSkrockStage &st, bool first, bool last, bool next_p, const RngArgs &rng, double *part,
+                     const MomArgs *mom = nullptr);
+
 #include "psf_taps.inc"   // psf_taps_point(): PSF formulas shared by host and device
 
 }  // namespace sbtv

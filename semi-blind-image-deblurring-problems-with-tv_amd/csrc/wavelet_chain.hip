@@ -5,6 +5,8 @@
 // element-wise kernels: the library is built without relocatable device code, so a kernel is launched from the unit that
 // defines it and the drivers reach these through the host functions of sbtv_internal.h.  The drivers keep what differs:
 // the order of the passes, where theta and sigma2 live, the update / trace kernels.
+// The SK-ROCK chain on the same target (sbtv_skrock_wavelet in wavelet_skrock.hip) runs the same passes on
+// either of its two coefficient buffers; its perturbation and stage kernels stand here next to wav_step_kernel.
 #include <cmath>
 #include <string>
 #include <type_traits>
@@ -73,6 +75,90 @@ __global__ __launch_bounds__(WAV_EWB) void wav_step_kernel(double *__restrict__ 
     }
     a = wav_block_sum(a, red);
     if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+}
+
+// SK-ROCK (include/sbtv.h, sbtv_skrock_wavelet): P = X + (nu_1 q) Z for the first step of a call; every later P comes out of
+// the last stage of the step before.  Z as in wav_step_kernel.
+__global__ __launch_bounds__(WAV_EWB) void wav_skrock_perturb_kernel(const double *__restrict__ X, double *__restrict__ P,
+                                                                      const double *__restrict__ Z, double nu1q, size_t dimX,
+                                                                      RngArgs rng) {
+    const int b = blockIdx.y;
+    const size_t base = (size_t)b * dimX;
+    for (size_t q = (size_t)blockIdx.x * WAV_EWB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WAV_EWB) {
+        const size_t o = base + 2 * q;
+        const double2 xv = *reinterpret_cast<const double2 *>(X + o);
+        const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
+                             : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
+        *reinterpret_cast<double2 *>(P + o) = make_double2(xv.x + nu1q * zv.x, xv.y + nu1q * zv.y);
+    }
+}
+
+// the first stage at one coefficient: K_1 = (x + (mu_1 delta) D(P)) + (kappa_1 q) z with P = x + (nu_1 q) z formed again
+__device__ __forceinline__ double wav_skrock_first_nocontract(double x, double g, double z, double T, double lamb, double s2,
+                                                              const WavSkrockStage &st) {
+    const double p = x + st.nu1q * z;
+    return (x + st.mud * wav_skrock_drift_nocontract(p, g, T, lamb, s2)) + st.kappa * z;
+}
+// a later stage: K_j = ((mu_j delta) D(K_{j-1}) + nu_j K_{j-1}) + kappa_j K_{j-2}
+__device__ __forceinline__ double wav_skrock_stage_nocontract(double u, double v, double g, double T, double lamb, double s2,
+                                                              const WavSkrockStage &st) {
+    return (st.mud * wav_skrock_drift_nocontract(u, g, T, lamb, s2) + st.nu * u) + st.kappa * v;
+}
+
+// One SK-ROCK stage of every chain, two coefficients per lane as wav_step_kernel; G is the gradient at K_{j-1} (FIRST: at P).
+// FIRST: V = X is read, Z is drawn (or read) again with the counters of the perturbation, K_1 goes to U (P is not read).
+// Otherwise U = K_{j-1} and V = K_{j-2} are read and K_j goes to V.  LAST: K_j is the new sample: part and, with MOM, the
+// moments as in wav_step_kernel; NEXT (every step but the last of a call): Z of step rng.step + 1 gives P of the next step,
+// written over U, which this lane has just read.
+// The compiler is asked for the six waves per SIMD of wav_step_kernel: left alone it spreads the four divisions of the last stage
+// over 100+ registers next to the generator (four waves); with the bound it needs 78 and no scratch.
+template <bool FIRST, bool LAST, bool NEXT, bool MOM>
+__global__ __launch_bounds__(WAV_EWB) __attribute__((amdgpu_waves_per_eu(6))) void wav_skrock_stage_kernel(
+    double *__restrict__ U, double *__restrict__ V, const double *__restrict__ G, const double *__restrict__ Z, WavStepPar par,
+    double lamb, WavSkrockStage st, size_t dimX, RngArgs rng, double *__restrict__ part,
+    std::conditional_t<MOM, MomArgs, WavNoMom> mom) {
+    static_assert(!(FIRST && LAST) && (LAST || !(MOM || NEXT)), "a step has at least two stages; only the last one has a sample");
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const size_t base = (size_t)b * dimX, pb = (size_t)b * par.stride;
+    const double T = lamb * par.theta[pb], s2 = par.sigma2[pb];
+    int k = 0;
+    if constexpr (MOM) k = mom.k;
+    const double rk = 1.0 / (double)(k > 0 ? k : 1);
+    double a = 0.0;
+    for (size_t q = (size_t)blockIdx.x * WAV_EWB + threadIdx.x; q < dimX / 2; q += (size_t)gridDim.x * WAV_EWB) {
+        const size_t o = base + 2 * q;
+        const double2 vv = *reinterpret_cast<const double2 *>(V + o);
+        const double2 gv = *reinterpret_cast<const double2 *>(G + o);
+        double2 r;
+        if constexpr (FIRST) {
+            const double2 zv = Z ? *reinterpret_cast<const double2 *>(Z + o)
+                                 : philox_normal_pair(q, rng.step, rng.chain0 + (unsigned)b, rng.seed);
+            r.x = wav_skrock_first_nocontract(vv.x, gv.x, zv.x, T, lamb, s2, st);
+            r.y = wav_skrock_first_nocontract(vv.y, gv.y, zv.y, T, lamb, s2, st);
+            *reinterpret_cast<double2 *>(U + o) = r;
+        } else {
+            const double2 uv = *reinterpret_cast<const double2 *>(U + o);
+            r.x = wav_skrock_stage_nocontract(uv.x, vv.x, gv.x, T, lamb, s2, st);
+            r.y = wav_skrock_stage_nocontract(uv.y, vv.y, gv.y, T, lamb, s2, st);
+            *reinterpret_cast<double2 *>(V + o) = r;
+        }
+        if constexpr (LAST) {
+            if constexpr (MOM) {
+                if (k > 0) moments_pair(mom, o, r, k, rk);
+            }
+            a += fabs(r.x) + fabs(r.y);
+            if constexpr (NEXT) {
+                const double2 zn = Z ? *reinterpret_cast<const double2 *>(Z + o)
+                                     : philox_normal_pair(q, rng.step + 1u, rng.chain0 + (unsigned)b, rng.seed);
+                *reinterpret_cast<double2 *>(U + o) = make_double2(r.x + st.nu1q * zn.x, r.y + st.nu1q * zn.y);
+            }
+        }
+    }
+    if constexpr (LAST) {
+        a = wav_block_sum(a, red);
+        if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = a;
+    }
 }
 
 }  // namespace
@@ -151,6 +237,56 @@ int wav_chain_step(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, doub
     else
         hipLaunchKernelGGL(wav_step_kernel<false>, grid, block, 0, ctx->stream, c.X, (const double *)c.G, zd, par, gam, lamb,
                            sq2g, c.dimX, rng, part, WavNoMom{});
+    SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int wav_skrock_noise(sbtv_ctx *ctx, const WavChain &c, unsigned step) {
+    if (!c.Z) return 0;
+    SBTV_HIP(ctx, hipMemcpyAsync(c.Z, c.noise + (size_t)step * c.ccnt, sizeof(double) * c.ccnt, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    return 0;
+}
+
+// the normals of `step` as the kernels read them: the staging buffer (wav_skrock_noise filled it), the caller's device array,
+// or null: Philox
+static const double *wav_skrock_z(const WavChain &c, unsigned step) {
+    if (c.Z) return c.Z;
+    return c.noise ? c.noise + (size_t)step * c.ccnt : nullptr;
+}
+
+int wav_skrock_perturb(sbtv_ctx *ctx, const WavChain &c, const double *X, double *P, double nu1q, const RngArgs &rng) {
+    hipLaunchKernelGGL(wav_skrock_perturb_kernel, dim3(c.nblk, c.batch), dim3(WAV_EWB), 0, ctx->stream, X, P,
+                       wav_skrock_z(c, rng.step), nu1q, c.dimX, rng);
+    SBTV_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+int wav_skrock_stage(sbtv_ctx *ctx, const WavChain &c, const WavStepPar &par, double lamb, double *U, double *V,
+                     const WavSkrockStage &st, bool first, bool last, bool next_p, const RngArgs &rng, double *part,
+                     const MomArgs *mom) {
+    if (first && last) return fail(ctx, SBTV_ERR_BADARG, "wav_skrock_stage: a step has at least two stages");
+    const dim3 grid(c.nblk, c.batch), block(WAV_EWB);
+    const double *G = c.G;
+    const bool np = last && next_p;
+    const double *zd = first ? wav_skrock_z(c, rng.step) : (np ? wav_skrock_z(c, rng.step + 1u) : nullptr);
+#define SBTV_SKROCK_STAGE(F, L, NX, MO, momarg)                                                                        \
+    hipLaunchKernelGGL((wav_skrock_stage_kernel<F, L, NX, MO>), grid, block, 0, ctx->stream, U, V, G, zd, par, lamb, st,   \
+                       c.dimX, rng, part, momarg)
+    const bool mo = mom && mom->k > 0;
+    if (first)
+        SBTV_SKROCK_STAGE(true, false, false, false, WavNoMom{});
+    else if (!last)
+        SBTV_SKROCK_STAGE(false, false, false, false, WavNoMom{});
+    else if (np && mo)
+        SBTV_SKROCK_STAGE(false, true, true, true, *mom);
+    else if (np)
+        SBTV_SKROCK_STAGE(false, true, true, false, WavNoMom{});
+    else if (mo)
+        SBTV_SKROCK_STAGE(false, true, false, true, *mom);
+    else
+        SBTV_SKROCK_STAGE(false, true, false, false, WavNoMom{});
+#undef SBTV_SKROCK_STAGE
     SBTV_HIP(ctx, hipGetLastError());
     return 0;
 }

@@ -271,34 +271,20 @@ def SAPG_wavelet(y, A, h, levels, op, noise=None, xw0=None, ctx=None):
     return eb, results
 
 
-def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=None, posterior=None, ctx=None):
-    """results = myula_wavelet(y, A, h, levels, op, theta, sigma2)
-
-    MYULA chain on the wavelet coefficients at a FIXED theta: samples of p(xw | y, theta) ~ exp(-||y - A W xw||^2 / (2 sigma2)
-    - theta ||xw||_1), e.g. at the theta_EB of SAPG_wavelet, with the posterior mean (the MMSE image) and variance of the
-    samples accumulated on the device.  It is the warm-up loop of SALSA/SAPG_algorithm_1.m:131-141 with the closures of
-    run_deblur_synthesis_L1.m:135-146 (include/sbtv.h, sbtv_myula_wavelet, states it); iteration 1 is the start state, samples-1
-    steps follow.
-    A, h, levels: as for SAPG_wavelet.  op (dict or object): samples, lambda, gamma; optional theta, sigma2 (or sigma), X0, seed
-    (1), chain_offset (0).  theta / sigma2 (default op.theta / op.sigma2): a scalar or one value per image of a batch.
-    noise: optional (samples-1, [B,] M, (3J+1) N) normals instead of the device Philox stream, as for SAPG_wavelet.
-    posterior: None (no moments), True, or dict(first=1, thin=1, pooled=False, coefficients=False): the iterations first,
-    first + thin, ... of 1..samples; pooled: one set over the chains of the call (chains of one posterior only);
-    coefficients: also the mean / variance per coefficient.
-    Returns a dict (a list of dicts for a batch): Xlast_sample, gXTrace (||X(ii)||_1), logPiTraceX, options, and with posterior:
-    posteriormean, posteriorvar (images W X(ii)), posteriorcount, and coefmean, coefvar when coefficients are requested.
-    Device tensors in give device tensors out."""
+def _fixed_theta_chain(entry, make_opts, finish_opts, y, A, h, levels, op, theta, sigma2, noise, xw0, posterior, ctx):
+    """What myula_wavelet and skrock_wavelet share: the arguments of sbtv_<entry> but its option struct.  make_opts() returns
+    the struct with the sampler's own fields set (samples, lambda, seed and chain_offset are set here); finish_opts(o, sigma2)
+    completes it once the per-chain sigma2 array is known."""
     ctx = ctx or L.default_context()
     if getattr(ctx, "is_group", False):
-        raise NotImplementedError("myula_wavelet has no sharded variant")
+        raise NotImplementedError(f"{entry} has no sharded variant")
     yi = L.Images(y)
     B, M, N = yi.B, yi.M, yi.N
     nb = max(_bands(levels), 1)
     ha, hp, K = _filter(h)
-    o = L.sbtv_myula_wavelet_opts()
+    o = make_opts()
     o.samples = int(_op(op, "samples"))
     o.lambda_ = float(_op(op, "lambda"))
-    o.gamma = float(_op(op, "gamma"))
     o.seed = int(_op(op, "seed", 1))
     o.chain_offset = int(_op(op, "chain_offset", 0))
     get = lambda name: op.get(name) if isinstance(op, dict) else getattr(op, name, None)
@@ -309,6 +295,8 @@ def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=
         if sigma2 is None:
             sigma2 = np.asarray(_op(op, "sigma"), dtype=np.float64) ** 2
     keep = [L.dvec(theta, B), L.dvec(sigma2, B)]
+    if finish_opts is not None:
+        finish_opts(o, keep[1][0])
     S = o.samples
     if xw0 is None:
         xw0 = get("X0")
@@ -332,10 +320,10 @@ def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=
         if coefficients:
             cm, cv, _ = _moment_buffers(xl, 1 if pooled else B)
     ptr = lambda im: im.ptr if im is not None else None
-    ctx.check(ctx.lib.sbtv_myula_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, int(levels), C.byref(o),
-                                         keep[0][1], keep[1][1], ptr(x0i), nz_ptr, _vp(gx), _vp(logpi), xl.ptr,
-                                         C.byref(mo) if mo is not None else None, ptr(pm), ptr(pv),
-                                         _vp(pc) if pc is not None else None, ptr(cm), ptr(cv), yi.flags), yi.flags)
+    fn = getattr(ctx.lib, "sbtv_" + entry)
+    ctx.check(fn(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, int(levels), C.byref(o), keep[0][1], keep[1][1], ptr(x0i),
+                 nz_ptr, _vp(gx), _vp(logpi), xl.ptr, C.byref(mo) if mo is not None else None, ptr(pm), ptr(pv),
+                 _vp(pc) if pc is not None else None, ptr(cm), ptr(cv), yi.flags), yi.flags)
     xs = L.images_result(xl, False)
     moments = {}
     if mo is not None:
@@ -351,6 +339,81 @@ def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=
         results.append(r)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
     return results[0] if sq else results
+
+
+def myula_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=None, posterior=None, ctx=None):
+    """results = myula_wavelet(y, A, h, levels, op, theta, sigma2)
+
+    MYULA chain on the wavelet coefficients at a FIXED theta: samples of p(xw | y, theta) ~ exp(-||y - A W xw||^2 / (2 sigma2)
+    - theta ||xw||_1), e.g. at the theta_EB of SAPG_wavelet, with the posterior mean (the MMSE image) and variance of the
+    samples accumulated on the device.  It is the warm-up loop of SALSA/SAPG_algorithm_1.m:131-141 with the closures of
+    run_deblur_synthesis_L1.m:135-146 (include/sbtv.h, sbtv_myula_wavelet, states it); iteration 1 is the start state, samples-1
+    steps follow.
+    A, h, levels: as for SAPG_wavelet.  op (dict or object): samples, lambda, gamma; optional theta, sigma2 (or sigma), X0, seed
+    (1), chain_offset (0).  theta / sigma2 (default op.theta / op.sigma2): a scalar or one value per image of a batch.
+    noise: optional (samples-1, [B,] M, (3J+1) N) normals instead of the device Philox stream, as for SAPG_wavelet.
+    posterior: None (no moments), True, or dict(first=1, thin=1, pooled=False, coefficients=False): the iterations first,
+    first + thin, ... of 1..samples; pooled: one set over the chains of the call (chains of one posterior only);
+    coefficients: also the mean / variance per coefficient.
+    Returns a dict (a list of dicts for a batch): Xlast_sample, gXTrace (||X(ii)||_1), logPiTraceX, options, and with posterior:
+    posteriormean, posteriorvar (images W X(ii)), posteriorcount, and coefmean, coefvar when coefficients are requested.
+    Device tensors in give device tensors out."""
+    def make_opts():
+        o = L.sbtv_myula_wavelet_opts()
+        o.gamma = float(_op(op, "gamma"))
+        return o
+    return _fixed_theta_chain("myula_wavelet", make_opts, None, y, A, h, levels, op, theta, sigma2, noise, xw0, posterior, ctx)
+
+
+def skrock_coefficients(stages, eta=0.05):
+    """The SK-ROCK table of include/sbtv.h (sbtv_skrock_coefficients, host arithmetic): dict(mu, nu, kappa: arrays of
+    `stages` entries, entry j-1 for stage j; omega0, omega1, ls)."""
+    s = int(stages)
+    mu, nu, kappa, om, ls = np.zeros(max(s, 1)), np.zeros(max(s, 1)), np.zeros(max(s, 1)), np.zeros(2), np.zeros(1)
+    lib = L.load_library()
+    rc = lib.sbtv_skrock_coefficients(s, float(eta), _vp(mu), _vp(nu), _vp(kappa), _vp(om), _vp(ls))
+    if rc != 0:
+        raise L.SbtvError(rc, lib.sbtv_last_error(None).decode())
+    return dict(mu=mu, nu=nu, kappa=kappa, omega0=float(om[0]), omega1=float(om[1]), ls=float(ls[0]))
+
+
+def skrock_max_step(stages, eta, sigma2, lam, normB2=1.0):
+    """The largest stable SK-ROCK step l_s / (normB2 / sigma2 + 1 / lam) (sbtv_skrock_max_step, host arithmetic);
+    normB2 = ||B||^2 is 1 for a normalised non-negative PSF."""
+    out = C.c_double(0.0)
+    lib = L.load_library()
+    rc = lib.sbtv_skrock_max_step(int(stages), float(eta), float(sigma2), float(lam), float(normB2), C.byref(out))
+    if rc != 0:
+        raise L.SbtvError(rc, lib.sbtv_last_error(None).decode())
+    return out.value
+
+
+def skrock_wavelet(y, A, h, levels, op, theta=None, sigma2=None, noise=None, xw0=None, posterior=None, ctx=None):
+    """results = skrock_wavelet(y, A, h, levels, op, theta, sigma2)
+
+    SK-ROCK chain on the wavelet coefficients at a FIXED theta: the target, arguments and results of myula_wavelet, with the
+    explicit stabilised step of Pereyra, Vargas Mieles and Zygalakis (2020) (include/sbtv.h, sbtv_skrock_wavelet, states it):
+    `stages` gradient evaluations per step, a step delta of about stages^2 (2 - 4 eta / 3) times MYULA's gamma.  Sample 1 is
+    the start state, samples-1 steps follow.
+    op (dict or object): samples, stages, lambda; optional delta (None: 0.8 skrock_max_step(stages, eta, the smallest sigma2, lambda)
+    with ||B||^2 = 1), eta (0.05), theta, sigma2 (or sigma), X0, seed (1), chain_offset (0).
+    theta, sigma2, noise, xw0, posterior and the returned keys: as for myula_wavelet."""
+    def make_opts():
+        o = L.sbtv_skrock_wavelet_opts()
+        o.stages = int(_op(op, "stages"))
+        o.eta = float(_op(op, "eta", 0.05))
+        return o
+
+    def finish_opts(o, s2):
+        delta = op.get("delta") if isinstance(op, dict) else getattr(op, "delta", None)
+        if delta is None:
+            # the stiffest chain of the call sets the step; arguments the bound cannot be formed from are the library's to refuse
+            s2 = float(np.min(s2))
+            ok = o.stages >= 2 and all(np.isfinite(v) and v > 0 for v in (o.eta, s2, o.lambda_))
+            delta = 0.8 * skrock_max_step(o.stages, o.eta, s2, o.lambda_) if ok else float("nan")
+        o.delta = float(delta)
+    return _fixed_theta_chain("skrock_wavelet", make_opts, finish_opts, y, A, h, levels, op, theta, sigma2, noise, xw0, posterior,
+                              ctx)
 
 
 _PSF_KIND = {"gaussian": 0, "moffat": 1, "laplace": 2}

@@ -4,12 +4,15 @@ empirical-Bayes estimate of theta for the Laplace prior on the coefficients of t
 (`sbtv.SAPG_wavelet`, :125-156) -> MAP image by `sbtv.SALSA_wavelet` at tau = theta_EB sigma^2, mu = theta_EB (:160-185).
 With `--posterior S` also S samples of the posterior at theta_EB (`sbtv.myula_wavelet`, started at the MAP coefficients): the
 MMSE image next to the MAP image, and the per-pixel standard deviation; `--out DIR` is where both are saved (.npy and .pgm).
+`--sampler skrock` draws them with `sbtv.skrock_wavelet` instead (`--stages` gradient evaluations per sample, `--delta` or
+0.8 of the stability bound), and prints ||X||_1 of the first and the last sample.
 With `--semiblind KIND` (gaussian, moffat or laplace) the blur is NOT given to the estimator: the image is blurred with the
 7 x 7 PSF of the family at its true parameters, `sbtv.SAPG_wavelet_semiblind` estimates (theta, p) from one chain with sigma^2
 known, the taps are rebuilt from p_EB, `sbtv.SALSA_wavelet` solves with them, and the estimates are printed next to the
 true values with the PSNR.
 
   python tools/run_wavelet_demo.py [--image tests/golden/man_512.npy] [--samples 3000] [--seed 1] [--posterior S] [--out DIR]
+                                   [--sampler skrock --stages 10 [--delta D]]
   python tools/run_wavelet_demo.py --semiblind laplace [--samples 3000] [--seed 1]
 
 Constants follow the script (:65-83,99,106-107,164-166).  The reference's uniform_blur is centred; the library's taps sit in
@@ -84,6 +87,9 @@ def main():
     ap.add_argument("--posterior", type=int, default=0, metavar="S",
                     help="after theta_EB, S MYULA samples at theta_EB: MMSE image and standard-deviation map")
     ap.add_argument("--posterior-first", type=int, default=0, help="first iteration used (default: S / 10 + 1)")
+    ap.add_argument("--sampler", default="myula", choices=("myula", "skrock"), help="the sampler of --posterior")
+    ap.add_argument("--stages", type=int, default=10, help="skrock: gradient evaluations per sample")
+    ap.add_argument("--delta", type=float, default=None, help="skrock: step (default: 0.8 of the stability bound)")
     ap.add_argument("--out", default=os.path.join(ROOT, "out"), help="directory for the mean / standard-deviation maps")
     ap.add_argument("--semiblind", default=None, choices=sorted(SEMIBLIND), metavar="KIND",
                     help="estimate (theta, p) of this PSF family with sigma^2 known instead of taking the blur as given")
@@ -129,16 +135,25 @@ def main():
     print(f"wall time {t_eb + t_map:.2f} s")
     if a.posterior >= 2:
         first = a.posterior_first or a.posterior // 10 + 1
-        pop = {"samples": a.posterior, "lambda": lam, "gamma": op["gamma"], "seed": a.seed + 1}
         t0 = time.perf_counter()
-        post = sbtv.myula_wavelet(y, A, h, levels, pop, theta=theta_EB, sigma2=sigma ** 2, xw0=np.asarray(out[0]),
-                                  posterior=dict(first=first), ctx=ctx)
+        if a.sampler == "skrock":
+            pop = {"samples": a.posterior, "stages": a.stages, "lambda": lam, "delta": a.delta, "seed": a.seed + 1}
+            post = sbtv.skrock_wavelet(y, A, h, levels, pop, theta=theta_EB, sigma2=sigma ** 2, xw0=np.asarray(out[0]),
+                                       posterior=dict(first=first), ctx=ctx)
+        else:
+            pop = {"samples": a.posterior, "lambda": lam, "gamma": op["gamma"], "seed": a.seed + 1}
+            post = sbtv.myula_wavelet(y, A, h, levels, pop, theta=theta_EB, sigma2=sigma ** 2, xw0=np.asarray(out[0]),
+                                      posterior=dict(first=first), ctx=ctx)
         t_post = time.perf_counter() - t0
         xMMSE = np.roll(np.asarray(post["posteriormean"]), (c, c), axis=(0, 1))
         sd = np.roll(np.sqrt(np.asarray(post["posteriorvar"])), (c, c), axis=(0, 1))
         mmse = 10 * math.log10(np.linalg.norm(x - xMMSE) ** 2 / dimX)
         err = np.abs(x - xMMSE)
-        print(f"myula_wavelet at theta_EB: {a.posterior} samples in {t_post:.2f} s, iterations {first}.. used "
+        if a.sampler == "skrock":
+            delta = a.delta if a.delta is not None else 0.8 * sbtv.skrock_max_step(a.stages, 0.05, sigma ** 2, lam)
+            print(f"skrock_wavelet: {a.stages} stages, delta {delta:.4g} ({delta / op['gamma']:.1f} gamma); ||X||_1 of the first "
+                  f"sample {post['gXTrace'][0]:.6g}, of the last {post['gXTrace'][-1]:.6g}")
+        print(f"{a.sampler}_wavelet at theta_EB: {a.posterior} samples in {t_post:.2f} s, iterations {first}.. used "
               f"({post['posteriorcount']}); MSE of the MMSE image {mmse:.2f} dB (MAP {mse:.2f} dB); standard deviation: "
               f"mean {sd.mean():.3f}, max {sd.max():.3f}; correlation of |x - MMSE| with it {np.corrcoef(err.ravel(), sd.ravel())[0, 1]:.2f}")
         os.makedirs(a.out, exist_ok=True)
