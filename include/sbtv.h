@@ -734,6 +734,54 @@ int sbtv_skrock_coefficients(int stages, double eta, double *mu, double *nu, dou
  * lambda <= 0, normB2 < 0, non-finite values, delta_max == NULL. */
 int sbtv_skrock_max_step(int stages, double eta, double sigma2, double lambda, double normB2, double *delta_max);
 
+/* ---- TV posterior at fixed parameters: SK-ROCK in the image domain -------------------------------------------------------
+ * No entry of the reference.  The sampler above on the target of sbtv_myula (the closures of SALSA/run_deblur_tv.m:126,131 with
+ * theta[b] and sigma2[b] per chain), the experiment of the SK-ROCK paper itself.  The drift is
+ *     D(K) = (prox(K) - K)/lambda - AT(A K - y)/sigma2_b,
+ *     prox(K) = chambolle_prox_TV_stop(K, 'lambda', lambda theta_b, 'maxiter', chambolleit)   (the library's tol / tau)
+ * and every evaluation of the prox starts from zero duals, as sbtv_myula's does.  Table and step: exactly those stated for
+ * sbtv_skrock_wavelet above (P, K_1, K_j, the SAME Z three times, q = sqrt(2 delta)), grouped as written there, no
+ * floating-point contraction; the table is sbtv_skrock_coefficients.  X(1) = x0 (NULL: y).  Samples ii = 2..samples, no
+ * off-by-one: the samples-1 quirk of SALSA/myula.m:13 is NOT copied.  Traces, ii = 1..samples:
+ *     gx(ii)    = TVnorm(X(ii))
+ *     logpi(ii) = -||y - A X(ii)||^2 / (2 sigma2_b) - theta_b gx(ii)
+ * Stability: delta <= sbtv_skrock_max_step(stages, eta, sigma2, lambda, 1.0, ...) (||A|| = 1 for a normalised non-negative
+ * PSF; the prox term has Lipschitz constant 1/lambda).  The entry does not police delta, as sbtv_myula does not police gamma.
+ * What runs: one step is s x (cold prox, gradient pass, one element-wise stage kernel: 32 B per pixel the first, 40 B a middle
+ * one, 48 B the last, which also forms P of the next step) and, when a trace is requested, one residual pass on X(ii); the TV
+ * partials ride on its forward column pass where the size allows.  Every stage kernel re-arms the prox control blocks, so no
+ * reset launch sits inside a step.  Two image buffers, prox and gradient.  Partial sums of up to 1024 samples wait in a ring;
+ * one launch turns them into trace entries, every sum in a fixed order; one synchronisation per 1024 steps and one at the
+ * end.  With gx == NULL and logpi == NULL the residual pass is not launched.  Chains of a batch share every launch; chain b is
+ * computed bit for bit as alone.  The call counter does not advance: the operator layer counts nothing for the s gradient
+ * passes and the residual pass of a step, as for sbtv_myula.  No lanes, no graph capture, no sharded variant, and the stage is
+ * not fused into the inverse column pass.
+ *   noise: NULL (device Philox randn with the counters of sbtv_myula: pair q of chain b at sample ii draws
+ *          (q, ii - 2, chain_offset + b), so a seed names the same normals in both samplers) or (samples-1) * batch * M*N
+ *          doubles, step-major, host or device
+ *   gx, logpi: [batch][samples], host, either may be NULL;  x_last: the last sample, may be NULL
+ * Moments (mo != NULL), of the samples 1..samples: selection (first = 0 means 1), pooling (pooled = 1 only for chains with the
+ * same y, taps, theta and sigma2), outputs and refusals as for sbtv_myula_moments; accumulated in the registers of the last
+ * stage kernel, unselected samples launch the plain kernel.  No bit of the chain or the traces depends on what is
+ * accumulated or on which traces are requested.
+ *   SBTV_DEVICE_PTRS applies to y / x0 / noise / x_last / post_mean / post_var.
+ * Refused before any GPU work: what sbtv_myula refuses, with its codes, gamma aside (SBTV_ERR_MAXITER for chambolleit <= 0,
+ * SBTV_ERR_PSF, SBTV_ERR_SIZE for an odd pixel count); with SBTV_ERR_BADARG: samples < 2, stages < 2, non-finite or <= 0
+ * lambda / delta / eta / theta[b] / sigma2[b], chain_offset < 0, op / theta / sigma2 == NULL, thin < 1, first < 0,
+ * first > samples, mo without post_mean, pooled = 1 on chains of different posteriors, a moment output with mo == NULL. */
+typedef struct sbtv_skrock_opts {
+    int    samples;            /* >= 2: sample 1 is the start state, samples-1 steps follow */
+    int    stages;             /* s >= 2 drift evaluations per step                          */
+    int    chambolleit;        /* > 0: Chambolle iterations of every prox, cold start        */
+    double lambda, delta, eta; /* Moreau-Yosida parameter, step, damping (e.g. 0.05)         */
+    unsigned long long seed;   /* Philox seed when noise == NULL                             */
+    int    chain_offset;       /* chain b draws the Philox stream chain_offset + b           */
+} sbtv_skrock_opts;
+int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                const sbtv_skrock_opts *op, const double *theta, const double *sigma2,
+                const double *x0, const double *noise, double *gx, double *logpi, double *x_last,
+                const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags);
+
 /* ---- a-9: largest eigenvalue of A'A by power iteration --------------------
  * Replaces max_eigenval(A,At,params,im_size,tol,max_iter,verbose)
  * (utils/max_eigenval_Gaussian_Moffat.m:1-27, max_eigenval_Laplace.m:1-28).

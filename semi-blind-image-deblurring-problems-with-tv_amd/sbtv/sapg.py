@@ -412,3 +412,65 @@ def myula_moments(op, im=None, noise=None, posterior=True, ctx=None):
     one = sq and not mo.pooled
     return dict(x=L.images_result(xo, sq), mean=L.images_result(pm, one or mo.pooled),
                 var=L.images_result(pv, one or mo.pooled), count=int(pc[0]) if (one or mo.pooled) else pc.copy())
+
+
+def skrock(op, im=None, noise=None, x0=None, posterior=None, ctx=None):
+    """SK-ROCK chain on the TV posterior at fixed theta / PSF / sigma2 (sbtv_skrock): the target and closures of sbtv.myula
+    with the explicit stabilised step of Pereyra, Vargas Mieles and Zygalakis (SIAM J. Imaging Sci. 2020), stated in
+    include/sbtv.h.  Sample 1 is the start state (x0, default y), op.samples - 1 steps follow (no off-by-one).
+
+    op: the fields of sbtv.myula (y, lambda, theta_op, samples, A, sigma2 or sigma, chambolleit (25), seed (1),
+    chain_offset (0)) without gamma, plus `stages` (s >= 2 drift evaluations per step), `delta` (the step; None: 0.8 of
+    skrock_max_step at ||A|| = 1 and the call's smallest sigma2) and `eta` (0.05).  `im` is ignored, as in myula.
+    noise: optional (samples-1, [B,] M, N) normals instead of the device Philox stream; x0: optional start images.
+    posterior: None | True | dict(first=1, thin=1, pooled=False): moments of the samples 1..samples.
+    Returns dict(x = last sample, gx, logpi: (samples,) or (B, samples)[, mean, var, count])."""
+    from .wavelet import skrock_max_step
+    ctx = ctx or L.default_context()
+    A = _get(op, "A")
+    if not isinstance(A, BlurOperator):
+        raise TypeError("op.A must be the sbtv.BlurOperator the closures op.gradF / op.proxG are built from")
+    yi = L.Images(_get(op, "y"))
+    B, M, N = yi.B, yi.M, yi.N
+    s2 = _get(op, "sigma2")
+    if s2 is None:
+        s2 = np.asarray(_get(op, "sigma"), dtype=np.float64) ** 2
+    th, s2v = L.dvec(_get(op, "theta_op"), B), L.dvec(s2, B)
+    taps = A._cm(B)
+    o = L.sbtv_skrock_opts()
+    o.samples, o.stages, o.chambolleit = int(_get(op, "samples")), int(_get(op, "stages")), int(_get(op, "chambolleit", 25))
+    o.lambda_, o.eta = float(_get(op, "lambda")), float(_get(op, "eta", 0.05))
+    delta = _get(op, "delta")
+    o.delta = float(delta) if delta is not None else 0.8 * skrock_max_step(o.stages, o.eta, float(np.min(s2v[0])), o.lambda_)
+    o.seed, o.chain_offset = int(_get(op, "seed", 1)), int(_get(op, "chain_offset", 0))
+    S = max(o.samples, 1)
+    xo = L.empty_like_images(yi)
+    x0i = None if x0 is None else L.Images(x0)
+    if x0i is not None and (x0i.torch != yi.torch or (x0i.B, x0i.M, x0i.N) != (B, M, N)):
+        raise ValueError("x0 must have the shape and the memory kind of op.y")
+    nz_ptr, nz_keep = None, None
+    if noise is not None:
+        if L._is_torch(noise):
+            nz_keep, nz_ptr = noise, C.c_void_p(noise.data_ptr())
+        else:
+            a = np.asarray(noise, dtype=np.float64)
+            if a.ndim == 3:
+                a = a[:, None]
+            nz_keep = L.column_major_images(a.reshape((-1,) + a.shape[2:])).reshape(a.shape[:2] + (a.shape[3], a.shape[2]))
+            nz_ptr = L.vptr(nz_keep)
+    gx, logpi = np.zeros((B, S)), np.zeros((B, S))
+    mo, pm, pv, pc = None, None, None, None
+    if posterior is not None and posterior is not False:
+        mo = _moments_opts(posterior)
+        pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else B)
+    ctx.check(ctx.lib.sbtv_skrock(ctx.h, yi.ptr, M, N, B, L.vptr(taps), A.taille, C.byref(o), th[1], s2v[1],
+                                  None if x0i is None else x0i.ptr, nz_ptr, L.vptr(gx), L.vptr(logpi), xo.ptr,
+                                  None if mo is None else C.byref(mo), None if mo is None else pm.ptr,
+                                  None if mo is None else pv.ptr, None if mo is None else L.vptr(pc), yi.flags), yi.flags)
+    y = _get(op, "y")
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    res = dict(x=L.images_result(xo, sq), gx=gx[0] if sq else gx, logpi=logpi[0] if sq else logpi)
+    if mo is not None:
+        one = sq or mo.pooled
+        res.update(mean=L.images_result(pm, one), var=L.images_result(pv, one), count=int(pc[0]) if one else pc.copy())
+    return res
