@@ -782,6 +782,62 @@ int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const d
                 const double *x0, const double *noise, double *gx, double *logpi, double *x_last,
                 const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags);
 
+/* ---- SAPG estimation of theta, the PSF parameters and sigma2 with SK-ROCK as its Markov kernel -------------------------------
+ * No entry of the reference: sbtv_SAPG_algorithm with its MYULA move replaced by one step of sbtv_skrock, the authors' own
+ * follow-up to MYULA-SAPG.  `batch` independent chains, one per image y_b.  The scalars, projections, traces and quirks are
+ * exactly those of sbtv_SAPG_algorithm, and the arithmetic of the gradients and of the projected steps is the same code.  With
+ * theta, p, s for theta(ii-1), p(ii-1), sigma2(ii-1):
+ *     X = x0 (NULL: y)
+ *     warm-up, ii = 2..warmup, at th_init, p_init, sigma2_init:
+ *         X = SKROCK_step(X; th_init, p_init, sigma2_init);   logpi_wu(ii) = logPi(X, th_init, p_init, sigma2_init)
+ *     logpi(1) = logPi(X, theta(1), p(1), sigma2(1))
+ *     ii = 2..samples:
+ *         X(ii) = SKROCK_step(X(ii-1); theta, p, s)
+ *         r = A_p X(ii) - y;  R = ||r||^2;  g = TVnorm(X(ii))
+ *         G_theta = dimX/theta - g;  G_pq = <dA/dp_q(p) X(ii), r>/s;  G_sigma = R/(2 s^2) - dimX/(2 s)
+ *         theta(ii), p(ii), sigma2(ii): the projected steps of sbtv_SAPG_algorithm with
+ *                                       delta(ii) = d_scale (ii + iter_offset)^(-d_exp)/dimX
+ *         logpi(ii) = -R/(2 s) - theta g;   gx(ii-1) = g        (the index quirk of sbtv_SAPG_algorithm, kept)
+ *     eb = means over burnIn..samples
+ * SKROCK_step(X; theta, p, s) is the step of sbtv_skrock with delta = sk->dt: the table of sbtv_skrock_coefficients, P, K_1, K_j
+ * and the SAME Z three times, grouped as written for sbtv_skrock_wavelet, no contraction, on the drift
+ *     D(K) = (prox(K) - K)/lambda - A_p'(A_p K - y)/s,   prox(K) = chambolle_prox_TV_stop(K, lambda theta, maxiter = chambolleit)
+ * from zero duals.  Two deliberate differences from the MYULA loop:
+ *   - no abs() reflection of the new sample, as in sbtv_skrock;
+ *   - no lagging prox: every stage evaluates its prox at theta(ii-1), where the MYULA loop moves with the prox it formed at
+ *     the end of the previous iteration.
+ * op->gamma is ignored.  dt is not policed: the safe bound is sbtv_skrock_max_step(stages, eta, min(sigma2_min, sigma2_max),
+ * lambda, 1.0, ...), taken at the smallest sigma2 the chain may reach, because sigma2 moves.
+ * What runs: one step is, with a free PSF parameter, the spectra of the taps the previous update left on the device; stages x
+ * (cold prox, gradient pass with the current spectrum, one stage kernel of sbtv_skrock, which reads sigma2 and lambda theta
+ * from the device); one gradient-sum pass on X(ii) (the TV partials ride on its forward column pass where the size allows;
+ * its row pass stores nothing and has no inverse); and one update kernel, one workgroup per chain, which totals the chain's
+ * sums in a fixed order, steps its parameters, books its traces and burn-in sums and builds the taps and derivative taps of
+ * p(ii) (the device's libm; every mask size).  The host only enqueues: one synchronisation per 1024 steps and one at the
+ * end.  Chains of a batch share every launch but the arithmetic of none: chain b is computed bit for bit as alone.  The call
+ * counter does not advance.  Not offered: reduce_fn, a host-side loop, lanes, graph capture, a sharded variant.
+ *   noise: NULL (device Philox randn with the counters of sbtv_SAPG_algorithm: pair q of chain b draws (q, step,
+ *          chain_offset + b), steps count from 0 through the warm-up and on) or (max(warmup-1, 0) + samples-1) * batch * M*N
+ *          doubles, step-major, host or device
+ *   traces, eb, x_last: layouts as for sbtv_SAPG_algorithm
+ *   Moments (mo != NULL; NULL: none), of the iterations 1..samples as for sbtv_SAPG_algorithm_moments (iteration 1 is the
+ *          state after the warm-up; first = 0 means burnIn), accumulated in the registers of the last stage kernel; no bit of
+ *          the chain or its traces depends on them.  pooled = 1 only with batch = 1: the chains estimate their own parameters.
+ *   SBTV_DEVICE_PTRS applies to y / x0 / noise / x_last / post_mean / post_var.
+ * Refused before any GPU work: everything sbtv_SAPG_algorithm refuses, with its codes; with SBTV_ERR_BADARG also
+ * share_gradients != 0, sk == NULL, stages < 2, non-finite or <= 0 dt / eta, and the moment refusals of sbtv_skrock (thin < 1,
+ * first < 0, first > samples, mo without post_mean, a moment output with mo == NULL, pooled = 1 with batch > 1). */
+typedef struct sbtv_sapg_skrock_step {
+    int    stages;             /* s >= 2 drift evaluations per step                          */
+    double dt;                 /* the step of the chain (delta of sbtv_skrock)               */
+    double eta;                /* damping (e.g. 0.05)                                        */
+} sbtv_sapg_skrock_step;
+int sbtv_SAPG_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op,
+                     const sbtv_sapg_skrock_step *sk, const double *x0, const double *noise,
+                     double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu, double *gx,
+                     double *grads, double *eb, double *x_last,
+                     const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags);
+
 /* ---- a-9: largest eigenvalue of A'A by power iteration --------------------
  * Replaces max_eigenval(A,At,params,im_size,tol,max_iter,verbose)
  * (utils/max_eigenval_Gaussian_Moffat.m:1-27, max_eigenval_Laplace.m:1-28).

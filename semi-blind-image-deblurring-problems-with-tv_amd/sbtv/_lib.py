@@ -95,6 +95,10 @@ class sbtv_skrock_opts(C.Structure):
                 ("delta", C.c_double), ("eta", C.c_double), ("seed", C.c_ulonglong), ("chain_offset", C.c_int)]
 
 
+class sbtv_sapg_skrock_step(C.Structure):
+    _fields_ = [("stages", C.c_int), ("dt", C.c_double), ("eta", C.c_double)]
+
+
 class sbtv_diag_pass(C.Structure):
     _fields_ = ([(n, C.c_int) for n in ("M", "N", "batch", "op", "epilogue", "taille", "shared_spec", "repeats")]
                 + [(n, C.c_void_p) for n in ("x", "add", "taps", "d1taps", "d2taps", "y", "e0", "mu", "cs", "frozen", "u",
@@ -174,6 +178,8 @@ SIGNATURES = {
                                  _P, _P, C.POINTER(sbtv_moments_opts), _P, _P, _P, _P, _P, _I]),
     "sbtv_skrock": (_I, [_P, _P, _I, _I, _I, _P, _I, C.POINTER(sbtv_skrock_opts), _P, _P, _P, _P, _P, _P, _P,
                          C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
+    "sbtv_SAPG_skrock": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), C.POINTER(sbtv_sapg_skrock_step), _P, _P, _P, _P, _P,
+                              _P, _P, _P, _P, _P, _P, C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
     "sbtv_skrock_coefficients": (_I, [_I, _D, _P, _P, _P, _P, _P]),
     "sbtv_skrock_max_step": (_I, [_I, _D, _D, _D, _D, C.POINTER(_D)]),
     "sbtv_max_eigenval": (_I, [_P, _P, _I, _P, _I, _I, _D, _I, _P, _P, _I]),

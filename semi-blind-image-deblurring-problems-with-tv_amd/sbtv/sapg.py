@@ -127,8 +127,10 @@ def combine_moments(parts):
 
 
 def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=None, ctx=None, reduce_dev_fn=None,
-          host_loop=False, posterior=None):
-    """reduce_fn(user, buf, n): host all-reduce of the shared-gradient sums (selects the host-side parameter loop);
+          host_loop=False, posterior=None, skrock=None):
+    """skrock = (stages, dt, eta): the chain moves with SK-ROCK steps (sbtv_SAPG_skrock) instead of MYULA steps; no
+    share_gradients, reduce_fn, host_loop or sbtv.Group then.
+    reduce_fn(user, buf, n): host all-reduce of the shared-gradient sums (selects the host-side parameter loop);
     reduce_dev_fn(user, dev_ptr, n, stream): in-stream all-reduce on the device buffer (`dist.make_device_allreduce_fn`),
     the loop stays device-resident; host_loop=True forces the host-side loop (SBTV_SAPG_HOST_LOOP).
     posterior = True | dict(first, thin, pooled): also the posterior mean / variance of the samples
@@ -147,7 +149,8 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
     o.chambolleit = int(_get(op, "chambolleit", 25))              # run_Gaussian_demo.m:188
     o.share_gradients = 1 if share_gradients else 0
     o.lambda_ = float(c.get("lam", 1.0)) * float(_get(op, "lambda"))     # lamb = c.lam*op.lambda (:30)
-    o.gamma = float(c.get("gam", 1.0)) * float(_get(op, "gamma"))
+    # sbtv_SAPG_skrock ignores gamma: op need not carry it then
+    o.gamma = float(c.get("gam", 1.0)) * float(_get(op, "gamma", 0.0) if skrock is not None else _get(op, "gamma"))
     o.th_init = float(_get(op, "th_init"))
     o.min_th = float(_get(op, "min_th"))
     o.max_th = float(_get(op, "max_th"))
@@ -216,7 +219,20 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
     if posterior is not None and posterior is not False and getattr(ctx, "is_group", False):
         raise NotImplementedError("posterior moments over a sbtv.Group: run the shards' chains per call and "
                                   "sbtv.combine_moments their results")
-    if getattr(ctx, "is_group", False):
+    if skrock is not None:
+        if share_gradients or reduce_fn is not None or reduce_dev_fn is not None or host_loop or getattr(ctx, "is_group", False):
+            raise ValueError("SAPG_skrock offers no share_gradients, reduce_fn, host_loop or sbtv.Group")
+        sk = L.sbtv_sapg_skrock_step(int(skrock[0]), float(skrock[1]), float(skrock[2]))
+        mo = pm = pv = pc = None
+        if posterior is not None and posterior is not False:
+            mo = _moments_opts(posterior)
+            pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else nch)
+        ctx.check(ctx.lib.sbtv_SAPG_skrock(ctx.h, yptr, M, N, nch, C.byref(o), C.byref(sk), x0i.ptr if x0i else None, nz_ptr,
+                                           vp(thetas), vp(ps), vp(sigmas), vp(logpi), vp(logpi_wu), vp(gx), vp(grads),
+                                           vp(eb), xl.ptr, None if mo is None else C.byref(mo),
+                                           None if mo is None else pm.ptr, None if mo is None else pv.ptr,
+                                           None if mo is None else vp(pc), yi.flags), yi.flags)
+    elif getattr(ctx, "is_group", False):
         # several GPUs behind this process (sbtv.Group): images / chains dealt to the devices in contiguous blocks; with
         # share_gradients the six gradient sums are exchanged in-process, in-stream (no reduce_fn needed or accepted)
         if yi.flags != L.SBTV_HOST_PTRS or (noise is not None and L._is_torch(noise)):
@@ -335,6 +351,17 @@ def SAPG_algorithm_laplace(y, op, c=None, **kw):
     c = c or dict(theta=0.01, b=100.0, sigma=1e4, lam=1.0, gam=1.0)
     res = _sapg("laplace", y, op, c, **kw)
     return _unpack("laplace", res, len(res) > 1)
+
+
+def SAPG_skrock(kind, y, op, c, stages, dt, eta=0.05, noise=None, x0=None, posterior=None, ctx=None):
+    """SAPG_algorithm_Guassian / _moffat / _laplace (kind = "gaussian" | "moffat" | "laplace") with SK-ROCK as the Markov
+    kernel (sbtv_SAPG_skrock, include/sbtv.h): every iteration moves the chain by one SK-ROCK step of `stages` drift
+    evaluations and step `dt` at the current theta, PSF parameters and sigma2.  op.gamma is not used.  dt: at most
+    sbtv.skrock_max_step(stages, eta, min(op.sigma_min, op.sigma_max), lambda), the bound at the smallest sigma2 the chain
+    may reach.  noise: optional (max(warmup-1, 0) + samples-1, [B,] M, N) normals instead of the device Philox stream.
+    Returns what the mirror of that family returns: (theta_EB, <PSF parameters>_EB, sigma_EB, results)."""
+    res = _sapg(kind, y, op, c, noise=noise, x0=x0, posterior=posterior, ctx=ctx, skrock=(stages, dt, eta))
+    return _unpack(kind, res, len(res) > 1)
 
 
 def myula(op, im=None, noise=None, ctx=None):
