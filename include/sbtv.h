@@ -273,8 +273,8 @@ int sbtv_CoRAL_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
  * Errors before any GPU work: mask == NULL, mu1[b] <= 0, mu2[b] <= 0 -> SBTV_ERR_BADARG; odd pixel count -> SBTV_ERR_SIZE;
  * stop criterion and initialization as sbtv_SALSA_v2.  With SBTV_HOST_PTRS a mask with a negative or non-finite entry is
  * rejected (SBTV_ERR_BADARG); a device-resident mask (it lives where y lives) is the caller's responsibility.
- * Out of scope: the SAPG / MYULA samplers keep the circular, fully observed likelihood (their gradients and parameter
- * sums live in the spectral domain by Parseval, which a mask breaks). */
+ * The samplers of the same likelihood, which estimate the tau, the PSF parameters and the sigma2 this entry needs, are
+ * sbtv_myula_masked and sbtv_SAPG_masked below. */
 int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch,
                       const double *taps, int taille, const double *tau, const double *mu1, const double *mu2,
                       const sbtv_salsa_opts *opts, const double *true_x, const double *x_init,
@@ -834,6 +834,59 @@ typedef struct sbtv_sapg_skrock_step {
 } sbtv_sapg_skrock_step;
 int sbtv_SAPG_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op,
                      const sbtv_sapg_skrock_step *sk, const double *x0, const double *noise,
+                     double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu, double *gx,
+                     double *grads, double *eb, double *x_last,
+                     const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags);
+
+/* ---- masked-observation MYULA and SAPG on the TV model -----------------------------------------------------------
+ * No entry of the reference: the chains of sbtv_myula and sbtv_SAPG_algorithm on the likelihood of sbtv_SALSA_masked, an
+ * observation that does not wrap round or that has missing or weighted pixels.  With m = mask (M*N*batch non-negative weights
+ * like y, 0 = not observed), n_obs = the number of pixels of a chain with m > 0 and B_p the circular blur at the PSF
+ * parameters p:
+ *     p(y | x, p, s2) ~ s2^(-n_obs/2) exp( -R / (2 s2) ),   R = sum( m .* (B_p x - y).^2 )
+ *     gradF(x)  = B_p' ( m .* (B_p x - y) ) / s2
+ *     G_theta   = dimX / theta - TVnorm(X)                     (dimX = M*N, unchanged: the prior covers every pixel)
+ *     G_p(q)    = sum( (dB/dp_q X) .* m .* (B_p X - y) ) / s2
+ *     G_sigma   = R / (2 s2^2) - n_obs / (2 s2)
+ *     logPi     = -R / (2 s2) - theta * TVnorm(X)
+ * Everything else is the loop of sbtv_myula / sbtv_SAPG_algorithm line for line: the MYULA move (the reflecting abs() in SAPG,
+ * none in myula), the prox the SAPG move uses (formed at the end of the previous iteration), the order of the updates, the
+ * projections, delta(ii), the burn-in means, the traces with their layouts and index quirks, and the Philox counters.  With
+ * m = 1 everywhere the model is that of those entries; the sums are then taken in space where they take them by Parseval, so
+ * the traces agree to rounding, not bit for bit.
+ * y enters only as m .* y: its values under m = 0 must be finite and influence no output, with one exception: sbtv_myula_masked
+ * always, and sbtv_SAPG_masked with x0 == NULL, start from y as given.
+ * The steps gamma the demos compute (1 / (Lf + 1/lambda), Lf = ||B||^2 / sigma2) hold for max(m) <= 1; larger weights raise
+ * the Lipschitz constant of gradF by max(m) and are the caller's to account for.
+ * What runs: the gradient's middle and the three sums are spatial.  One element-wise kernel writes
+ * r = m .* (B x - y) and leaves per-workgroup partial sums of R, <dB/dp_1 X, r>, <dB/dp_2 X, r>, summed in a fixed order without
+ * atomics; one kernel, one workgroup per chain, totals them, runs the parameter step of sbtv_SAPG_algorithm (the same code),
+ * books the traces and builds the taps of p(ii).  B X, dB/dp_1 X, dB/dp_2 X come from one forward column pass (grads books
+ * G_p whether or not p is free, as sbtv_SAPG_algorithm does).  With the PSF fixed the r of the sums is the next gradient's
+ * input and no spectrum is rebuilt; with a free PSF parameter B X and r are formed again after the update, with the new
+ * spectrum, from the column spectrum still held.  sbtv_myula_masked and the warm-up take two FFT round trips per iteration
+ * (B X, B' r).  The loops are device-resident: the host only enqueues, one synchronisation per 1024 iterations and one at the
+ * end.  Chains of a batch share every launch but the arithmetic of none: chain b is computed bit for bit as alone.  n_obs is
+ * counted on the device once per call.  Not offered: reduce_fn, share_gradients, a host-side loop, lanes, graph capture, a
+ * sharded variant.  The call counter does not advance.
+ *
+ * sbtv_myula_masked: sbtv_myula / sbtv_myula_moments (arguments, noise layout, Philox counters, iterations 1 = y, 2..samples-1).
+ *   mo == NULL: no moments, and post_mean, post_var, post_count must be NULL; otherwise as for sbtv_myula_moments (first = 0
+ *   means 1), pooled = 1 only with batch = 1 (the chains have their own masks).
+ * sbtv_SAPG_masked: sbtv_SAPG_algorithm (op, x0, noise, traces, eb, x_last and their layouts); moments as for sbtv_SAPG_skrock
+ *   (mo == NULL: none; first = 0 means burnIn; pooled = 1 only with batch = 1).
+ * SBTV_DEVICE_PTRS applies to y / mask / x0 / noise / x_out / x_last / post_mean / post_var.
+ * Refused before any GPU work: everything sbtv_myula / sbtv_SAPG_algorithm refuse, with their codes; with SBTV_ERR_BADARG also
+ * mask == NULL, share_gradients != 0, a moment output with mo == NULL, pooled = 1 with batch > 1 and, with SBTV_HOST_PTRS, a
+ * negative or non-finite mask entry or a chain whose mask has no positive entry.  A device-resident mask is the caller's
+ * responsibility, as for sbtv_SALSA_masked. */
+int sbtv_myula_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch,
+                      const double *taps, int taille, double lambda, double gamma, const double *theta,
+                      const double *sigma2, int samples, int chambolleit, unsigned long long seed, int chain_offset,
+                      const double *noise, double *x_out, const sbtv_moments_opts *mo, double *post_mean,
+                      double *post_var, long long *post_count, int flags);
+int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch,
+                     const sbtv_sapg_opts *op, const double *x0, const double *noise,
                      double *thetas, double *ps, double *sigmas, double *logpi, double *logpi_wu, double *gx,
                      double *grads, double *eb, double *x_last,
                      const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags);

@@ -180,6 +180,10 @@ SIGNATURES = {
                          C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
     "sbtv_SAPG_skrock": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), C.POINTER(sbtv_sapg_skrock_step), _P, _P, _P, _P, _P,
                               _P, _P, _P, _P, _P, _P, C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
+    "sbtv_myula_masked": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _D, _D, _P, _P, _I, _I, C.c_ulonglong, _I, _P, _P,
+                               C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
+    "sbtv_SAPG_masked": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                              C.POINTER(sbtv_moments_opts), _P, _P, _P, _I]),
     "sbtv_skrock_coefficients": (_I, [_I, _D, _P, _P, _P, _P, _P]),
     "sbtv_skrock_max_step": (_I, [_I, _D, _D, _D, _D, C.POINTER(_D)]),
     "sbtv_max_eigenval": (_I, [_P, _P, _I, _P, _I, _I, _D, _I, _P, _P, _I]),

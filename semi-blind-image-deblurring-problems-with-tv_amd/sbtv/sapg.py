@@ -127,8 +127,10 @@ def combine_moments(parts):
 
 
 def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=None, ctx=None, reduce_dev_fn=None,
-          host_loop=False, posterior=None, skrock=None):
-    """skrock = (stages, dt, eta): the chain moves with SK-ROCK steps (sbtv_SAPG_skrock) instead of MYULA steps; no
+          host_loop=False, posterior=None, skrock=None, mask=None):
+    """mask: the chains sample the masked-observation posterior (sbtv_SAPG_masked): non-negative weights with the shape and the
+    memory kind of y; no share_gradients, reduce_fn, host_loop, skrock or sbtv.Group then.
+    skrock = (stages, dt, eta): the chain moves with SK-ROCK steps (sbtv_SAPG_skrock) instead of MYULA steps; no
     share_gradients, reduce_fn, host_loop or sbtv.Group then.
     reduce_fn(user, buf, n): host all-reduce of the shared-gradient sums (selects the host-side parameter loop);
     reduce_dev_fn(user, dev_ptr, n, stream): in-stream all-reduce on the device buffer (`dist.make_device_allreduce_fn`),
@@ -219,7 +221,23 @@ def _sapg(kind, y, op, c, noise=None, x0=None, share_gradients=False, reduce_fn=
     if posterior is not None and posterior is not False and getattr(ctx, "is_group", False):
         raise NotImplementedError("posterior moments over a sbtv.Group: run the shards' chains per call and "
                                   "sbtv.combine_moments their results")
-    if skrock is not None:
+    if mask is not None:
+        if (share_gradients or reduce_fn is not None or reduce_dev_fn is not None or host_loop or skrock is not None
+                or getattr(ctx, "is_group", False)):
+            raise ValueError("SAPG_masked offers no share_gradients, reduce_fn, host_loop, skrock or sbtv.Group")
+        mi = L.Images(mask)
+        if mi.torch != yi.torch or (mi.B, mi.M, mi.N) != (B, M, N):
+            raise ValueError("mask must have the shape and the memory kind of y")
+        mo = pm = pv = pc = None
+        if posterior is not None and posterior is not False:
+            mo = _moments_opts(posterior)
+            pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else nch)
+        ctx.check(ctx.lib.sbtv_SAPG_masked(ctx.h, yptr, mi.ptr, M, N, nch, C.byref(o), x0i.ptr if x0i else None, nz_ptr,
+                                           vp(thetas), vp(ps), vp(sigmas), vp(logpi), vp(logpi_wu), vp(gx), vp(grads),
+                                           vp(eb), xl.ptr, None if mo is None else C.byref(mo),
+                                           None if mo is None else pm.ptr, None if mo is None else pv.ptr,
+                                           None if mo is None else vp(pc), yi.flags), yi.flags)
+    elif skrock is not None:
         if share_gradients or reduce_fn is not None or reduce_dev_fn is not None or host_loop or getattr(ctx, "is_group", False):
             raise ValueError("SAPG_skrock offers no share_gradients, reduce_fn, host_loop or sbtv.Group")
         sk = L.sbtv_sapg_skrock_step(int(skrock[0]), float(skrock[1]), float(skrock[2]))
@@ -362,6 +380,68 @@ def SAPG_skrock(kind, y, op, c, stages, dt, eta=0.05, noise=None, x0=None, poste
     Returns what the mirror of that family returns: (theta_EB, <PSF parameters>_EB, sigma_EB, results)."""
     res = _sapg(kind, y, op, c, noise=noise, x0=x0, posterior=posterior, ctx=ctx, skrock=(stages, dt, eta))
     return _unpack(kind, res, len(res) > 1)
+
+
+def SAPG_masked(kind, y, mask, op, c, noise=None, x0=None, posterior=None, ctx=None):
+    """SAPG_algorithm_Guassian / _moffat / _laplace (kind = "gaussian" | "moffat" | "laplace") on the masked-observation
+    likelihood of sbtv.SALSA_masked (sbtv_SAPG_masked, include/sbtv.h): R = sum(mask .* (B_p x - y).^2) and the number of
+    observed pixels take the place of ||B_p x - y||^2 and dimX in the likelihood, its gradient and the sigma2 step.  mask:
+    non-negative weights like y (0 = not observed; embed a valid convolution with sbtv.embed_observation / valid_mask).
+    op.gamma as the demos compute it holds for max(mask) <= 1.  noise: optional (max(warmup-1, 0) + samples-1, [B,] M, N)
+    normals instead of the device Philox stream.
+    Returns what the mirror of that family returns: (theta_EB, <PSF parameters>_EB, sigma_EB, results)."""
+    res = _sapg(kind, y, op, c, noise=noise, x0=x0, posterior=posterior, ctx=ctx, mask=mask)
+    return _unpack(kind, res, len(res) > 1)
+
+
+def myula_masked(op, mask, im=None, noise=None, posterior=None, ctx=None):
+    """sbtv.myula / sbtv.myula_moments on the masked-observation likelihood (sbtv_myula_masked): gradF(x) =
+    AT(mask .* (A x - y)) / sigma2.  mask: non-negative weights with the shape and the memory kind of op.y.  The chain starts
+    from op.y as given.  posterior = None: the last sample, as sbtv.myula returns it; True | dict(first=1, thin=1): what
+    sbtv.myula_moments returns, dict(x, mean, var, count).  Other arguments as for sbtv.myula."""
+    ctx = ctx or L.default_context()
+    A = _get(op, "A")
+    if not isinstance(A, BlurOperator):
+        raise TypeError("op.A must be the sbtv.BlurOperator the closures op.gradF / op.proxG are built from")
+    yi = L.Images(_get(op, "y"))
+    B, M, N = yi.B, yi.M, yi.N
+    mi = L.Images(mask)
+    if mi.torch != yi.torch or (mi.B, mi.M, mi.N) != (B, M, N):
+        raise ValueError("mask must have the shape and the memory kind of op.y")
+    s2 = _get(op, "sigma2")
+    if s2 is None:
+        s2 = np.asarray(_get(op, "sigma"), dtype=np.float64) ** 2
+    keep = [L.dvec(_get(op, "theta_op"), B), L.dvec(s2, B)]
+    taps = A._cm(B)
+    xo = L.empty_like_images(yi)
+    nz_ptr, nz_keep = None, None
+    if noise is not None:
+        if L._is_torch(noise):
+            nz_keep, nz_ptr = noise, C.c_void_p(noise.data_ptr())
+        else:
+            a = np.asarray(noise, dtype=np.float64)
+            if a.ndim == 3:
+                a = a[:, None]
+            nz_keep = L.column_major_images(a.reshape((-1,) + a.shape[2:])).reshape(a.shape[:2] + (a.shape[3], a.shape[2]))
+            nz_ptr = L.vptr(nz_keep)
+    mo = pm = pv = pc = None
+    if posterior is not None and posterior is not False:
+        mo = _moments_opts(posterior)
+        pm, pv, pc = _moment_buffers(yi, 1 if mo.pooled else B)
+    ctx.check(ctx.lib.sbtv_myula_masked(ctx.h, yi.ptr, mi.ptr, M, N, B, L.vptr(taps), A.taille,
+                                        float(_get(op, "lambda")), float(_get(op, "gamma")), keep[0][1], keep[1][1],
+                                        int(_get(op, "samples")), int(_get(op, "chambolleit", 25)),
+                                        int(_get(op, "seed", 1)), int(_get(op, "chain_offset", 0)), nz_ptr, xo.ptr,
+                                        None if mo is None else C.byref(mo), None if mo is None else pm.ptr,
+                                        None if mo is None else pv.ptr, None if mo is None else L.vptr(pc), yi.flags),
+              yi.flags)
+    y = _get(op, "y")
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    if mo is None:
+        return L.images_result(xo, sq)
+    one = sq or mo.pooled
+    return dict(x=L.images_result(xo, sq), mean=L.images_result(pm, one), var=L.images_result(pv, one),
+                count=int(pc[0]) if one else pc.copy())
 
 
 def myula(op, im=None, noise=None, ctx=None):
