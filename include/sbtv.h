@@ -488,6 +488,50 @@ int sbtv_fista_tv(sbtv_ctx *ctx, const double *b, int M, int N, int batch,
                   int zero_start, const double *true_x, double *x_out,
                   double *objective, double *mses, int *n_iter, int flags);
 
+/* ---- FISTA on the wavelet-l1 problem --------------------------------------
+ * Replaces my_fista_l1(b,h,tau,W,WT,stopcriterion,tolerance,maxiters,true,verbose) (SALSA/my_fista_l1.m:5-68), the FISTA the
+ * SALSA toolbox compares its solver with: min over x  0.5 ||b - B W x||^2 + tau ||x||_1 on the coefficients x of the frame of
+ * sbtv_mrdwt_TI2D, A = B W, AT = W' B' (:12-13).  The reference fixes L = 1 (:7) and starts at zero (:20-22, t(1) = 1); its
+ * iteration k = 2..maxiters is (:34-66)
+ *     x_old = x ;  t_old = t
+ *     y = y - (1/L) AT(A(y) - b) ;  x = soft(y, tau/L)
+ *     t = 0.5 (1 + sqrt(1 + 4 t_old^2)) ;  y = x + ((t_old - 1)/t) (x - x_old)
+ *     objective(k) = 0.5 ||A(x) - b||^2 + tau sum|x| ;  mses(k) = ||x - true||^2 / numel(true)
+ *     criterion: 1 |objective(k) - objective(k-1)| / objective(k) ; 2 ||x - x_old|| / sqrt(sum x^2) ; 3 objective(k)
+ *     break if criterion < tolerance          (from k = 2 on)
+ * with objective(1), mses(1) from the start (:27-29).  IEEE semantics of the criteria are kept: at x = 0 rule 2 is 0/0 = NaN,
+ * which is never below the tolerance.
+ * What runs: the momentum point y is never stored.  The coefficients x_{k-1}, x_{k-2} and their images zx = W x live in two
+ * buffers each that swap roles; with c the factor (t_old - 1)/t of the iteration before (0 for k = 2) iteration k is
+ *     zy = zx_{k-1} + c (zx_{k-1} - zx_{k-2})  (= W y) ;  g = W' B'(B zy - b)
+ *     x_k = soft((x_{k-1} + c (x_{k-1} - x_{k-2})) - (1/L) g, tau/L) ;  zx_k = W x_k ;  ||B zx_k - b||^2 by Parseval
+ * one synthesis per iteration instead of two: a momentum pass over the pixels, the FFT triple of the gradient, one analysis
+ * (J launches), the step pass over the coefficients with the sums of the traces, one synthesis (J launches), the residual
+ * passes and one reduction launch.  The host evaluates the stop rule one iteration late while the next iteration runs;
+ * that iteration writes the buffers of x_{k-1}, so xw_out / x_out are those of the stopping iteration.  With
+ * SBTV_FISTA_L1_NOLAG the host waits for every iteration (same result).
+ * b: [batch][M*N]; taps [batch][taille^2]; h / hlen / levels and the coefficient layout [batch][3J+1][M*N] as for
+ * sbtv_SALSA_wavelet; tau[batch] (host) >= 0; L > 0 (any L >= ||B||^2 converges).  xw_init NULL: the zero start of the
+ * reference; otherwise (an extension) x = y = xw_init, t = 1, objective(1) from that state.  xw_out (required): the
+ * coefficients of the stopping iteration; x_out (optional): W xw_out.  true_xw may be NULL: mses is then not written.
+ * objective / times / mses: [batch][maxiters], host, any may be NULL; entry 0 is the state before the loop, entry k-1
+ * iteration k of the reference; n_iter[b] is the last k run, entries from n_iter[b] on are not written; times[0] = 0, then
+ * wall seconds since the loop started when the host books the iteration.  maxiters = 1 returns the start state.
+ * Images of a batch are solved one after another, image k bit for bit as alone.  SBTV_DEVICE_PTRS applies to b / true_xw /
+ * xw_init / xw_out / x_out.  The call counter advances by 2 + 3 (n_iter - 1) per image, the reference's `calls` (:15-18).
+ * Refused before any GPU work: b, taps, h, tau or xw_out NULL, batch < 1, L not finite or <= 0, tolerance NaN, a tau[b]
+ * negative or not finite -> SBTV_ERR_BADARG; stopcriterion outside 1..3 -> SBTV_ERR_STOPCRITERION 'Invalid stopping
+ * criterion!' (:57); maxiters < 1 -> SBTV_ERR_MAXITER; taps that do not fit -> SBTV_ERR_PSF; for h / levels / size what
+ * sbtv_SALSA_wavelet refuses, with its codes (non-orthonormal h -> SBTV_ERR_BADARG, tap reach >= min(M, N) or an odd pixel
+ * count -> SBTV_ERR_SIZE). */
+#define SBTV_FISTA_L1_NOLAG 2   /* sbtv_fista_l1 only: the host waits for iteration k's scalars before it enqueues k+1 */
+int sbtv_fista_l1(sbtv_ctx *ctx, const double *b, int M, int N, int batch,
+                  const double *taps, int taille, const double *h, int hlen, int levels,
+                  const double *tau, double L, int stopcriterion, double tolerance, int maxiters,
+                  const double *true_xw, const double *xw_init,
+                  double *xw_out, double *x_out,
+                  double *objective, double *times, double *mses, int *n_iter, int flags);
+
 /* ---- a-5/a-6: SAPG (MYULA) parameter estimation ---------------------------
  * Replaces SAPG_algorithm_Guassian / _moffat / _laplace (SAPG/ directory) for `batch`
  * independent chains.  One chain = one image y_b with its own state.  */

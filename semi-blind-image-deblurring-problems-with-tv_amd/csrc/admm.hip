@@ -413,6 +413,44 @@ __global__ __launch_bounds__(AB) void wav_sum_kernel(const double *__restrict__ 
     }
 }
 
+// ---- wavelet-l1 FISTA (fista_l1_one) ------------------------------------------------------------------------------
+// zy = zx + c (zx - zxo): the image W y of the momentum point y = x + c (x - xo), by linearity of W
+__global__ __launch_bounds__(AB) void fl1_momentum_kernel(const double *__restrict__ zx, const double *__restrict__ zxo,
+                                                           double c, double *__restrict__ zy, size_t P) {
+    AD_LOOP(q, P) {
+        const double2 a = AD_LD(zx, q), b = AD_LD(zxo, q);
+        AD_ST(zy, q, make_double2(a.x + c * (a.x - b.x), a.y + c * (a.y - b.y)));
+    }
+}
+
+// The step of an iteration (my_fista_l1.m:38-39,42 of the iteration before): y = x + c (x - xo) ; xn = soft(y - (1/L) g, T),
+// T = tau / L, written over xo.  partials [3 or 4][nb]: |xn|, xn^2, (xn - x)^2 and, TRU, (xn - true)^2
+template <bool TRU>
+__global__ __launch_bounds__(AB) void fl1_step_kernel(const double *__restrict__ x, double *__restrict__ xo,
+                                                       const double *__restrict__ g, const double *__restrict__ tru, double c,
+                                                       double invL, double T, double *__restrict__ partials, size_t C) {
+    constexpr int NQ = TRU ? 4 : 3;
+    double acc[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) acc[i] = 0.0;
+    AD_LOOP(q, C) {
+        const double2 xv = AD_LD(x, q), ov = AD_LD(xo, q), gv = AD_LD(g, q);
+        const double y0 = xv.x + c * (xv.x - ov.x), y1 = xv.y + c * (xv.y - ov.y);
+        const double n0 = wav_soft(y0 - invL * gv.x, T), n1 = wav_soft(y1 - invL * gv.y, T);
+        AD_ST(xo, q, make_double2(n0, n1));
+        acc[0] += fabs(n0) + fabs(n1);
+        acc[1] += n0 * n0 + n1 * n1;
+        const double d0 = n0 - xv.x, d1 = n1 - xv.y;
+        acc[2] += d0 * d0 + d1 * d1;
+        if constexpr (TRU) {
+            const double2 t = AD_LD(tru, q);
+            const double m0 = n0 - t.x, m1 = n1 - t.y;
+            acc[3] += m0 * m0 + m1 * m1;
+        }
+    }
+    ad_store_partials<NQ>(acc, partials);
+}
+
 inline int ad_blocks(size_t P) {
     size_t nb = (P / 2 + AB - 1) / AB;
     if (nb > 1024) nb = 1024;
@@ -1222,6 +1260,128 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// FISTA on the same problem (SALSA/my_fista_l1.m:5-68): min over x  0.5 ||b - B W x||^2 + tau ||x||_1.  The reference's
+// iteration k = 2..maxiters is (:34-47)
+//     y = y - (1/L) W'B'(B W y - b) ; x = soft(y, tau/L) ; t = 0.5 (1 + sqrt(1 + 4 t_old^2)) ; y = x + ((t_old-1)/t)(x - x_old)
+//     objective(k) = 0.5 ||B W x - b||^2 + tau sum|x|
+// What runs keeps x_{k-1}, x_{k-2} and their images zx = W x in two buffers each and never stores y: with c the momentum
+// factor of the iteration before (0 for k = 2; t and c depend on no data, the host knows them when it enqueues)
+//     zy = zx_{k-1} + c (zx_{k-1} - zx_{k-2})              (= W y by linearity; fl1_momentum_kernel)
+//     g  = W' B'(B zy - b)                                  (op_gradf, wav_analysis)
+//     x_k = soft((x_{k-1} + c (x_{k-1} - x_{k-2})) - (1/L) g, tau/L)   over x_{k-2}, with its sums (fl1_step_kernel)
+//     zx_k = W x_k over zx_{k-2} ; ||B zx_k - b||^2         (wav_synthesis, op_resid)
+// one synthesis per iteration where the reference has two (W y inside A(y), W x for the objective).  The host books the
+// traces and the stop rule one iteration late (lag 1); iteration k + 1 writes the buffers of x_{k-1}, so x_k and zx_k are
+// intact when the rule of iteration k is seen.
+int fista_l1_one(sbtv_ctx *ctx, const double *bd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
+                 double L, int stopcriterion, double tolerance, int maxiters, int lag, const double *td, const double *xwi,
+                 double *xw_out_dev, double *x_out_dev, double *objective, double *times, double *mses, int *n_iter) {
+    BlurOp c;
+    SBTV_TRY(admm_common(ctx, M, N, taps, taille, bd, &c));
+    const size_t P = c.P, C = P * wp.bands();
+    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
+    double *xb[2], *zb[2], *zy, *gi, *g, *partials, *sums, *acc;
+    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &xb[0]));
+    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &xb[1]));
+    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &g));
+    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &zb[0]));
+    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &zb[1]));
+    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &zy));
+    SBTV_TRY(ws_get_t(ctx, "admm.g", P, &gi));
+    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..3] step sums, nb each
+    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0] |x|, [1] x^2, [2] (x-xprev)^2, [3] (x-true)^2, [8] resid2
+    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, nullptr, nullptr, n_iter));
+    const double T = tau / L, invL = 1.0 / L;                            // :38-39
+    const int nq = td ? 4 : 3;
+    ctx->calls += 2;                                                     // AT(b) (:20), A(x) (:28)
+    // iterate 1, the start (:20-22; x = y = xw_init): in the buffers of parity 1, and as "x_0" in those of parity 0, where
+    // c = 0 multiplies a zero difference
+    if (xwi) {
+        SBTV_HIP(ctx, hipMemcpyAsync(xb[1], xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
+        SBTV_HIP(ctx, hipMemcpyAsync(xb[0], xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        SBTV_HIP(ctx, hipMemsetAsync(xb[1], 0, sizeof(double) * C, ctx->stream));
+        SBTV_HIP(ctx, hipMemsetAsync(xb[0], 0, sizeof(double) * C, ctx->stream));
+    }
+    double obj_prev;
+    {
+        SBTV_TRY(wav_synthesis(ctx, wp, xb[1], zb[1], 1));               // :27-29
+        SBTV_HIP(ctx, hipMemcpyAsync(zb[0], zb[1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+        SBTV_TRY(op_resid(ctx, c, zb[1], acc));
+        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
+        hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[1], td, partials, C);
+        RedJobs jb;
+        jb.add(partials, 2, nb, sums);
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        SBTV_HIP(ctx, hipGetLastError());
+        const double *hs;
+        SBTV_TRY(run.fetch(sums, 16, &hs));
+        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
+        if (objective) objective[0] = obj_prev;
+        if (times) times[0] = 0.0;
+        if (mses && td) mses[0] = hs[1] / (double)C;                     // :29
+    }
+    SBTV_TRY(run.start());
+    double t_enq = 1.0, c_enq = 0.0;                                     // t and the momentum factor as the next enqueue sees them
+    auto enqueue = [&](int k) -> int {                                   // :34
+        const int o = k & 1, p = o ^ 1;
+        const double cm = c_enq;
+        hipLaunchKernelGGL(fl1_momentum_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)zb[p],
+                           (const double *)zb[o], cm, zy, P);
+        SBTV_TRY(op_gradf(ctx, c, zy, acc, gi));                         // :38; its residual sum (of the momentum point) is not used
+        SBTV_TRY(wav_analysis(ctx, wp, gi, g, 1));
+        if (td)
+            hipLaunchKernelGGL(fl1_step_kernel<true>, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[p], xb[o],
+                               (const double *)g, td, cm, invL, T, partials, C);
+        else
+            hipLaunchKernelGGL(fl1_step_kernel<false>, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[p], xb[o],
+                               (const double *)g, td, cm, invL, T, partials, C);
+        SBTV_TRY(wav_synthesis(ctx, wp, xb[o], zb[o], 1));               // :43
+        SBTV_TRY(op_resid(ctx, c, zb[o], acc));                          // :44
+        RedJobs jb;
+        jb.add(partials, nq, nb, sums);
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        const double t_old = t_enq;
+        t_enq = 0.5 * (1 + sqrt(1 + 4 * t_old * t_old));                 // :41
+        c_enq = (t_old - 1) / t_enq;                                     // :42
+        return run.publish(k, sums, 12, 0);
+    };
+    bool stop = false;
+    // host side of iteration k: traces and the stop rule (:44-66)
+    auto process = [&](int k) -> int {
+        const double *hsl;
+        SBTV_TRY(run.wait(k, &hsl));
+        ctx->calls += 3;                                                 // A(y), AT, A(x)
+        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :44
+        if (objective) objective[k - 1] = f;
+        if (mses && td) mses[k - 1] = hsl[3] / (double)C;                // :45
+        if (times) times[k - 1] = run.seconds();
+        double crit;
+        if (stopcriterion == 1)
+            crit = fabs(f - obj_prev) / f;                               // :51
+        else if (stopcriterion == 2)
+            crit = sqrt(hsl[2]) / sqrt(hsl[1]);                          // :53 (0 / 0 = NaN at x = 0: never below the tolerance)
+        else
+            crit = f;                                                    // :55
+        obj_prev = f;
+        stop = crit < tolerance;                                         // :64
+        return 0;
+    };
+    int last = 1;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiters, lag, false, enqueue, process, [&] { return !stop; }));
+    SBTV_TRY(run.finish(P, last, nullptr, nullptr));
+    SBTV_HIP(ctx, hipMemcpyAsync(xw_out_dev, xb[last & 1], sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
+    if (x_out_dev)
+        SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, zb[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // item b of a batch as its solver sees it (device pointers)
 struct AdmmItem {
     const double *y, *mask, *tru, *x_init;
@@ -1379,6 +1539,45 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
         SBTV_TRY(wavelet_one(ctx, yd + b * P, M, N, taps + b * taille * taille, taille, wp, tau[b], mu[b], opts, off(td, b * C),
                              off(xi, b * C), xwo + b * C, off(xo, b * P), off(objective, b * (mi + 1)), off(distance, b * mi),
                              off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
+    SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
+    if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return canary_epilogue(ctx, 0);
+}
+
+int sbtv_fista_l1(sbtv_ctx *ctx, const double *b, int M, int N, int batch, const double *taps, int taille, const double *h,
+                  int hlen, int levels, const double *tau, double L, int stopcriterion, double tolerance, int maxiters,
+                  const double *true_xw, const double *xw_init, double *xw_out, double *x_out, double *objective,
+                  double *times, double *mses, int *n_iter, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    if (!b || !taps || !h || !tau || !xw_out || batch < 1)
+        return fail(ctx, SBTV_ERR_BADARG, "fista_l1: missing required argument (b, taps, h, tau, xw_out; batch >= 1)");
+    if (stopcriterion < 1 || stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Invalid stopping criterion!");   // :57
+    if (maxiters < 1) return fail(ctx, SBTV_ERR_MAXITER, "fista_l1: maxiters must be positive");
+    if (!std::isfinite(L) || !(L > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: L must be finite and > 0");
+    if (std::isnan(tolerance)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: tolerance is NaN");
+    for (int i = 0; i < batch; ++i)
+        if (!std::isfinite(tau[i]) || !(tau[i] >= 0.0)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: tau must be finite and >= 0");
+    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
+    WavPlan wp;
+    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
+    SBTV_TRY(check_even_pixels(ctx, M, N));
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
+    const size_t P = (size_t)M * N, C = P * wp.bands(), cnt = P * batch, ccnt = C * batch;
+    const double *bd = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "admm.in.y", b, cnt, flags, &bd));
+    SBTV_TRY(stage_in(ctx, "wav.in.true", true_xw, ccnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "wav.in.xinit", xw_init, ccnt, flags, &xi));
+    double *xwo = nullptr, *xo = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "wav.out.xw", xw_out, ccnt, flags, &xwo));
+    if (x_out) SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
+    const size_t mi = (size_t)maxiters;
+    const int lag = (flags & SBTV_FISTA_L1_NOLAG) ? 0 : 1;
+    for (size_t i = 0; i < (size_t)batch; ++i)
+        SBTV_TRY(fista_l1_one(ctx, bd + i * P, M, N, taps + i * taille * taille, taille, wp, tau[i], L, stopcriterion, tolerance,
+                              maxiters, lag, off(td, i * C), off(xi, i * C), xwo + i * C, off(xo, i * P), off(objective, i * mi),
+                              off(times, i * mi), off(mses, i * mi), off(n_iter, i)));
     SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
     if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));

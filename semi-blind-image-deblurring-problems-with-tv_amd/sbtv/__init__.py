@@ -14,13 +14,13 @@ from .admm import csalsa, CSALSA_v2, CoRAL, CoRAL_v2, SALSA_masked, valid_mask, 
 from .wavelet import mrdwt_TI2D, mirdwt_TI2D, soft, daubcqf, SALSA_wavelet, SAPG_wavelet, myula_wavelet, SAPG_wavelet_semiblind, skrock_wavelet, skrock_coefficients, skrock_max_step
 from .diagnostics import ssim, save_results, load_results, plot_traces, save_image
 from .metrics import PSNR, MSE
-from .fista import my_fista, my_deblur_fista, Psi_TV
+from .fista import my_fista, my_deblur_fista, my_fista_l1, Psi_TV
 from .sapg import (SAPG_algorithm_Guassian, SAPG_algorithm_moffat, SAPG_algorithm_laplace, max_eigenval,
                    demo_setup, myula, myula_moments, combine_moments, skrock, SAPG_skrock,
                    SAPG_masked, myula_masked)
 
 __all__ = [
-    "my_fista", "my_deblur_fista", "Psi_TV", "SAPG_algorithm_Guassian", "SAPG_algorithm_moffat",
+    "my_fista", "my_deblur_fista", "my_fista_l1", "Psi_TV", "SAPG_algorithm_Guassian", "SAPG_algorithm_moffat",
     "SAPG_algorithm_laplace", "max_eigenval", "demo_setup", "myula", "myula_moments", "combine_moments", "skrock", "SAPG_skrock",
     "SAPG_masked", "myula_masked",
     "Context", "Group", "SbtvError", "switches", "default_context", "load_library", "to_device", "to_host", "LIB_PATH",

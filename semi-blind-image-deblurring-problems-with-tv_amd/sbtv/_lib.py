@@ -119,6 +119,7 @@ ALLREDUCE_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_voi
 REDUCE_DEVICE = 2        # include/sbtv.h SBTV_REDUCE_DEVICE
 SAPG_HOST_LOOP = 4       # include/sbtv.h SBTV_SAPG_HOST_LOOP
 FISTA_EXACT_PROX = 2     # include/sbtv.h SBTV_FISTA_EXACT_PROX
+FISTA_L1_NOLAG = 2       # include/sbtv.h SBTV_FISTA_L1_NOLAG
 
 _P = C.c_void_p
 _D = C.c_double
@@ -165,6 +166,7 @@ SIGNATURES = {
     "sbtv_SAPG_wavelet_semiblind": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_sb_opts), _P, _P, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_fista_tv": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _I]),
+    "sbtv_fista_l1": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _D, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_algorithm": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, ALLREDUCE_FN, _P, _I]),
     "sbtv_SAPG_algorithm_moments": (_I, [_P, _P, _I, _I, _I, C.POINTER(sbtv_sapg_opts), _P, _P, _P, _P, _P, _P, _P, _P,

@@ -1,4 +1,4 @@
-"""Host mirror of SALSA/my_fista.m and SALSA/my_deblur_fista.m over the device-resident loop."""
+"""Host mirror of SALSA/my_fista.m, SALSA/my_deblur_fista.m and SALSA/my_fista_l1.m over the device-resident loops."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,6 +8,8 @@ import numpy as np
 from . import _lib as L
 from .operators import BlurOperator, _Adjoint
 from .tv import TVnorm
+
+_lib = L      # my_fista_l1 names its step constant L, as the reference does
 
 
 class Psi_TV:
@@ -86,3 +88,64 @@ def my_deblur_fista(b, h, tau, Phi_TV, Psi_TV_, stopcriterion, tolerance, maxite
     A = BlurOperator(h[:t, :t], ctx=ctx)
     return my_fista(b, A, A.T, tau, 1.0, Phi_TV, Psi_TV_, stopcriterion, tolerance, maxiters, true, verbose, ctx=ctx,
                     _zero_start=True)
+
+
+def my_fista_l1(b, h, tau, wavelet, levels, stopcriterion, tolerance, maxiters, true, verbose=0, L=1.0, xw_init=None,
+                lag=True, return_xw=False, ctx=None):
+    """[Wx, objective, times, mses] = my_fista_l1(b,h,tau,W,WT,stopcriterion,tolerance,maxiters,true,verbose)
+    (SALSA/my_fista_l1.m:5-68): FISTA on min 0.5 ||b - B W x||^2 + tau ||x||_1 over the coefficients x of the redundant
+    wavelet frame; the iteration is stated in include/sbtv.h (sbtv_fista_l1).
+    h: the FULL-SIZE kernel (H_FFT = fft2(h)) with its support in the top-left 15 x 15 corner, as for my_deblur_fista, or a
+    sbtv.BlurOperator.  The reference's handles W / WT are the frame itself here: `wavelet` is its orthonormal scaling filter
+    (sbtv.daubcqf(K)), `levels` its depth.  true: the true COEFFICIENTS (e.g. mrdwt_TI2D(x_true)), or None (no mses).
+    Extensions: L (the reference fixes 1), xw_init (start coefficients, x = y = xw_init; default the reference's zeros),
+    lag=False (SBTV_FISTA_L1_NOLAG: the host waits for every iteration; same result), return_xw=True appends the
+    coefficients of the stopping iteration.  b may be a batch (B, M, N) or a device tensor, as for SALSA_wavelet."""
+    from .wavelet import _bands, _filter, _resized
+    ctx = ctx or _lib.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("my_fista_l1 has no sharded variant")
+    if isinstance(h, BlurOperator):
+        A = h
+    else:
+        hk = np.asarray(h, dtype=np.float64)
+        nz = np.argwhere(hk != 0)
+        t = int(nz[:, -2:].max()) + 1 if nz.size else 1
+        if t > 15:
+            raise _lib.SbtvError(-10, "my_fista_l1: kernel support larger than 15 x 15 is not supported")
+        A = BlurOperator(hk[..., :t, :t], ctx=ctx)
+    bi = _lib.Images(b)
+    B, M, N = bi.B, bi.M, bi.N
+    levels = int(levels)
+    nb = max(_bands(levels), 1)
+    ha, hp, K = _filter(wavelet)
+    ti = _lib.Images(true) if true is not None else None
+    xi = _lib.Images(xw_init) if xw_init is not None else None
+    for other in (ti, xi):
+        if other is not None:
+            if (other.B, other.M, other.N) != (B, M, nb * N):
+                raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+            if other.flags != bi.flags:
+                raise ValueError("all image arguments must live in the same memory space")
+    Kmax = max(int(maxiters), 1)
+    xwo = _resized(bi, nb * N)
+    xo = _lib.empty_like_images(bi)
+    objective, times, mses = np.zeros((B, Kmax)), np.zeros((B, Kmax)), np.zeros((B, Kmax))
+    nit = (C.c_int * B)()
+    taps = A._cm(B)
+    tau_a, tau_p = _lib.dvec(tau, B)
+    vp = _lib.vptr
+    ctx.check(ctx.lib.sbtv_fista_l1(ctx.h, bi.ptr, M, N, B, vp(taps), A.taille, hp, K, levels, tau_p, float(L),
+                                    int(stopcriterion), float(tolerance), int(maxiters), ti.ptr if ti else None,
+                                    xi.ptr if xi else None, xwo.ptr, xo.ptr, vp(objective), vp(times),
+                                    vp(mses) if ti else None, nit, bi.flags | (0 if lag else _lib.FISTA_L1_NOLAG)), bi.flags)
+    sq = (b.dim() == 2) if bi.torch else bi.squeeze
+    Wx, xw = _lib.images_result(xo, sq), _lib.images_result(xwo, sq)
+    n = np.array(nit[:])
+    if sq or B == 1:
+        k = int(n[0])
+        out = (Wx, objective[0, :k].copy(), times[0, :k].copy(), mses[0, :k].copy() if ti else np.array([]))
+    else:
+        out = (Wx, [objective[i, :n[i]].copy() for i in range(B)], [times[i, :n[i]].copy() for i in range(B)],
+               [mses[i, :n[i]].copy() for i in range(B)] if ti else [])
+    return out + (xw,) if return_xw else out
