@@ -159,26 +159,7 @@ __global__ __launch_bounds__(256) void sapg_update_kernel(SapgDev u, int phase) 
         for (int sset = 0; sset < u.nspec; ++sset) {
             const SapgChain c = u.chain[sset];
             const double pv[3] = {c.p0, u.kind == 2 ? 0.0 : c.p1, u.kind == 0 ? u.phi : 0.0};
-            if (tid < t2) psf_taps_point(u.kind, u.taille, pv, tid, &sf[tid], &se0[tid], &se1[tid]);
-            __syncthreads();
-            if (tid == 0) {
-                double a = 0, a0 = 0, a1 = 0;     // MATLAB sum(k(:)): column-major order
-                for (int q = 0; q < t2; ++q) {
-                    a += sf[q];
-                    a0 += se0[q];
-                    a1 += se1[q];
-                }
-                ssum[0] = a;
-                ssum[1] = a0;
-                ssum[2] = a1;
-            }
-            __syncthreads();
-            if (tid < t2) {
-                const double a = ssum[0];
-                u.par[(size_t)sset * t2 + tid] = sf[tid] / a;
-                u.par[(size_t)t2 * u.nspec + (size_t)sset * t2 + tid] = (se0[tid] * a - sf[tid] * ssum[1]) / (a * a);
-                u.par[(size_t)2 * t2 * u.nspec + (size_t)sset * t2 + tid] = (se1[tid] * a - sf[tid] * ssum[2]) / (a * a);
-            }
+            psf_taps_block(u.kind, u.taille, pv, u.par, sset, u.nspec, sf, se0, se1, ssum);
             __syncthreads();
         }
     }
@@ -196,18 +177,6 @@ using namespace sbtv;
 // a-6: plain MYULA chain at fixed parameters (SALSA/myula.m:1-22)
 // ---------------------------------------------------------------------------
 namespace sbtv {
-// sbtv_moments_opts -> MomReq: checks first / thin (first = 0 -> first0) against the last iteration `last`
-static int mom_resolve(sbtv_ctx *ctx, const char *who, const sbtv_moments_opts *mo, int first0, int last, double *post_mean,
-                       double *post_var, long long *post_count, int flags, MomReq *out) {
-    if (!mo || !post_mean) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": moments options and post_mean are required");
-    const int first = mo->first == 0 ? first0 : mo->first;
-    if (mo->thin < 1 || first < 1 || first > last)
-        return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": need thin >= 1 and 1 <= first <= the last iteration");
-    *out = MomReq{first, mo->thin, mo->pooled ? 1 : 0, post_mean, post_var, post_count, (flags & SBTV_DEVICE_PTRS) != 0,
-                  false};
-    return 0;
-}
-
 static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
                       double lambda, double gamma, const double *theta, const double *sigma2, int samples, int chambolleit,
                       unsigned long long seed, int chain_offset, const double *noise, double *x_out, int flags,
@@ -255,22 +224,10 @@ static int myula_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, c
     if (mom_sample_of(mom, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));            // iteration 1 = y
     SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, nullptr));
     const ProxArm arm{pp.ctrl, lam_d, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, nullptr};
-    for (int ii = 2; ii <= samples - 1; ++ii) {             // :13
-        const size_t step = (size_t)(ii - 2);
-        SBTV_TRY(prox_iterate(ctx, pp, X, chambolleit, prox, true));                         // :15
-        SBTV_TRY(op_gradf(ctx, bop, X, acc, grad));         // gradF = AT(A x - y) / sigma2   (run_deblur_tv.m:131)
-        const double *zd = nullptr;
-        if (noise_host) {
-            SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * cnt, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
-            zd = Z;
-        } else if (noise) {
-            zd = noise + step * cnt;
-        }
-        const RngArgs r{seed, (unsigned)step, (unsigned)chain_offset, nullptr};
-        const MomArgs ma{pm_mean, pm_m2, mom_sample_of(mom, ii), nullptr, 1, 1};
-        SBTV_TRY(myula_plain_step(ctx, X, prox, grad, zd, sig_d, gamma, lambda, P, batch, &r, &arm,
-                                  ma.k > 0 ? &ma : nullptr));                                       // :16
-    }
+    // the loop (:13-16) never waits for the host; gradF = AT(A x - y) / sigma2   (run_deblur_tv.m:131)
+    const MyulaLoop loop{X, prox, grad, sig_d, &pp, arm, NoiseFeed{ctx, noise, Z, cnt}, gamma, lambda, P, batch, samples,
+                         chambolleit, seed, chain_offset, mom, pm_mean, pm_m2, 0};
+    SBTV_TRY(myula_plain_loop(ctx, loop, [&] { return op_gradf(ctx, bop, X, acc, grad); }));
     if (mom) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(*mom, samples > 2 ? samples - 1 : 1), *mom));
     SBTV_TRY(stage_out_copy(ctx, x_out, X, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -293,27 +250,12 @@ int sbtv_myula_moments(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
                        const sbtv_moments_opts *mo, double *post_mean, double *post_var, long long *post_count, int flags) {
     if (!ctx) return SBTV_ERR_BADARG;
     MomReq mr;
-    SBTV_TRY(mom_resolve(ctx, "myula_moments", mo, 1, samples > 2 ? samples - 1 : 1, post_mean, post_var, post_count, flags,
-                         &mr));
-    if (mr.pooled && batch > 1) {
-        // pooling needs chains of ONE posterior: the same y, taps, theta and sigma2 in every chain
-        const size_t P = (size_t)M * N, t2 = (size_t)taille * taille;
-        bool same = y && taps && theta && sigma2 && M > 0 && N > 0 && taille > 0;
-        for (int b = 1; same && b < batch; ++b)
-            same = theta[b] == theta[0] && sigma2[b] == sigma2[0] && !memcmp(taps, taps + b * t2, sizeof(double) * t2);
-        if (same) {
-            std::vector<double> yh;
-            const double *yv = y;
-            if (flags & SBTV_DEVICE_PTRS) {
-                SBTV_HIP(ctx, hipSetDevice(ctx->device));
-                yh.resize(P * batch);
-                SBTV_HIP(ctx, hipMemcpy(yh.data(), y, sizeof(double) * P * batch, hipMemcpyDeviceToHost));
-                yv = yh.data();
-            }
-            for (int b = 1; same && b < batch; ++b) same = !memcmp(yv, yv + b * P, sizeof(double) * P);
-        }
-        if (!same) return fail(ctx, SBTV_ERR_BADARG, "myula_moments: pooled = 1 needs chains with the same y, taps, theta and sigma2");
-    }
+    const bool dev = (flags & SBTV_DEVICE_PTRS) != 0;
+    SBTV_TRY(mom_resolve(ctx, "myula_moments", mo, 1, samples > 2 ? samples - 1 : 1, post_mean, post_var, post_count, dev, &mr,
+                         nullptr));
+    if (mr.pooled && batch > 1)
+        SBTV_TRY(check_one_posterior(ctx, "myula_moments", y, M > 0 && N > 0 ? (size_t)M * N : 0, taps, taille, theta, sigma2,
+                                     batch, dev));
     return myula_impl(ctx, y, M, N, batch, taps, taille, lambda, gamma, theta, sigma2, samples, chambolleit, seed,
                       chain_offset, noise, x_out, flags, &mr);
 }
@@ -337,8 +279,8 @@ int sbtv_SAPG_algorithm_moments(sbtv_ctx *ctx, const double *y, int M, int N, in
     if (!ctx) return SBTV_ERR_BADARG;
     if (!op) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm_moments: bad arguments");
     MomReq mr;
-    SBTV_TRY(mom_resolve(ctx, "SAPG_algorithm_moments", mo, op->burnIn, op->samples, post_mean, post_var, post_count, flags,
-                         &mr));
+    SBTV_TRY(mom_resolve(ctx, "SAPG_algorithm_moments", mo, op->burnIn, op->samples, post_mean, post_var, post_count,
+                         (flags & SBTV_DEVICE_PTRS) != 0, &mr, nullptr));
     if (mr.pooled && !op->share_gradients && batch > 1)
         return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm_moments: pooled = 1 needs chains of one posterior (share_gradients = 1)");
     return sapg_impl(ctx, y, M, N, batch, op, x0, noise, thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb, x_last,
@@ -395,11 +337,7 @@ struct SapgRun {
     bool in_stream() const { return u.shared && reduce_dev; }
 
     // spectra of the taps and of their parameter derivatives, ONE launch for the two or three sets
-    int spectra() {
-        const double *tp[3] = {par, par + t2 * u.nspec, par + 2 * t2 * u.nspec};
-        double2 *up[3] = {Hs, D1s, D2s};
-        return psf_spectrum_sets(ctx, fps, tp, u.taille, up, u.npar > 1 ? 3 : 2);
-    }
+    int spectra() { return sapg_spectra(ctx, fps, u, par, Hs, D1s, D2s); }
     // taps / derivative taps of the chains' current PSF parameters, every spectrum set, into the pinned block
     int stage_taps() {
         for (int s = 0; s < u.nspec; ++s) {
@@ -579,16 +517,15 @@ struct SapgRun {
     }
 
     int setup() {
-        u.taille = op->psf_size;
-        u.npar = (op->kind == SBTV_PSF_LAPLACE) ? 1 : 2;
-        u.shared = op->share_gradients ? 1 : 0;
-        u.nspec = u.shared ? 1 : batch;              // spectra sets (H, D1, D2, Y)
+        // ---- the constants of the parameter step; one set of spectra (H, D1, D2, Y) for shared-gradient chains
+        sapg_fill_const(&u, op, M, N, batch, op->share_gradients != 0, 1.0 / ((double)M * N));
+        params_move = u.params_move != 0;
         SBTV_TRY(fft_plan(ctx, M, N, batch, &fp));
         SBTV_TRY(fft_plan(ctx, M, N, u.nspec, &fps));
         SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
         P = (size_t)M * N;
         cnt = P * batch;
-        const int nspec = u.nspec, warmup = op->warmup;
+        const int nspec = u.nspec;
 
         // ---- buffers
         const double *yd = nullptr, *x0d = nullptr;
@@ -634,16 +571,6 @@ struct SapgRun {
         inv_scale = 1.0 / ((double)fp.n1 * N);
         gam = op->gamma;
 
-        // ---- the constants of the parameter step
-        params_move = !(op->fix_p[0] && (u.npar < 2 || op->fix_p[1]));
-        u.kind = op->kind; u.batch = batch; u.samples = op->samples; u.warmup = warmup > 0 ? warmup : 1; u.burnIn = op->burnIn;
-        u.params_move = params_move ? 1 : 0; u.fix_p0 = op->fix_p[0]; u.fix_p1 = op->fix_p[1]; u.fix_sigma = op->fix_sigma;
-        u.dimX = (double)P; u.parseval = 1.0 / ((double)M * N); u.lamb = op->lambda; u.c_theta = op->c_theta; u.c_p0 = op->c_p[0];
-        u.c_p1 = op->c_p[1]; u.c_sigma = op->c_sigma; u.min_th = op->min_th; u.max_th = op->max_th; u.p_min0 = op->p_min[0];
-        u.p_max0 = op->p_max[0]; u.p_min1 = op->p_min[1]; u.p_max1 = op->p_max[1]; u.p_true0 = op->p_true[0]; u.p_true1 = op->p_true[1];
-        u.s_lo = fmin(op->sigma2_min, op->sigma2_max); u.s_hi = fmax(op->sigma2_min, op->sigma2_max);
-        u.sigma2_init = op->sigma2_init; u.phi = op->phi; u.step_base = (double)(warmup > 0 ? warmup - 1 : 0);
-
         // ---- where the parameter updates run.  Default: on the device (sapg_update_kernel), the host only enqueues.
         // A host reduce_fn needs the gradients on the host every iteration, which selects the host-side loop.
         static const bool env_host_loop = [] {
@@ -660,9 +587,7 @@ struct SapgRun {
         }
 
         // ---- chain state, traces
-        chain.assign(batch, SapgChain{op->th_init, op->p_init[0], u.npar > 1 ? op->p_init[1] : 0.0, op->sigma2_init, 0.0, 0.0, 0.0, 0.0});
-        if (op->burnIn == 1)
-            for (SapgChain &c : chain) { c.sum_th = c.theta; c.sum_s = c.sig2; c.sum_p0 = c.p0; c.sum_p1 = c.p1; }
+        chain.assign(batch, sapg_chain_start(u, op));
         tr.assign(sapg_traces_len(u), 0.0);
         logpi0.assign(batch, 0.0);
         last_p0.assign(nspec, NAN);
@@ -722,7 +647,7 @@ struct SapgRun {
     // the traces and chains (on the host, or on their way there), EB means (:258-284), last sample, posterior moments ->
     // the caller's arrays
     int finish() {
-        const int samples = u.samples, warmup = op->warmup;
+        const int samples = u.samples;
         if (x_last) {
             if (flags & SBTV_DEVICE_PTRS)
                 SBTV_HIP(ctx, hipMemcpyAsync(x_last, X, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
@@ -731,28 +656,7 @@ struct SapgRun {
         }
         if (mom) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(*mom, samples), *mom));
         SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const SapgTraces h = sapg_traces(tr.data(), u);
-        for (int b = 0; b < batch; ++b) {
-            const size_t o = (size_t)b * samples;
-            if (thetas) { memcpy(thetas + o, h.theta + o, sizeof(double) * samples); thetas[o] = op->th_init; }
-            if (sigmas) { memcpy(sigmas + o, h.sigma + o, sizeof(double) * samples); sigmas[o] = op->sigma2_init; }
-            if (logpi) { memcpy(logpi + o, h.logpi + o, sizeof(double) * samples); logpi[o] = logpi0[b]; }
-            if (gx) memcpy(gx + o, h.gx + o, sizeof(double) * samples);
-            if (ps) {
-                memcpy(ps + 2 * o, h.p + 2 * o, sizeof(double) * 2 * samples);
-                ps[2 * o] = op->p_init[0];
-                ps[2 * o + samples] = u.npar > 1 ? op->p_init[1] : 0.0;
-            }
-            if (grads) memcpy(grads + 4 * o, h.grads + 4 * o, sizeof(double) * 4 * samples);
-            if (logpi_wu && warmup > 0) memcpy(logpi_wu + (size_t)b * warmup, h.wu + (size_t)b * warmup, sizeof(double) * warmup);
-            if (eb) {
-                const double cntm = (double)(samples - op->burnIn + 1);
-                eb[(size_t)b * 4 + 0] = chain[b].sum_th / cntm;
-                eb[(size_t)b * 4 + 1] = chain[b].sum_p0 / cntm;
-                eb[(size_t)b * 4 + 2] = chain[b].sum_p1 / cntm;
-                eb[(size_t)b * 4 + 3] = chain[b].sum_s / cntm;
-            }
-        }
+        sapg_copy_out(u, op, tr.data(), chain.data(), logpi0.data(), SapgOut{thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb});
         return canary_epilogue(ctx, 0);
     }
 
@@ -947,18 +851,9 @@ int sapg_impl(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const sbt
               double *grads, double *eb, double *x_last, sbtv_allreduce_fn reduce_fn, void *reduce_user, int flags,
               const MomReq *mom) {
     if (!ctx) return SBTV_ERR_BADARG;
-    if (!y || !op || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: bad arguments");
-    if (op->kind < 0 || op->kind > 2) return fail(ctx, SBTV_ERR_PSF, "SAPG_algorithm: unknown PSF kind");
-    const int taille = op->psf_size;
-    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
-    if (op->samples < 2 || op->warmup < 0 || op->burnIn < 1 || op->burnIn > op->samples)
-        return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: need samples >= 2, 1 <= burnIn <= samples");
-    if (op->chambolleit <= 0) return fail(ctx, SBTV_ERR_MAXITER, "SAPG_algorithm: chambolleit must be positive");
-    if (op->chain_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: chain_offset must be >= 0");
-    if (op->iter_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_algorithm: iter_offset must be >= 0");
+    SBTV_TRY(sapg_refuse(ctx, "SAPG_algorithm", y, M, N, batch, op));
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
     const int shared = op->share_gradients ? 1 : 0;
-    SBTV_TRY(check_even_pixels(ctx, M, N));
     // independent chains (SAPG_algorithm_moffat.m:143-173: every chain has its own state) -> two lanes of this context;
     // shared-gradient chains only in lanes_mode 2 (their per-iteration exchange couples the two streams).  Not when the
     // caller reduces across processes itself, forces the host loop, or injects device-resident noise (re-packed per lane).

@@ -3,9 +3,11 @@
 //     p(y | x, p, s2) ~ s2^(-n_obs/2) exp(-R / (2 s2)),   R = sum(m .* (B_p x - y).^2)
 // include/sbtv.h states the model.  A mask breaks Parseval, so the middle of the gradient B'(m .* (Bx - y)) and the three
 // parameter sums are spatial: one element-wise kernel forms the masked residual and leaves the partial sums, one kernel per
-// chain totals them and runs the parameter step.  The arithmetic of that step is sapg_step.inc, the transforms are the
-// row / column passes of the blur-operator layer, the prox is prox_iterate and the move is myula_step: all shared with the
-// circular drivers, not copied.
+// chain totals them and runs the parameter step.  The arithmetic of that step is sapg_step.inc and its kernel
+// sapg_chain_update.inc (shared with sapg_skrock.hip: `nobs` puts the observed pixels in place of dimX), the transforms are the
+// row / column passes of the blur-operator layer, the prox is prox_iterate and the move is myula_step; the loop of
+// sbtv_myula_masked is myula_plain_loop, and the refusals, the constants, the start state, the device set-up and the copy-out
+// of sbtv_SAPG_masked are the sapg_* functions of sampler_common.hip: all shared with the circular drivers, not copied.
 //
 // One SAPG iteration on the context's stream: the MYULA move with the gradient and the prox the previous iteration left, the
 // cold Chambolle prox of the new sample, one forward column pass of it (with the TV partials where fft_cols_tv_ok allows),
@@ -32,6 +34,7 @@ namespace sbtv {
 
 namespace {
 
+#include "sapg_chain_update.inc"     // SapgChainDev, sapg_chain_update_kernel
 constexpr int MSB = WAV_EWB;           // lanes per workgroup of the kernels below (wav_block_sum sums four waves)
 constexpr int SAPG_MK_SYNC = 1024;     // iterations between two synchronisations
 
@@ -89,83 +92,6 @@ __global__ __launch_bounds__(MSB) void masked_count_kernel(const double *__restr
         s += m[(size_t)b * P + i] > 0.0 ? 1.0 : 0.0;
     const double t = wav_block_sum(s, red);
     if (threadIdx.x == 0) nobs[(size_t)b * gridDim.x + blockIdx.x] = t;
-}
-
-struct SapgMkDev : SapgConst {
-    const double *acc;         // [batch][3][nrb]: partial sums of the residual kernel, R and the two <dB/dp_q X, r>
-    const double *tvp;         // [batch][ntv]: partial sums of TVnorm(X)
-    int nrb, ntv;
-    const double *nobs;        // [batch]: observed pixels of every chain
-    double *scal;              // [4*batch]: the totals, in the layout sapg_gradients reads (sapg_collect_kernel's)
-    SapgChain *chain;          // [batch]
-    double *par;               // [taps | d0 | d1] of every chain, lam[batch], sigma2[batch]
-    const double *delta;       // [samples + 1]: delta(ii), tabulated by the host (pow)
-    SapgTraces tr;             // device traces
-};
-// what the update kernel does with the sums: logpi_wu(ii) of warm-up iteration ii; logpi(1) of the state the SAPG loop starts
-// from; the parameter step of SAPG iteration ii
-enum { SAPG_MK_WARMUP = 0, SAPG_MK_START = 1, SAPG_MK_MAIN = 2 };
-
-// The update of sapg_skrock_update_kernel on the spatial sums, one workgroup per chain, so that chain b of a batch is computed
-// exactly as alone: the four totals in a fixed order; one lane runs sapg_gradients / sapg_step with the sums taken as they are
-// (parseval = 1) and n_obs in place of dimX in G_sigma; with a free PSF parameter the workgroup builds the taps and both
-// derivative taps of p(ii), summed in MATLAB's column-major order by one lane per set (every mask size: 15 x 15 is 225 lanes).
-__global__ __launch_bounds__(MSB) void sapg_masked_update_kernel(SapgMkDev u, int phase, int ii) {
-    __shared__ double red[4], sf[MSB], se0[MSB], se1[MSB], ssum[3], pnew[2];
-    const int b = blockIdx.x, tid = threadIdx.x, t2 = u.taille * u.taille;
-    double tot[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const double *p = q < 3 ? u.acc + ((size_t)b * 3 + q) * u.nrb : u.tvp + (size_t)b * u.ntv;
-        const int n = q < 3 ? u.nrb : u.ntv;
-        double s = 0.0;
-        for (int i = tid; i < n; i += MSB) s += p[i];
-        tot[q] = wav_block_sum(s, red);
-    }
-    if (tid == 0) {
-        for (int q = 0; q < 3; ++q) u.scal[(size_t)b * 3 + q] = tot[q];
-        u.scal[3 * (size_t)u.batch + b] = tot[3];
-        SapgChain c = u.chain[b];
-        if (phase == SAPG_MK_WARMUP) {
-            u.tr.wu[(size_t)b * u.warmup + (ii - 1)] = sapg_logpi(u, c, u.scal, b);                  // :85
-        } else if (phase == SAPG_MK_START) {
-            u.tr.logpi[(size_t)b * u.samples] = sapg_logpi(u, c, u.scal, b);                         // :131
-        } else {
-            double G[4];
-            sapg_gradients(u, u.tr, c, u.scal, b, ii, G);
-            G[3] = tot[0] / (2 * c.sig2 * c.sig2) - u.nobs[b] / (2 * c.sig2);        // :188 with n_obs observed pixels
-            sapg_step(u, u.tr, c, b, ii, u.delta[ii], G);
-            u.chain[b] = c;
-            double *lam_d = u.par + (size_t)3 * t2 * u.batch, *sig_d = lam_d + u.batch;
-            lam_d[b] = u.lamb * c.theta;         // proxG(x, theta): 'lambda', op.lambda*theta  (run_Gaussian_demo.m:191)
-            sig_d[b] = c.sig2;
-            pnew[0] = c.p0;
-            pnew[1] = c.p1;
-        }
-    }
-    if (phase != SAPG_MK_MAIN || !u.params_move) return;
-    __syncthreads();
-    const double pv[3] = {pnew[0], u.kind == 2 ? 0.0 : pnew[1], u.kind == 0 ? u.phi : 0.0};
-    double f = 0.0, e0 = 0.0, e1 = 0.0;
-    if (tid < t2) psf_taps_point(u.kind, u.taille, pv, tid, &f, &e0, &e1);
-    sf[tid] = f;
-    se0[tid] = e0;
-    se1[tid] = e1;
-    __syncthreads();
-    if (tid < 3) {
-        const double *v = tid == 0 ? sf : (tid == 1 ? se0 : se1);
-        double a = 0.0;                          // MATLAB sum(k(:)): column-major order
-        for (int q = 0; q < t2; ++q) a += v[q];
-        ssum[tid] = a;
-    }
-    __syncthreads();
-    if (tid < t2) {
-        const double a = ssum[0];
-        const size_t set = (size_t)t2 * u.batch, o = (size_t)b * t2 + tid;
-        u.par[o] = f / a;
-        u.par[set + o] = (e0 * a - f * ssum[1]) / (a * a);
-        u.par[2 * set + o] = (e1 * a - f * ssum[2]) / (a * a);
-    }
 }
 
 // with host pointers: every entry finite and >= 0, and a positive one in every chain
@@ -242,41 +168,9 @@ int masked_open(sbtv_ctx *ctx, const char *prefix, const double *y, const double
     return 0;
 }
 
-// the normals of one step as the kernels read them: the staging buffer, the caller's device array, or null (Philox)
-struct NoiseFeed {
-    sbtv_ctx *ctx;
-    const double *noise;
-    double *Z;                 // staging of one step of host noise (null: none needed)
-    size_t cnt;
-    int get(size_t step, const double **zd) const {
-        *zd = nullptr;
-        if (Z) {
-            SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * cnt, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
-            *zd = Z;
-        } else if (noise) {
-            *zd = noise + step * cnt;
-        }
-        return 0;
-    }
-};
-
-// the moments request of both entries: first = 0 means first0; the chains of a call have their own masks (and in SAPG their
-// own parameters), so they are never pooled
-int masked_moments(sbtv_ctx *ctx, const char *who, const sbtv_moments_opts *mo, int first0, int last, int batch,
-                   double *post_mean, double *post_var, long long *post_count, bool dev, MomReq *sel, const MomReq **selp) {
-    *selp = nullptr;
-    if (!mo) {
-        if (post_mean || post_var || post_count)
-            return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": moment outputs without moments options");
-        return 0;
-    }
-    if (!post_mean) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": moments options and post_mean are required");
-    const int first = mo->first == 0 ? first0 : mo->first;
-    if (mo->thin < 1 || first < 1 || first > last)
-        return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": need thin >= 1 and 1 <= first <= the last iteration");
-    if (mo->pooled && batch > 1) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": pooled = 1 needs batch = 1");
-    *sel = MomReq{first, mo->thin, mo->pooled ? 1 : 0, post_mean, post_var, post_count, dev, false};
-    *selp = sel;
+// the chains of a call have their own masks (and in SAPG their own parameters), so their moments are never pooled
+int masked_pooled(sbtv_ctx *ctx, const char *who, const MomReq *selp, int batch) {
+    if (selp && selp->pooled && batch > 1) return fail(ctx, SBTV_ERR_BADARG, std::string(who) + ": pooled = 1 needs batch = 1");
     return 0;
 }
 
@@ -307,7 +201,8 @@ int sbtv_myula_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
     MomReq sel{};
     const MomReq *selp = nullptr;
     const int last = samples > 2 ? samples - 1 : 1;
-    SBTV_TRY(masked_moments(ctx, "myula_masked", mo, 1, last, batch, post_mean, post_var, post_count, dev, &sel, &selp));
+    SBTV_TRY(mom_resolve(ctx, "myula_masked", mo, 1, last, post_mean, post_var, post_count, dev, &sel, &selp));
+    SBTV_TRY(masked_pooled(ctx, "myula_masked", selp, batch));
 
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
     MaskedOp mk;
@@ -341,21 +236,14 @@ int sbtv_myula_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
     if (mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));                // iteration 1 = y
     SBTV_TRY(prox_reset(ctx, pp, lam_d, 1.0, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, false, nullptr));
     const ProxArm arm{pp.ctrl, lam_d, chambolleit, CHAMBOLLE_TOL, CHAMBOLLE_TAU, nullptr};
-    const NoiseFeed nz{ctx, noise, Z, cnt};
-    for (int ii = 2; ii <= samples - 1; ++ii) {             // :13
-        const size_t step = (size_t)(ii - 2);
-        SBTV_TRY(prox_iterate(ctx, pp, X, chambolleit, prox, true));                         // :15
+    // the loop (:13-16): gradF = B'(m .* (B x - y)) / sigma2; one synchronisation per SAPG_MK_SYNC iterations
+    const MyulaLoop loop{X, prox, grad, sig_d, &pp, arm, NoiseFeed{ctx, noise, Z, cnt}, gamma, lambda, P, batch, samples,
+                         chambolleit, seed, chain_offset, selp, pm_mean, pm_m2, SAPG_MK_SYNC};
+    SBTV_TRY(myula_plain_loop(ctx, loop, [&]() -> int {
         SBTV_TRY(fft_cols_fwd(ctx, mk.bop.fp, X, nullptr, mk.bop.S));
         SBTV_TRY(mk.residual(nullptr, nullptr));
-        SBTV_TRY(mk.gradient(grad));                        // gradF = B'(m .* (B x - y)) / sigma2
-        const double *zd = nullptr;
-        SBTV_TRY(nz.get(step, &zd));
-        const RngArgs r{seed, (unsigned)step, (unsigned)chain_offset, nullptr};
-        const MomArgs ma{pm_mean, pm_m2, mom_sample_of(selp, ii), nullptr, 1, 1};
-        SBTV_TRY(myula_plain_step(ctx, X, prox, grad, zd, sig_d, gamma, lambda, P, batch, &r, &arm,
-                                  ma.k > 0 ? &ma : nullptr));                                       // :16
-        if ((ii - 1) % SAPG_MK_SYNC == 0) SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+        return mk.gradient(grad);
+    }));
     if (selp) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(sel, last), sel));
     SBTV_TRY(stage_out_copy(ctx, x_out, X, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -367,58 +255,27 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
                      double *logpi_wu, double *gx, double *grads, double *eb, double *x_last, const sbtv_moments_opts *mo,
                      double *post_mean, double *post_var, long long *post_count, int flags) {
     if (!ctx) return SBTV_ERR_BADARG;
-    // ---- what sbtv_SAPG_algorithm refuses, with its codes
-    if (!y || !op || batch < 1) return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: bad arguments");
-    if (op->kind < 0 || op->kind > 2) return fail(ctx, SBTV_ERR_PSF, "SAPG_masked: unknown PSF kind");
-    const int taille = op->psf_size;
-    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
-    if (op->samples < 2 || op->warmup < 0 || op->burnIn < 1 || op->burnIn > op->samples)
-        return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: need samples >= 2, 1 <= burnIn <= samples");
-    if (op->chambolleit <= 0) return fail(ctx, SBTV_ERR_MAXITER, "SAPG_masked: chambolleit must be positive");
-    if (op->chain_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: chain_offset must be >= 0");
-    if (op->iter_offset < 0) return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: iter_offset must be >= 0");
-    SBTV_TRY(check_even_pixels(ctx, M, N));
+    SBTV_TRY(sapg_refuse(ctx, "SAPG_masked", y, M, N, batch, op));   // what sbtv_SAPG_algorithm refuses, with its codes
     // ---- its own
     if (!mask) return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: the mask is missing");
     if (op->share_gradients) return fail(ctx, SBTV_ERR_BADARG, "SAPG_masked: share_gradients is not offered");
     const bool dev = (flags & SBTV_DEVICE_PTRS) != 0;
-    const size_t P = (size_t)M * N, cnt = P * batch, t2 = (size_t)taille * taille;
+    const size_t P = (size_t)M * N, cnt = P * batch;
     if (!dev) SBTV_TRY(check_mask_host(ctx, "SAPG_masked", mask, P, batch));
     const int samples = op->samples, warmup = op->warmup, chambolleit = op->chambolleit;
     MomReq sel{};
     const MomReq *selp = nullptr;
-    SBTV_TRY(masked_moments(ctx, "SAPG_masked", mo, op->burnIn, samples, batch, post_mean, post_var, post_count, dev, &sel,
-                            &selp));
+    SBTV_TRY(mom_resolve(ctx, "SAPG_masked", mo, op->burnIn, samples, post_mean, post_var, post_count, dev, &sel, &selp));
+    SBTV_TRY(masked_pooled(ctx, "SAPG_masked", selp, batch));
 
-    // ---- the constants of the parameter step (those of sapg.hip; the sums are spatial: no Parseval factor)
-    SapgMkDev u{};
-    u.kind = op->kind; u.taille = taille; u.npar = (op->kind == SBTV_PSF_LAPLACE) ? 1 : 2; u.nspec = batch; u.batch = batch;
-    u.shared = 0; u.samples = samples; u.warmup = warmup > 0 ? warmup : 1; u.burnIn = op->burnIn;
-    const bool params_move = !(op->fix_p[0] && (u.npar < 2 || op->fix_p[1]));
-    u.params_move = params_move ? 1 : 0; u.fix_p0 = op->fix_p[0]; u.fix_p1 = op->fix_p[1]; u.fix_sigma = op->fix_sigma;
-    u.dimX = (double)M * N; u.parseval = 1.0; u.lamb = op->lambda; u.c_theta = op->c_theta; u.c_p0 = op->c_p[0];
-    u.c_p1 = op->c_p[1]; u.c_sigma = op->c_sigma; u.min_th = op->min_th; u.max_th = op->max_th; u.p_min0 = op->p_min[0];
-    u.p_max0 = op->p_max[0]; u.p_min1 = op->p_min[1]; u.p_max1 = op->p_max[1]; u.p_true0 = op->p_true[0]; u.p_true1 = op->p_true[1];
-    u.s_lo = fmin(op->sigma2_min, op->sigma2_max); u.s_hi = fmax(op->sigma2_min, op->sigma2_max);
-    u.sigma2_init = op->sigma2_init; u.phi = op->phi; u.step_base = (double)(warmup > 0 ? warmup - 1 : 0);
-    const size_t npar = 3 * t2 * batch + 2 * (size_t)batch;
-
-    // the chains' start, and the taps and derivative taps of p_init (the host's, as in sbtv_SAPG_algorithm)
-    SapgChain c0{op->th_init, op->p_init[0], u.npar > 1 ? op->p_init[1] : 0.0, op->sigma2_init, 0.0, 0.0, 0.0, 0.0};
-    if (op->burnIn == 1) { c0.sum_th = c0.theta; c0.sum_s = c0.sig2; c0.sum_p0 = c0.p0; c0.sum_p1 = c0.p1; }
-    std::vector<SapgChain> chain(batch, c0);
-    std::vector<double> hp(npar);
-    {
-        const double pv[3] = {c0.p0, op->kind == SBTV_PSF_LAPLACE ? 0.0 : c0.p1, op->kind == SBTV_PSF_GAUSSIAN ? op->phi : 0.0};
-        const int rc = sbtv_psf_taps(op->kind, taille, pv, hp.data(), hp.data() + t2 * batch, hp.data() + 2 * t2 * batch);
-        if (rc != 0) return fail(ctx, rc, "SAPG_masked: PSF parameters out of range");
-        for (int b = 1; b < batch; ++b)
-            for (int s = 0; s < 3; ++s) memcpy(&hp[s * t2 * batch + b * t2], &hp[s * t2 * batch], sizeof(double) * t2);
-        for (int b = 0; b < batch; ++b) {
-            hp[3 * t2 * batch + b] = u.lamb * c0.theta;      // proxG(x, theta): 'lambda', op.lambda*theta  (run_Gaussian_demo.m:191)
-            hp[3 * t2 * batch + batch + b] = c0.sig2;
-        }
-    }
+    // ---- the constants of the parameter step (the sums are spatial: no Parseval factor), the chains' start, the taps and
+    // derivative taps of p_init (the host's)
+    SapgChainDev u{};
+    sapg_fill_const(&u, op, M, N, batch, false, 1.0);
+    const bool params_move = u.params_move != 0;
+    std::vector<SapgChain> chain;
+    std::vector<double> hp, tr;
+    SBTV_TRY(sapg_start(ctx, "SAPG_masked", u, op, &chain, &hp));
 
     // ---- buffers
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
@@ -430,9 +287,8 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
     const bool tv_fused = fft_cols_tv_ok(fp);
     const double *x0d = nullptr;
     SBTV_TRY(stage_in(ctx, "sapgm.grad", x0, cnt, flags, &x0d));             // staged where the gradient goes later
-    double *X = nullptr, *prox = nullptr, *grad = nullptr, *Z = nullptr, *D1x = nullptr, *D2x = nullptr, *par = nullptr,
-           *tvc = nullptr, *scal = nullptr, *delta_d = nullptr, *tr_d = nullptr, *nobs = nullptr, *pm_mean = nullptr,
-           *pm_m2 = nullptr;
+    double *X = nullptr, *prox = nullptr, *grad = nullptr, *Z = nullptr, *D1x = nullptr, *D2x = nullptr, *tvc = nullptr,
+           *nobs = nullptr, *pm_mean = nullptr, *pm_m2 = nullptr;
     double2 *D1s = nullptr, *D2s = nullptr;
     SBTV_TRY(stage_out_buf(ctx, "sapgm.X", x_last, cnt, flags, &X));
     SBTV_TRY(ws_get_t(ctx, "sapgm.prox", cnt, &prox));
@@ -451,34 +307,16 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
         SBTV_TRY(ws_get_t(ctx, "sapgm.pm_mean", cnt, &pm_mean));
         SBTV_TRY(ws_get_t(ctx, "sapgm.pm_m2", cnt, &pm_m2));
     }
-    SBTV_TRY(ws_get_t(ctx, "sapgm.par", npar, &par));
-    SBTV_TRY(ws_get_t(ctx, "sapgm.scal", 4 * (size_t)batch, &scal));
     SBTV_TRY(ws_get_t(ctx, "sapgm.nobs", (size_t)batch * (mk.nblk + 1), &nobs));   // [batch] totals, then the partials
-    SBTV_TRY(ws_get_t(ctx, "sapgm.delta", (size_t)samples + 1, &delta_d));
-    SBTV_TRY(ws_get_t(ctx, "sapgm.chain", (size_t)batch, &u.chain));
-    std::vector<double> tr(sapg_traces_len(u), 0.0);
-    SBTV_TRY(ws_get_t(ctx, "sapgm.traces", tr.size(), &tr_d));
-    double *lam_d = par + 3 * t2 * batch, *sig_d = lam_d + batch;
-    u.acc = mk.acc; u.tvp = tvc; u.nrb = mk.nblk; u.ntv = ntvc; u.nobs = nobs; u.scal = scal; u.par = par; u.delta = delta_d;
-    u.tr = sapg_traces(tr_d, u);
-    {
-        std::vector<double> dl((size_t)samples + 1, 0.0);
-        for (int ii = 2; ii <= samples; ++ii) dl[ii] = sapg_delta(op, u.dimX, ii);
-        SBTV_HIP(ctx, hipMemcpyAsync(par, hp.data(), sizeof(double) * npar, hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipMemcpyAsync(delta_d, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipMemcpyAsync(u.chain, chain.data(), sizeof(SapgChain) * batch, hipMemcpyHostToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipMemsetAsync(tr_d, 0, sizeof(double) * tr.size(), ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));                    // the staging vector goes out of scope
-    }
+    SapgDevBufs d{};
+    SBTV_TRY(sapg_device_setup(ctx, "sapgm", u, op, chain, hp, &d));
+    double *par = d.par, *lam_d = par + 3 * (size_t)u.taille * u.taille * batch, *sig_d = lam_d + batch;
+    u.acc = mk.acc; u.tvp = tvc; u.nrb = mk.nblk; u.ntv = ntvc; u.nobs = nobs;
+    u.scal = d.scal; u.chain = d.chain; u.par = par; u.delta = d.delta; u.traces = d.traces;
     hipLaunchKernelGGL(masked_count_kernel, dim3(mk.nblk, batch), dim3(MSB), 0, ctx->stream, mk.md, nobs + batch, P);
     SBTV_HIP(ctx, hipGetLastError());
     SBTV_TRY(reduce_partials(ctx, nobs + batch, batch, mk.nblk, nobs));
-    // spectra of the taps and of their parameter derivatives in `par`, ONE launch for the two or three sets
-    auto spectra = [&]() -> int {
-        const double *tp[3] = {par, par + t2 * batch, par + 2 * t2 * batch};
-        double2 *up[3] = {mk.bop.Hs, D1s, D2s};
-        return psf_spectrum_sets(ctx, fp, tp, taille, up, u.npar > 1 ? 3 : 2);
-    };
+    auto spectra = [&] { return sapg_spectra(ctx, fp, u, par, mk.bop.Hs, D1s, D2s); };
     SBTV_TRY(spectra());
     // X = x0, or y as given  (SAPG_algorithm_Guassian.m:10-12)
     const double *start = x0d ? x0d : mk.yd;
@@ -501,7 +339,7 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
         return mk.residual(der ? D1x : nullptr, der ? D2x : nullptr);
     };
     auto update = [&](int phase, int ii) -> int {
-        hipLaunchKernelGGL(sapg_masked_update_kernel, dim3(batch), dim3(MSB), 0, ctx->stream, u, phase, ii);
+        hipLaunchKernelGGL(sapg_chain_update_kernel, dim3(batch), dim3(SAPG_CHAIN_WG), 0, ctx->stream, u, phase, ii);
         SBTV_HIP(ctx, hipGetLastError());
         return 0;
     };
@@ -527,16 +365,16 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
     for (int ii = 2; ii <= warmup; ++ii) {
         SBTV_TRY(move(0));
         SBTV_TRY(sums(false));
-        SBTV_TRY(update(SAPG_MK_WARMUP, ii));
+        SBTV_TRY(update(SAPG_CHAIN_WARMUP, ii));
         SBTV_TRY(mk.gradient(grad));
     }
-    SBTV_TRY(update(SAPG_MK_START, 1));                                      // the sums of the state the loop starts from stand
+    SBTV_TRY(update(SAPG_CHAIN_START, 1));                                      // the sums of the state the loop starts from stand
     if (mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));
     // ---- SAPG iterations (:98-248)
     for (int ii = 2; ii <= samples; ++ii) {
         SBTV_TRY(move(mom_sample_of(selp, ii)));
         SBTV_TRY(sums(true));                                                // G_p is booked whether or not p is free
-        SBTV_TRY(update(SAPG_MK_MAIN, ii));
+        SBTV_TRY(update(SAPG_CHAIN_MAIN, ii));
         if (ii == samples) break;
         if (params_move) {                                                   // r at p(ii): new spectra, B X from S (X has not moved)
             SBTV_TRY(spectra());
@@ -547,32 +385,10 @@ int sbtv_SAPG_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M, 
 
     // ---- the traces, the chains, the last sample and the moments -> the caller's arrays
     if (selp) SBTV_TRY(moments_finish(ctx, pm_mean, pm_m2, P, batch, mom_count(sel, samples), sel));
-    SBTV_HIP(ctx, hipMemcpyAsync(tr.data(), tr_d, sizeof(double) * tr.size(), hipMemcpyDeviceToHost, ctx->stream));
-    SBTV_HIP(ctx, hipMemcpyAsync(chain.data(), u.chain, sizeof(SapgChain) * batch, hipMemcpyDeviceToHost, ctx->stream));
+    SBTV_TRY(sapg_download(ctx, u, d, &tr, &chain));
     SBTV_TRY(stage_out_copy(ctx, x_last, X, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const SapgTraces h = sapg_traces(tr.data(), u);
-    for (int b = 0; b < batch; ++b) {
-        const size_t o = (size_t)b * samples;
-        if (thetas) { memcpy(thetas + o, h.theta + o, sizeof(double) * samples); thetas[o] = op->th_init; }
-        if (sigmas) { memcpy(sigmas + o, h.sigma + o, sizeof(double) * samples); sigmas[o] = op->sigma2_init; }
-        if (logpi) memcpy(logpi + o, h.logpi + o, sizeof(double) * samples);
-        if (gx) memcpy(gx + o, h.gx + o, sizeof(double) * samples);
-        if (ps) {
-            memcpy(ps + 2 * o, h.p + 2 * o, sizeof(double) * 2 * samples);
-            ps[2 * o] = op->p_init[0];
-            ps[2 * o + samples] = u.npar > 1 ? op->p_init[1] : 0.0;
-        }
-        if (grads) memcpy(grads + 4 * o, h.grads + 4 * o, sizeof(double) * 4 * samples);
-        if (logpi_wu && warmup > 0) memcpy(logpi_wu + (size_t)b * warmup, h.wu + (size_t)b * warmup, sizeof(double) * warmup);
-        if (eb) {
-            const double cntm = (double)(samples - op->burnIn + 1);
-            eb[(size_t)b * 4 + 0] = chain[b].sum_th / cntm;
-            eb[(size_t)b * 4 + 1] = chain[b].sum_p0 / cntm;
-            eb[(size_t)b * 4 + 2] = chain[b].sum_p1 / cntm;
-            eb[(size_t)b * 4 + 3] = chain[b].sum_s / cntm;
-        }
-    }
+    sapg_copy_out(u, op, tr.data(), chain.data(), nullptr, SapgOut{thetas, ps, sigmas, logpi, logpi_wu, gx, grads, eb});
     return canary_epilogue(ctx, 0);
 }
 

@@ -1,6 +1,8 @@
 // ---- the SAPG parameter step (SAPG_algorithm_Guassian.m:165-248 and twins) ---------------------------------------
-// Shared by the drivers of the semi-blind TV estimation: sapg.hip (MYULA kernel) and sapg_skrock.hip (SK-ROCK kernel) include
-// this file inside namespace sbtv, as tv.hip includes tv_fused.inc; nothing here is relocatable device code.
+// Shared by the drivers of the semi-blind TV estimation: sapg.hip (MYULA kernel), sapg_skrock.hip (SK-ROCK kernel), sapg_masked.hip
+// (masked observation) and their common host side, sampler_common.hip, include this file inside namespace sbtv, as tv.hip
+// includes tv_fused.inc; nothing here is relocatable device code.  The per-chain update kernel of the two newer drivers is
+// sapg_chain_update.inc.
 // State of one chain, the constants of a run and the traces; the arithmetic below is written once and runs inside the
 // update kernel of the device-resident loop, so that no iteration has to wait for the host, and on the host in the
 // host-side loop.  No FMA contraction on either side: theta / p / sigma traces are bit-identical for the same scalars.
@@ -17,7 +19,7 @@ struct SapgTraces {
     double *theta, *p, *sigma, *logpi, *gx, *grads, *wu;
 };
 static inline size_t sapg_traces_len(const SapgConst &k) { return (size_t)k.batch * k.samples * 10 + (size_t)k.batch * k.warmup; }
-static inline SapgTraces sapg_traces(double *base, const SapgConst &k) {
+__host__ __device__ static inline SapgTraces sapg_traces(double *base, const SapgConst &k) {
     const size_t bs = (size_t)k.batch * k.samples;
     return SapgTraces{base, base + 4 * bs, base + bs, base + 2 * bs, base + 3 * bs, base + 6 * bs, base + 10 * bs};
 }
@@ -28,9 +30,11 @@ __host__ __device__ __forceinline__ double sapg_logpi(const SapgConst &k, const 
     const double resid2 = scal[(size_t)b * 3] * k.parseval;
     return -resid2 / (2 * c.sig2) - c.theta * scal[3 * (size_t)k.batch + b];
 }
-// G[4] = G_theta, G_p0, G_p1, G_sigma of chain b in SAPG iteration ii from the collector's scalars; books logPi and g(X)
+// G[4] = G_theta, G_p0, G_p1, G_sigma of chain b in SAPG iteration ii from the collector's scalars; books logPi and g(X).
+// nobs non-null (masked observation): nobs[b] observed pixels take the place of dimX in G_sigma
 __host__ __device__ __forceinline__ void sapg_gradients(const SapgConst &k, const SapgTraces &tr, const SapgChain &c,
-                                                        const double *scal, int b, int ii, double *G) {
+                                                        const double *scal, int b, int ii, double *G,
+                                                        const double *nobs = nullptr) {
 #pragma clang fp contract(off)
     const int i0 = ii - 1;
     const double resid2 = scal[(size_t)b * 3] * k.parseval;
@@ -38,7 +42,7 @@ __host__ __device__ __forceinline__ void sapg_gradients(const SapgConst &k, cons
     G[0] = k.dimX / c.theta - tv;                                                             // :165
     G[1] = (scal[(size_t)b * 3 + 1] * k.parseval) / c.sig2;                                   // :170
     G[2] = (scal[(size_t)b * 3 + 2] * k.parseval) / c.sig2;                                   // :179
-    G[3] = resid2 / (2 * c.sig2 * c.sig2) - k.dimX / (2 * c.sig2);                            // :188
+    G[3] = resid2 / (2 * c.sig2 * c.sig2) - (nobs ? nobs[b] : k.dimX) / (2 * c.sig2);         // :188
     tr.logpi[(size_t)b * k.samples + i0] = lp;                                                // :207
     tr.gx[(size_t)b * k.samples + (i0 - 1)] = tv;                                             // :208
 }

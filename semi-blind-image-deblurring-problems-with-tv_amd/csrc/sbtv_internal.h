@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -330,6 +331,17 @@ inline int mom_sample_of(const MomReq *mr, int ii) {
     return (ii - mr->first) / mr->thin + 1;
 }
 inline long long mom_count(const MomReq &mr, int last) { return (last - mr.first) / mr.thin + 1; }
+// The moments request of an entry (sampler_common.hip), every refusal SBTV_ERR_BADARG "<who>: ...".  mo null: no request,
+// *selp = null, and moment outputs without options are refused; an entry whose request is not optional passes selp = null and
+// has a missing one refused.  Otherwise `mean` is required, thin >= 1, and first (0: the entry's first0) lies in 1..last, the
+// entry's last iteration; *sel is filled and *selp points to it.  The pooled check is the caller's: check_one_posterior, or
+// its own rule.
+int mom_resolve(sbtv_ctx *ctx, const char *who, const sbtv_moments_opts *mo, int first0, int last, double *mean, double *var,
+                long long *count, bool dev, MomReq *sel, const MomReq **selp);
+// pooled = 1 over batch > 1 chains needs chains of ONE posterior: the same y [batch][P] (dev: read back from the device),
+// taps [batch][taille^2], theta and sigma2 in every chain; a null array refuses too
+int check_one_posterior(sbtv_ctx *ctx, const char *who, const double *y, size_t P, const double *taps, int taille,
+                        const double *theta, const double *sigma2, int batch, bool dev);
 // iteration 1 (the start state) as sample 1: mean = X, m2 = 0
 int moments_seed(sbtv_ctx *ctx, const double *X, double *mean, double *m2, size_t P, int batch);
 // mean / m2 of `batch` chains of n samples each -> req's outputs: per chain (var = m2 / (n-1), 0 for n = 1), or pooled over
@@ -729,6 +741,82 @@ int op_resid(sbtv_ctx *ctx, const BlurOp &c, const double *x, double *acc, const
 int op_gradf(sbtv_ctx *ctx, const BlurOp &c, const double *x, double *acc, double *grad);
 // the start image by `initialization` of sbtv_salsa_opts: 0 zeros, 2 AT(y), else the caller's xi
 int op_init_x(sbtv_ctx *ctx, const BlurOp &c, int initialization, const double *yd, const double *xi, double *x);
+
+// ----------------------------- what the TV sampler drivers share on the host (sampler_common.hip) ---------
+// The normals of one step as the kernels read them: the staging buffer Z of one step of host noise (null: none needed), the
+// caller's device array, or null (Philox).  stage() enqueues the copy of the step's normals into Z, ptr() is what a kernel
+// launched after it reads; get() is both.
+struct NoiseFeed {
+    sbtv_ctx *ctx;
+    const double *noise;
+    double *Z;
+    size_t cnt;
+    int stage(size_t step) const {
+        if (Z) SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + step * cnt, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    }
+    const double *ptr(size_t step) const { return Z ? Z : (noise ? noise + step * cnt : nullptr); }
+    int get(size_t step, const double **zd) const {
+        SBTV_TRY(stage(step));
+        *zd = ptr(step);
+        return 0;
+    }
+};
+// The plain MYULA chain (SALSA/myula.m:13-16) on buffers its caller has set up: for ii = 2..samples - 1 the cold prox of X,
+// the caller's gradient() of the likelihood at X into `grad` (times sigma2), the step; sample ii joins the moments where mom
+// selects it.  sync_every > 0: the stream is synchronised every so many iterations.
+struct MyulaLoop {
+    double *X, *prox, *grad;
+    const double *sig_d;        // [batch] (device)
+    const ProxPlan *pp;
+    ProxArm arm;
+    NoiseFeed nz;
+    double gamma, lambda;
+    size_t P;
+    int batch, samples, chambolleit;
+    unsigned long long seed;
+    int chain_offset;
+    const MomReq *mom;
+    double *pm_mean, *pm_m2;
+    int sync_every;
+};
+int myula_plain_loop(sbtv_ctx *ctx, const MyulaLoop &a, const std::function<int()> &gradient);
+
+// The front and back end of the SAPG drivers of the TV model (sapg.hip, sapg_skrock.hip, sapg_masked.hip); SapgConst, SapgChain
+// and the trace layout are sapg_step.inc's.
+struct SapgConst;
+struct SapgChain;
+// what sbtv_SAPG_algorithm refuses, with its codes; every message starts "<who>: "
+int sapg_refuse(sbtv_ctx *ctx, const char *who, const double *y, int M, int N, int batch, const sbtv_sapg_opts *op);
+// the constants of the parameter step; shared: one spectrum set for all chains; parseval: the factor on the collector's sums
+void sapg_fill_const(SapgConst *u, const sbtv_sapg_opts *op, int M, int N, int batch, bool shared, double parseval);
+// the state every chain starts from, with the burn-in sums at burnIn = 1
+SapgChain sapg_chain_start(const SapgConst &u, const sbtv_sapg_opts *op);
+// the start of a call whose chains own their parameters: `batch` chains at sapg_chain_start, and the block the device's `par`
+// starts from: the host's taps and derivative taps of p_init for every chain, [taps | d0 | d1], then lam[batch], sigma2[batch]
+int sapg_start(sbtv_ctx *ctx, const char *who, const SapgConst &u, const sbtv_sapg_opts *op, std::vector<SapgChain> *chain,
+               std::vector<double> *par);
+// the device side of such a call in the workspaces "<prefix>.par", ".scal" [4*batch], ".delta" [samples + 1], ".chain" and
+// ".traces": par, delta(ii) and the chains uploaded, the traces zeroed; returns after the uploads have completed
+struct SapgDevBufs {
+    double *par, *scal, *delta, *traces;
+    SapgChain *chain;
+};
+int sapg_device_setup(sbtv_ctx *ctx, const char *prefix, const SapgConst &u, const sbtv_sapg_opts *op,
+                      const std::vector<SapgChain> &chain, const std::vector<double> &par, SapgDevBufs *d);
+// enqueues the copies of the device traces and chains to the host (tr is sized here); the caller synchronises
+int sapg_download(sbtv_ctx *ctx, const SapgConst &u, const SapgDevBufs &d, std::vector<double> *tr,
+                  std::vector<SapgChain> *chain);
+// spectra of the taps and of their parameter derivatives in `par`, ONE launch for the two or three sets (fp: u.nspec images)
+int sapg_spectra(sbtv_ctx *ctx, const FftPlan &fp, const SapgConst &u, const double *par, double2 *Hs, double2 *D1s,
+                 double2 *D2s);
+// the traces (layout of sapg_traces, on the host) and the chains' end state -> the caller's arrays, each optional: slot 0 of
+// theta / sigma2 / p is the start value, eb the four EB means (:258-284); logpi0 non-null: logpi of slot 0 per chain
+struct SapgOut {
+    double *thetas, *ps, *sigmas, *logpi, *logpi_wu, *gx, *grads, *eb;
+};
+void sapg_copy_out(const SapgConst &u, const sbtv_sapg_opts *op, const double *tr, const SapgChain *chain,
+                   const double *logpi0, const SapgOut &out);
 
 // ---- argument checks the entry points share
 int check_psf_fits(sbtv_ctx *ctx, int taille, int M, int N);       // SBTV_ERR_PSF "Mask does not fit inside array"

@@ -6,7 +6,9 @@
 // element-wise stage kernel - and one residual pass (op_resid) on the new sample.  Two image buffers alternate: stage j reads
 // K_{j-1} (U) and K_{j-2} (V) and writes K_j over V; the last stage also writes the perturbed state P of the next step over
 // U, so the new sample and P_next swap buffers when `stages` is odd.  Every stage kernel re-arms the prox control blocks for
-// the cold prox that follows it (ProxArm), as myula_plain_kernel does.
+// the cold prox that follows it (ProxArm), as myula_plain_kernel does.  The kernels and the host side of a step - stage table,
+// noise feed, perturb launch, stage dispatch, buffer parity - are SkrockStepper of skrock_stage.inc, shared with sapg_skrock.hip;
+// the moments request and the pooled check are mom_resolve / check_one_posterior (sampler_common.hip).
 //
 // Traces.  Ring slot r holds, for ONE sample ii, the accumulators of its residual pass and the partial sums of TVnorm(X(ii))
 // (from the forward column pass of that residual pass where fft_cols_tv_ok allows, else from tvnorm_partials):
@@ -91,42 +93,10 @@ int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const d
     // the moments request: the checks of sbtv_myula_moments
     MomReq sel{};
     const MomReq *selp = nullptr;
-    if (mo) {
-        if (!post_mean) return fail(ctx, SBTV_ERR_BADARG, "skrock: moments options and post_mean are required");
-        const int first = mo->first == 0 ? 1 : mo->first;
-        if (mo->thin < 1 || first < 1 || first > samples)
-            return fail(ctx, SBTV_ERR_BADARG, "skrock: need thin >= 1 and 1 <= first <= samples");
-        sel = MomReq{first, mo->thin, mo->pooled ? 1 : 0, post_mean, post_var, post_count, dev, false};
-        selp = &sel;
-        if (sel.pooled && batch > 1) {
-            // pooling needs chains of ONE posterior: the same y, taps, theta and sigma2 in every chain
-            bool same = true;
-            for (int b = 1; same && b < batch; ++b)
-                same = theta[b] == theta[0] && sigma2[b] == sigma2[0] && !memcmp(taps, taps + b * t2, sizeof(double) * t2);
-            if (same) {
-                std::vector<double> yh;
-                const double *yv = y;
-                if (dev) {
-                    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-                    yh.resize(cnt);
-                    SBTV_HIP(ctx, hipMemcpy(yh.data(), y, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-                    yv = yh.data();
-                }
-                for (int b = 1; same && b < batch; ++b) same = !memcmp(yv, yv + b * P, sizeof(double) * P);
-            }
-            if (!same) return fail(ctx, SBTV_ERR_BADARG, "skrock: pooled = 1 needs chains with the same y, taps, theta and sigma2");
-        }
-    } else if (post_mean || post_var || post_count) {
-        return fail(ctx, SBTV_ERR_BADARG, "skrock: moment outputs without moments options");
-    }
-
-    // the coefficient table and the scalars of the stages
-    std::vector<double> mu(stages), nu(stages), kappa(stages);
-    SBTV_TRY(sbtv_skrock_coefficients(stages, op->eta, mu.data(), nu.data(), kappa.data(), nullptr, nullptr));
-    const double lambda = op->lambda, delta = op->delta, q = sqrt(2 * delta), nu1q = nu[0] * q;
-    std::vector<SkrockStage> st(stages);
-    st[0] = SkrockStage{mu[0] * delta, 0.0, kappa[0] * q, nu1q};
-    for (int j = 1; j < stages; ++j) st[j] = SkrockStage{mu[j] * delta, nu[j], kappa[j], nu1q};
+    SBTV_TRY(mom_resolve(ctx, "skrock", mo, 1, samples, post_mean, post_var, post_count, dev, &sel, &selp));
+    if (selp && sel.pooled && batch > 1)
+        SBTV_TRY(check_one_posterior(ctx, "skrock", y, P, taps, taille, theta, sigma2, batch, dev));
+    const double lambda = op->lambda;
 
     SBTV_HIP(ctx, hipSetDevice(ctx->device));
     BlurOp bop;
@@ -134,7 +104,7 @@ int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const d
     ProxPlan pp;
     SBTV_TRY(prox_plan(ctx, M, N, batch, &pp));
     const bool traces = gx || logpi, tv_fused = fft_cols_tv_ok(bop.fp), noise_host = noise && !dev;
-    const int nrb = fft_rows_blocks(bop.fp), nblk = ew_blocks(P);
+    const int nrb = fft_rows_blocks(bop.fp);
     const int ring = samples < SK_RING ? samples : SK_RING;
     const double *yd = nullptr, *x0d = nullptr;
     SBTV_TRY(stage_in(ctx, "skrock.y", y, cnt, flags, &yd));
@@ -207,73 +177,22 @@ int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const d
         u.ntv = ntv; u.nrb = nrb; u.samples = samples; u.parseval = bop.parseval;
     }
 
-    // the normals of `step` as the kernels read them: the staging buffer, the caller's device array, or null: Philox
-    auto stage_noise = [&](unsigned step) -> int {
-        if (!noise_host) return 0;
-        SBTV_HIP(ctx, hipMemcpyAsync(Z, noise + (size_t)step * cnt, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
-        return 0;
-    };
-    auto normals = [&](unsigned step) -> const double * {
-        if (noise_host) return Z;
-        return noise ? noise + (size_t)step * cnt : nullptr;
-    };
-    const dim3 grid(nblk, batch), block(SKB);
-    // one stage: the drift at U (prox and gradient), then the stage kernel
-    auto stage = [&](double *U, double *V, int j, bool next_p, const RngArgs &r, const MomArgs *mc) -> int {
-        const bool first = j == 1, last = j == stages, np = last && next_p, mo_on = last && mc && mc->k > 0;
-        SBTV_TRY(prox_iterate(ctx, pp, U, chambolleit, prox, true));
-        SBTV_TRY(op_gradf(ctx, bop, U, acc_g, grad));
-        const double *zd = first ? normals(r.step) : (np ? normals(r.step + 1u) : nullptr);
-        const SkrockStage &sj = st[j - 1];
-#define SBTV_SKROCK_STAGE(F, L, NX, MO, momarg)                                                                           \
-    hipLaunchKernelGGL((skrock_stage_kernel<F, L, NX, MO>), grid, block, 0, ctx->stream, U, V, (const double *)prox,         \
-                       (const double *)grad, zd, (const double *)sig_d, lambda, sj, P, r, arm, momarg)
-        if (first)
-            SBTV_SKROCK_STAGE(true, false, false, false, SkNoMom{});
-        else if (!last)
-            SBTV_SKROCK_STAGE(false, false, false, false, SkNoMom{});
-        else if (np && mo_on)
-            SBTV_SKROCK_STAGE(false, true, true, true, *mc);
-        else if (np)
-            SBTV_SKROCK_STAGE(false, true, true, false, SkNoMom{});
-        else if (mo_on)
-            SBTV_SKROCK_STAGE(false, true, false, true, *mc);
-        else
-            SBTV_SKROCK_STAGE(false, true, false, false, SkNoMom{});
-#undef SBTV_SKROCK_STAGE
-        SBTV_HIP(ctx, hipGetLastError());
-        return 0;
-    };
+    // the steps: the sample sits in sk.X, the caller's buffer or the second one, as the parity of the stage count has it
+    SkrockStepper sk{ctx, &bop, &pp, arm, NoiseFeed{ctx, noise, Z, cnt}, A, K, prox, grad, acc_g, sig_d, pm_mean, pm_m2, lambda, P,
+                     batch, stages, chambolleit, op->seed, (unsigned)op->chain_offset};
+    SBTV_TRY(sk.table(op->eta, op->delta));
 
-    double *X = A, *Pb = K;                                                  // the sample; the perturbed state of the next step
     // sample 1: the start state
-    if (mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, X, pm_mean, pm_m2, P, batch));
+    if (mom_sample_of(selp, 1)) SBTV_TRY(moments_seed(ctx, sk.X, pm_mean, pm_m2, P, batch));
     int filled = 0;                                                          // ring slots waiting for the trace kernel
     if (traces) {
-        SBTV_TRY(residual_pass(X, 0));
+        SBTV_TRY(residual_pass(sk.X, 0));
         filled = 1;
     }
     for (int ii = 2; ii <= samples; ++ii) {
-        const RngArgs r{op->seed, (unsigned)(ii - 2), (unsigned)op->chain_offset, nullptr};
-        const bool more = ii < samples;
-        if (ii == 2) {
-            SBTV_TRY(stage_noise(r.step));
-            hipLaunchKernelGGL(skrock_perturb_kernel, grid, block, 0, ctx->stream, (const double *)X, Pb, normals(r.step), nu1q,
-                               P, r, arm);
-            SBTV_HIP(ctx, hipGetLastError());
-        }
-        double *U = Pb, *V = X;                                              // K_{j-1} (stage 1: P), K_{j-2}
-        SBTV_TRY(stage(U, V, 1, false, r, nullptr));
-        if (more) SBTV_TRY(stage_noise(r.step + 1u));                        // after FIRST, before LAST
-        for (int j = 2; j <= stages; ++j) {
-            const MomArgs mc{pm_mean, pm_m2, j == stages ? mom_sample_of(selp, ii) : 0, nullptr, 1, 1};
-            SBTV_TRY(stage(U, V, j, more, r, &mc));
-            std::swap(U, V);                                                 // U = K_j, V = K_{j-1} (after the last: P_next)
-        }
-        X = U;
-        Pb = V;
+        SBTV_TRY(sk.step(mom_sample_of(selp, ii), ii < samples));
         if (traces) {
-            SBTV_TRY(residual_pass(X, filled));
+            SBTV_TRY(residual_pass(sk.X, filled));
             if (++filled == ring || ii == samples) {
                 SBTV_TRY(trace(filled, ii - filled + 1));
                 if (filled == SK_RING) SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -288,9 +207,9 @@ int sbtv_skrock(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const d
     std::vector<double> tr(traces ? trlen : 0);
     if (traces) SBTV_HIP(ctx, hipMemcpyAsync(tr.data(), tr_d, sizeof(double) * trlen, hipMemcpyDeviceToHost, ctx->stream));
     // the last sample sits in the caller's buffer or in the second one, as the parity of the stage count has it
-    if (dev && x_last && X != x_last)
-        SBTV_HIP(ctx, hipMemcpyAsync(x_last, X, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_TRY(stage_out_copy(ctx, x_last, X, cnt, flags));
+    if (dev && x_last && sk.X != x_last)
+        SBTV_HIP(ctx, hipMemcpyAsync(x_last, sk.X, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
+    SBTV_TRY(stage_out_copy(ctx, x_last, sk.X, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < bs && traces; ++i) {
         if (gx) gx[i] = tr[i];

@@ -1,5 +1,6 @@
 // The element-wise kernels of one SK-ROCK step on the TV posterior (include/sbtv.h, sbtv_skrock): the perturbation, the stage
-// kernels and the re-arming of the cold prox that follows each of them.  Shared by skrock.hip (fixed parameters) and
+// kernels and the re-arming of the cold prox that follows each of them, and SkrockStepper, the host side of a step (below).
+// Shared by skrock.hip (fixed parameters) and
 // sapg_skrock.hip (the SAPG estimation with this step as its Markov kernel): both include this file inside their unnamed
 // namespace, under `#pragma clang fp contract(off)`, as tv.hip includes tv_fused.inc; nothing here is relocatable device code.
 constexpr int SKB = 256;          // lanes per workgroup of the element-wise kernels (grid: ew_blocks(P) x batch)
@@ -119,3 +120,88 @@ __global__ __launch_bounds__(SKB) __attribute__((amdgpu_waves_per_eu(6))) void s
         }
     }
 }
+
+// The host side of the steps of one call: the stage table, the two image buffers and the noise feed; it owns the perturb launch
+// of the first step, the stage dispatch and the buffer parity.  Two image buffers alternate: stage j reads K_{j-1} (U) and
+// K_{j-2} (V) and writes K_j over V; the last stage also writes the perturbed state P of the next step over U, so the new sample
+// and P_next swap buffers when `stages` is odd.  The caller fills the fields up to `chain0`, calls table() and then step() once
+// per sample; X is the buffer that holds the sample.  sigma2 and the lambda theta of `arm` are read on the device.
+struct SkrockStepper {
+    sbtv_ctx *ctx;
+    const BlurOp *bop;
+    const ProxPlan *pp;
+    ProxArm arm;
+    NoiseFeed nz;
+    double *X, *Pb;              // the sample; the perturbed state of the next step
+    double *prox, *grad, *acc_g; // prox and gradient of a stage's input; the residual sums of the gradient passes (not used)
+    const double *sig_d;         // [batch] (device)
+    double *pm_mean, *pm_m2;     // running mean / M2 of the samples [batch][P], or null
+    double lambda;
+    size_t P;
+    int batch, stages, chambolleit;
+    unsigned long long seed;
+    unsigned chain0;
+    unsigned done = 0;           // steps taken: the counter of the next one (steps count from 0)
+    std::vector<SkrockStage> st;
+
+    // the coefficient table and the scalars of the stages for the step dt
+    int table(double eta, double dt) {
+        std::vector<double> mu(stages), nu(stages), kappa(stages);
+        SBTV_TRY(sbtv_skrock_coefficients(stages, eta, mu.data(), nu.data(), kappa.data(), nullptr, nullptr));
+        const double q = sqrt(2 * dt), nu1q = nu[0] * q;
+        st.assign(stages, SkrockStage{});
+        st[0] = SkrockStage{mu[0] * dt, 0.0, kappa[0] * q, nu1q};
+        for (int j = 1; j < stages; ++j) st[j] = SkrockStage{mu[j] * dt, nu[j], kappa[j], nu1q};
+        return 0;
+    }
+    // one stage: the drift at U (prox and gradient with the current H), then the stage kernel
+    int stage(double *U, double *V, int j, bool next_p, const RngArgs &r, const MomArgs *mc) {
+        const bool first = j == 1, last = j == stages, np = last && next_p, mo_on = last && mc && mc->k > 0;
+        SBTV_TRY(prox_iterate(ctx, *pp, U, chambolleit, prox, true));
+        SBTV_TRY(op_gradf(ctx, *bop, U, acc_g, grad));
+        const double *zd = first ? nz.ptr(r.step) : (np ? nz.ptr(r.step + 1u) : nullptr);
+        const SkrockStage &sj = st[j - 1];
+        const dim3 grid(ew_blocks(P), batch), block(SKB);
+#define SBTV_SKROCK_STAGE(F, L, NX, MO, momarg)                                                                           \
+    hipLaunchKernelGGL((skrock_stage_kernel<F, L, NX, MO>), grid, block, 0, ctx->stream, U, V, (const double *)prox,         \
+                       (const double *)grad, zd, sig_d, lambda, sj, P, r, arm, momarg)
+        if (first)
+            SBTV_SKROCK_STAGE(true, false, false, false, SkNoMom{});
+        else if (!last)
+            SBTV_SKROCK_STAGE(false, false, false, false, SkNoMom{});
+        else if (np && mo_on)
+            SBTV_SKROCK_STAGE(false, true, true, true, *mc);
+        else if (np)
+            SBTV_SKROCK_STAGE(false, true, true, false, SkNoMom{});
+        else if (mo_on)
+            SBTV_SKROCK_STAGE(false, true, false, true, *mc);
+        else
+            SBTV_SKROCK_STAGE(false, true, false, false, SkNoMom{});
+#undef SBTV_SKROCK_STAGE
+        SBTV_HIP(ctx, hipGetLastError());
+        return 0;
+    }
+    // X <- SKROCK_step(X); momk > 0: the new sample is sample momk of the moments; more: another step follows, so the last
+    // stage forms its perturbed state
+    int step(int momk, bool more) {
+        const RngArgs r{seed, done, chain0, nullptr};
+        if (done == 0) {
+            SBTV_TRY(nz.stage(0));
+            hipLaunchKernelGGL(skrock_perturb_kernel, dim3(ew_blocks(P), batch), dim3(SKB), 0, ctx->stream, (const double *)X, Pb,
+                               nz.ptr(0), st[0].nu1q, P, r, arm);
+            SBTV_HIP(ctx, hipGetLastError());
+        }
+        double *U = Pb, *V = X;                                              // K_{j-1} (stage 1: P), K_{j-2}
+        SBTV_TRY(stage(U, V, 1, false, r, nullptr));
+        if (more) SBTV_TRY(nz.stage(done + 1u));                             // after FIRST, before LAST
+        for (int j = 2; j <= stages; ++j) {
+            const MomArgs mc{pm_mean, pm_m2, j == stages ? momk : 0, nullptr, 1, 1};
+            SBTV_TRY(stage(U, V, j, more, r, &mc));
+            std::swap(U, V);                                                 // U = K_j, V = K_{j-1} (after the last: P_next)
+        }
+        X = U;
+        Pb = V;
+        ++done;
+        return 0;
+    }
+};

@@ -110,34 +110,13 @@ int sbtv_myula_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
             return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: moments need post_mean or coef_mean");
         if ((post_var && !post_mean) || (coef_var && !coef_mean))
             return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: post_var needs post_mean and coef_var needs coef_mean");
-        const int first = mo->first == 0 ? 1 : mo->first;
-        if (mo->thin < 1 || first < 1 || first > samples)
-            return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: need thin >= 1 and 1 <= first <= samples");
-        sel = MomReq{first, mo->thin, mo->pooled ? 1 : 0, nullptr, nullptr, nullptr, dev, false};
-        selp = &sel;
-        if (sel.pooled && batch > 1) {
-            // pooling needs chains of ONE posterior: the same y, taps, theta and sigma2 in every chain
-            const size_t t2 = (size_t)taille * taille;
-            bool same = true;
-            for (int b = 1; same && b < batch; ++b)
-                same = theta[b] == theta[0] && sigma2[b] == sigma2[0] && !memcmp(taps, taps + b * t2, sizeof(double) * t2);
-            if (same) {
-                std::vector<double> yh;
-                const double *yv = y;
-                if (dev) {
-                    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-                    yh.resize(cnt);
-                    SBTV_HIP(ctx, hipMemcpy(yh.data(), y, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-                    yv = yh.data();
-                }
-                for (int b = 1; same && b < batch; ++b) same = !memcmp(yv, yv + b * P, sizeof(double) * P);
-            }
-            if (!same)
-                return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: pooled = 1 needs chains with the same y, taps, theta and sigma2");
-        }
     } else if (post_mean || post_var || post_count || coef_mean || coef_var) {
         return fail(ctx, SBTV_ERR_BADARG, "myula_wavelet: moment outputs without moments options");
     }
+    // MomReq's outputs are set per domain where the moments are finished
+    SBTV_TRY(mom_resolve(ctx, "myula_wavelet", mo, 1, samples, post_mean ? post_mean : coef_mean, nullptr, nullptr, dev, &sel, &selp));
+    if (selp && sel.pooled && batch > 1)
+        SBTV_TRY(check_one_posterior(ctx, "myula_wavelet", y, P, taps, taille, theta, sigma2, batch, dev));
     const bool mom_img = selp && post_mean, mom_coef = selp && coef_mean;
 
     WavChain wc;

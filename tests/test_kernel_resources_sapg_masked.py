@@ -13,7 +13,7 @@ from test_kernel_resources import HIPCC, _find, _report
 def test_sapg_masked_kernels_have_no_scratch_and_do_not_spill():
     rep = _report("sapg_masked.hip")
     kernels = {"residual with the derivative sums": "masked_resid_kernelILb1EE", "residual": "masked_resid_kernelILb0EE",
-               "count": "masked_count_kernel", "update": "sapg_masked_update_kernel"}
+               "count": "masked_count_kernel", "update": "sapg_chain_update_kernel"}    # the update: csrc/sapg_chain_update.inc
     assert len(rep) == len(kernels), sorted(rep)                          # every kernel of the file is looked at
     for what, name in kernels.items():
         k = _find(rep, name)
