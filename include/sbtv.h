@@ -333,6 +333,36 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                        double *xw_out, double *x_out,
                        double *objective, double *distance, double *times, double *mses,
                        int *numA, int *numAt, int *n_outer, int flags);
+/* min over the IMAGE x  0.5 ||y - B x||^2 + tau ||W' x||_1  (the analysis-prior form; B: circular blur of `taps`), as
+ * SALSA/SALSA_v2.m:389-494 solves it with its 'P' / 'PT' options (:98-101, 198-203): TVINITIALIZATION = 0, Psi = soft,
+ * Phi = l1, A = B, AT = B', PT = W' = mrdwt_TI2D applied to the image (:389, 438), P = W = mirdwt_TI2D applied to the
+ * coefficients (:434), and invLS(r) = real(ifft2(fft2(r) ./ (abs(H).^2 + mu))), the exact x-minimiser because W W' = I:
+ *     start:  x by opts->initialization (0 zeros, 2 B'y, 33333 x_init) ;  PTx = W'x ;  u = PTx ;  bu = 0            (:367-393)
+ *             objective(1) = 0.5 ||y - B x||^2 + tau ||u||_1 ;  mses(1) = ||x - true_x||^2 / (M N)                  (:399-415)
+ *     outer:  u   = soft(PTx - bu, tau/mu)                                                                          (:431)
+ *             x   = invLS(B'y + mu * W(u + bu))                                                                     (:434-436)
+ *             PTx = W'x ;  bu = bu + (u - PTx)                                                                      (:438-440)
+ *             objective(outer+1) = 0.5 ||y - B x||^2 + tau ||u||_1 ;  mses(outer+1) = ||x - true_x||^2 / (M N)      (:442-449)
+ *             distance(outer)    = ||PTx - u|| / sqrt(||PTx||^2 + ||u||^2)                                          (:451)
+ *             stop rules 1, 2, 3 from outer = 2 on (:453-482); rule 2 is ||x - xprev|| / ||x|| on the image
+ * What runs keeps the coefficient state (s, bu), s = u + bu: z = W s, X = (conj(H) .* fft2(y) + mu * fft2(z)) ./ (abs(H).^2 + mu),
+ * x = real(ifft2(X)), w = W'x, then one pass over the coefficients recovers u = s - bu (exactly zero where the threshold cut
+ * it), takes the sums of the traces, forms bu + (u - w) and the next s = soft(w - bu, tau/mu) + bu.
+ * true_x / x_init / x_out: [batch][M*N] images; x_out is required.  objective / times / mses: [batch*(maxiter+1)]; distance:
+ * [batch*maxiter]; numA = 1 + one per outer iteration, numAt = 1 (B'y), as SALSA_v2 counts them (P and PT are not counted).
+ * opts->TViters and the Chambolle knobs are ignored; opts->speculate bit 0 as for sbtv_SALSA_wavelet (x, s and bu are
+ * double-buffered: the result is that of the stopping iteration).  Images of a batch are solved one after another, image k bit
+ * for bit as alone.  SBTV_DEVICE_PTRS applies to y / true_x / x_init / x_out.
+ * Errors before any GPU work: those of sbtv_SALSA_wavelet, with its codes: h not orthonormal, mu[b] <= 0, tau / mu / x_out
+ * NULL -> SBTV_ERR_BADARG; odd pixel count or tap reach >= min(M, N) -> SBTV_ERR_SIZE; stop criterion, initialization,
+ * maxiter and PSF fit as sbtv_SALSA_v2. */
+int sbtv_SALSA_analysis(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                        const double *taps, int taille,
+                        const double *h, int hlen, int levels,
+                        const double *tau, const double *mu, const sbtv_salsa_opts *opts,
+                        const double *true_x, const double *x_init, double *x_out,
+                        double *objective, double *distance, double *times, double *mses,
+                        int *numA, int *numAt, int *n_outer, int flags);
 
 /* ---- empirical-Bayes estimate of theta for the wavelet-l1 prior (SALSA/run_deblur_synthesis_L1.m:125-156) -----------------
  * The script estimates the regularisation parameter before it solves the MAP problem: a MYULA chain on the wavelet

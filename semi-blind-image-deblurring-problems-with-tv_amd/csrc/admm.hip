@@ -413,6 +413,54 @@ __global__ __launch_bounds__(AB) void wav_sum_kernel(const double *__restrict__ 
     }
 }
 
+// ---- analysis-prior wavelet SALSA (analysis_one) ------------------------------------------------------------------
+// The one coefficient pass of an outer iteration k, after the analysis w = W'x_k, on the state (s, bu) = (u_k + bu_{k-1}, bu_{k-1}):
+//   u = s - bu (exactly zero where the threshold cut it: there s == bu bit for bit) ; bu' = bu + (u - w)    (SALSA_v2.m:440)
+//   u' = soft(w - bu', T) ; s' = u' + bu'                                                                  (:431 of k + 1)
+//   partials [4][nb]: |u|, u^2, (w-u)^2, w^2
+// The start is the same pass with s = w_0 and bu = 0.
+__global__ __launch_bounds__(AB) void wav_astep_kernel(const double *__restrict__ s, const double *__restrict__ bu,
+                                                        const double *__restrict__ w, double *__restrict__ bun,
+                                                        double *__restrict__ sn, double T, double *__restrict__ partials,
+                                                        size_t C) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    AD_LOOP(q, C) {
+        const double2 sv = AD_LD(s, q), bv = AD_LD(bu, q), wv = AD_LD(w, q);
+        const double u0 = sv.x - bv.x, u1 = sv.y - bv.y;
+        const double d0 = wv.x - u0, d1 = wv.y - u1;
+        const double b0 = bv.x + (u0 - wv.x), b1 = bv.y + (u1 - wv.y);
+        AD_ST(bun, q, make_double2(b0, b1));
+        AD_ST(sn, q, make_double2(wav_soft(wv.x - b0, T) + b0, wav_soft(wv.y - b1, T) + b1));
+        acc[0] += fabs(u0) + fabs(u1);
+        acc[1] += u0 * u0 + u1 * u1;
+        acc[2] += d0 * d0 + d1 * d1;
+        acc[3] += wv.x * wv.x + wv.y * wv.y;
+    }
+    ad_store_partials<4>(acc, partials);
+}
+
+// the image-domain sums of an outer iteration: partials [3][nb]: (x-true)^2, (x-xprev)^2, x^2 (tru / xprev null: not summed)
+__global__ __launch_bounds__(AB) void ad_xsums_kernel(const double *__restrict__ x, const double *__restrict__ tru,
+                                                       const double *__restrict__ xprev, double *__restrict__ partials,
+                                                       size_t P) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    AD_LOOP(q, P) {
+        const double2 xv = AD_LD(x, q);
+        if (tru) {
+            const double2 tv = AD_LD(tru, q);
+            const double m0 = xv.x - tv.x, m1 = xv.y - tv.y;
+            acc[0] += m0 * m0 + m1 * m1;
+        }
+        if (xprev) {
+            const double2 xo = AD_LD(xprev, q);
+            const double m0 = xv.x - xo.x, m1 = xv.y - xo.y;
+            acc[1] += m0 * m0 + m1 * m1;
+        }
+        acc[2] += xv.x * xv.x + xv.y * xv.y;
+    }
+    ad_store_partials<3>(acc, partials);
+}
+
 // ---- wavelet-l1 FISTA (fista_l1_one) ------------------------------------------------------------------------------
 // zy = zx + c (zx - zxo): the image W y of the momentum point y = x + c (x - xo), by linearity of W
 __global__ __launch_bounds__(AB) void fl1_momentum_kernel(const double *__restrict__ zx, const double *__restrict__ zxo,
@@ -1261,6 +1309,119 @@ int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *tap
 }
 
 // ------------------------------------------------------------------------------------------------
+// Wavelet-l1 deconvolution in the analysis form, the 'P' / 'PT' mode of SALSA_v2.m (:98-101, 198-203):
+//     min over the image x   0.5 ||y - B x||^2 + tau ||W' x||_1,
+// solved as SALSA_v2.m:389-494 does with Psi = soft, Phi = l1, A = B, AT = B', PT = W', P = W and invLS(r) =
+// real(ifft2(fft2(r) ./ (|H|^2 + mu))), the exact x-minimiser because W W' = I.  One outer iteration k on the coefficient
+// state (s, bu), s = u + bu:
+//     z = W s_k ;  X = (conj(H) fft2(y) + mu fft2(z)) / (|H|^2 + mu) ;  x_k = real(ifft2(X))      (the row pass OP_SALSA on z)
+//     w_k = W' x_k ;  the step pass (wav_astep_kernel): u_k = s_k - bu_{k-1}, its sums, bu_k, s_{k+1}
+// with ||y - B x_k||^2 from the row pass's Parseval sum and the image-domain sums of x_k from a pixel pass, launched only when
+// 'TRUE_X' or stop rule 2 ask for them.  s, bu and x are double-buffered, so the result of the stopping iteration is intact
+// when the host evaluates the stop rule one iteration late.  Per outer iteration: one synthesis (J launches), the FFT triple,
+// one analysis (J launches), the step pass, the pixel pass and one reduction launch.
+int analysis_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
+                 double mu, const sbtv_salsa_opts *opts, const double *td, const double *xi, double *x_out_dev,
+                 double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer) {
+    BlurOp c;
+    SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
+    const size_t P = c.P, C = P * wp.bands();
+    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
+    double *sbuf[2], *bbuf[2], *xbuf[2], *w, *z, *par, *partials, *sums, *acc;
+    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &sbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &sbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &bbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "wav.we1", C, &bbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "wav.w", C, &w));
+    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &xbuf[0]));
+    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &xbuf[1]));
+    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &z));
+    SBTV_TRY(ws_get_t(ctx, "admm.par", (size_t)4, &par));               // mu
+    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..3] step sums, nb each, then [0..2] pixel sums, nbp each
+    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0..3] step sums, [4..6] pixel sums, [8] resid2
+    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
+    double *ppix = partials + (size_t)4 * nb;
+    AdmmRun run;
+    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
+    SBTV_TRY(upload_par(ctx, par, {mu, 0.0, 0.0, 0.0}));
+    const double T = tau / mu;                                           // :394
+    const int maxiter = opts->maxiter;
+    const bool rule2 = opts->stopcriterion == 2;
+    run.numAt = 1;                                                       // ATy (:288)
+    ctx->calls += 2;                                                     // AT(y), invLS(ATy)
+    if (opts->initialization == 0) ctx->calls += 1;                      // AT(zeros) (:369)
+    SBTV_TRY(op_init_x(ctx, c, opts->initialization, yd, xi, xbuf[0]));  // :367-381
+    // PTx = W'x ; u = PTx ; bu = 0 (:389-393) and the initial objective (:399-401): the step pass on (s, bu) = (PTx, 0)
+    double obj_prev;
+    {
+        SBTV_TRY(wav_analysis(ctx, wp, xbuf[0], w, 1));
+        SBTV_HIP(ctx, hipMemsetAsync(bbuf[1], 0, sizeof(double) * C, ctx->stream));
+        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
+        hipLaunchKernelGGL(wav_astep_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)w, (const double *)bbuf[1],
+                           (const double *)w, bbuf[0], sbuf[0], T, partials, C);
+        SBTV_TRY(op_resid(ctx, c, xbuf[0], acc));
+        RedJobs jb;
+        jb.add(partials, 4, nb, sums);
+        if (td) {
+            hipLaunchKernelGGL(ad_xsums_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xbuf[0], td,
+                               (const double *)nullptr, ppix, P);
+            jb.add(ppix, 3, nbp, sums + 4);
+        }
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        SBTV_HIP(ctx, hipGetLastError());
+        const double *hs;
+        SBTV_TRY(run.fetch(sums, 16, &hs));
+        run.numA += 1;
+        ctx->calls += 1;
+        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
+        if (objective) objective[0] = obj_prev;
+        if (times) times[0] = 0.0;
+        if (mses && td) mses[0] = hs[4] / (double)P;                     // :415
+    }
+    SBTV_TRY(run.start());
+    const int lag = (opts->speculate & 1) ? 1 : 0;
+    auto enqueue = [&](int outer) -> int {                               // :423
+        const int o = outer & 1, p = o ^ 1;
+        double *xn = xbuf[o];
+        SBTV_TRY(wav_synthesis(ctx, wp, sbuf[p], z, 1));                 // P(u + bu) (:434)
+        SBTV_TRY(op_solve(ctx, c, z, nullptr, c.Ys, par, acc, xn));      // :434-436
+        SBTV_TRY(wav_analysis(ctx, wp, xn, w, 1));                       // :438
+        hipLaunchKernelGGL(wav_astep_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sbuf[p],
+                           (const double *)bbuf[p], (const double *)w, bbuf[o], sbuf[o], T, partials, C);   // :440, :431
+        RedJobs jb;
+        jb.add(partials, 4, nb, sums);
+        if (td || rule2) {
+            hipLaunchKernelGGL(ad_xsums_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xn, td,
+                               rule2 ? (const double *)xbuf[p] : (const double *)nullptr, ppix, P);
+            jb.add(ppix, 3, nbp, sums + 4);
+        }
+        jb.add(acc, 1, nrb, sums + 8);
+        SBTV_TRY(reduce_jobs(ctx, jb));
+        return run.publish(outer, sums, 12, 0);
+    };
+    bool stop = false;
+    // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
+    auto process = [&](int outer) -> int {
+        const double *hsl;
+        SBTV_TRY(run.wait(outer, &hsl));
+        run.numA += 1;                                                   // :443
+        ctx->calls += 2;                                                 // invLS, A
+        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :444
+        if (objective) objective[outer] = f;
+        if (mses && td) mses[outer] = hsl[4] / (double)P;                // :446-449
+        if (distance) distance[outer - 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[1]);   // :451
+        if (times) times[outer] = run.seconds();
+        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[5], hsl[6], opts->tolA);
+        obj_prev = f;
+        return 0;
+    };
+    int last = 0;
+    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
+    return run.finish(P, last, xbuf[last & 1], x_out_dev);
+}
+
+// ------------------------------------------------------------------------------------------------
 // FISTA on the same problem (SALSA/my_fista_l1.m:5-68): min over x  0.5 ||b - B W x||^2 + tau ||x||_1.  The reference's
 // iteration k = 2..maxiters is (:34-47)
 //     y = y - (1/L) W'B'(B W y - b) ; x = soft(y, tau/L) ; t = 0.5 (1 + sqrt(1 + 4 t_old^2)) ; y = x + ((t_old-1)/t)(x - x_old)
@@ -1541,6 +1702,38 @@ int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, 
                              off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
     SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
     if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
+    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return canary_epilogue(ctx, 0);
+}
+
+int sbtv_SALSA_analysis(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
+                        const double *h, int hlen, int levels, const double *tau, const double *mu,
+                        const sbtv_salsa_opts *opts, const double *true_x, const double *x_init, double *x_out,
+                        double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
+                        int *n_outer, int flags) {
+    if (!ctx) return SBTV_ERR_BADARG;
+    SBTV_TRY(check_common(ctx, "SALSA_analysis", y, taps, opts, x_init, M, N, batch, taille, "x_init", false));   // no TV prox
+    if (!tau || !mu || !x_out) return fail(ctx, SBTV_ERR_BADARG, "SALSA_analysis: missing required argument");
+    WavPlan wp;
+    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
+    for (int b = 0; b < batch; ++b)
+        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_analysis: mu must be > 0");
+    SBTV_TRY(check_even_pixels(ctx, M, N));
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
+    const size_t P = (size_t)M * N, cnt = P * batch;
+    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
+    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
+    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
+    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
+    double *xo = nullptr;
+    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
+    const size_t mi = (size_t)opts->maxiter;
+    for (size_t b = 0; b < (size_t)batch; ++b)
+        SBTV_TRY(analysis_one(ctx, yd + b * P, M, N, taps + b * taille * taille, taille, wp, tau[b], mu[b], opts, off(td, b * P),
+                              off(xi, b * P), xo + b * P, off(objective, b * (mi + 1)), off(distance, b * mi),
+                              off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
+    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return canary_epilogue(ctx, 0);
 }

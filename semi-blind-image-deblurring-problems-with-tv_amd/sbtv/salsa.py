@@ -65,7 +65,8 @@ def SALSA_v2(y, A, tau, *varargin, ctx=None, **kw):
     if ("P" in opts) != ("PT" in opts):
         raise ValueError("If you give P you must also give PT, and vice versa.")               # :252
     if "P" in opts:
-        raise NotImplementedError("'P'/'PT' other than the identity are not supported")
+        raise NotImplementedError("'P'/'PT' other than the identity are not supported here; for the wavelet frame "
+                                  "(P = mirdwt_TI2D, PT = mrdwt_TI2D, Psi = soft) use sbtv.SALSA_analysis")
     if not opts.get("TVINITIALIZATION", 0):
         raise NotImplementedError("only the TV path ('TVINITIALIZATION', 1) runs on the GPU")
     if "PSI" in opts:

@@ -1,9 +1,10 @@
 """Host mirror of the wavelet-l1 path (SALSA/run_deblur_synthesis_L1.m): the redundant, translation-invariant wavelet frame
 `mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
 with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
-`SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), and `SAPG_wavelet`, the empirical-Bayes estimate of the
-regularisation parameter that the script runs first (the theta part of SALSA/SAPG_algorithm_1.m), and `myula_wavelet`, the
-MYULA chain at a fixed theta with the posterior mean / variance of its samples.  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
+`SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), `SALSA_analysis` (its analysis-prior form, 'P' = W and
+'PT' = W', on the image), and `SAPG_wavelet`, the empirical-Bayes estimate of the regularisation parameter that the script runs
+first (the theta part of SALSA/SAPG_algorithm_1.m), and `myula_wavelet`, the MYULA chain at a fixed theta with the posterior
+mean / variance of its samples.  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
 [a_J | LH1 HL1 HH1 | LH2 ...], or (B, M, (3J+1) N) for a batch; host and device arrays as everywhere in this package."""
 from __future__ import annotations
 
@@ -161,6 +162,57 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
         return (xw, x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(),
                 times[0, :k + 1].copy(), mses[0, :k + 1].copy() if ti else np.array([]))
     return (xw, x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
+            [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
+            [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
+
+
+def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
+    """[x, numA, numAt, objective, distance, times, mses] = SALSA_analysis(y, A, tau, 'MU', mu, 'WAVELET', h, 'LEVELS', L,
+    'AT', A.T, ...)
+
+    minimise 0.5 ||y - A x||^2 + tau ||W' x||_1 over the IMAGE x, W' the analysis operator of the redundant wavelet frame
+    (`mrdwt_TI2D`): the analysis-prior form, which SALSA_v2 solves when it is given 'P' = W and 'PT' = W' (SALSA/SALSA_v2.m:98-101,
+    389-440) with 'Psi' = soft and 'LS' = real(ifft2(fft2(r) ./ (|H|^2 + mu))); the iteration is stated in include/sbtv.h
+    (sbtv_SALSA_analysis).  The options of SALSA_wavelet; 'TRUE_X' is the true IMAGE and an array 'INITIALIZATION' a start image
+    (0: zeros, 2: A' y).  distance is ||W'x - u|| / sqrt(||W'x||^2 + ||u||^2), mses ||x - true||^2 / numel(x)."""
+    opts = _parse_varargin(varargin, _WAVELET_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("SALSA_analysis has no sharded variant")
+    levels = int(opts.get("LEVELS", 4))
+    init = opts.get("INITIALIZATION", 0)
+    if not (np.ndim(init) > 0 or L._is_torch(init)) and int(init) not in (0, 2):
+        raise L.SbtvError(-7, "Unknown 'Initialization' option")          # the random start of SALSA_v2 is not offered
+    so, yi, xinit, ti = _common(y, A, opts, ctx, 1)
+    if "MU" not in opts:
+        raise L.SbtvError(-1, "SALSA_analysis: 'MU' is required")
+    ha, hp, K = _filter(opts.get("WAVELET", daubcqf(2)))
+    B, M, N = yi.B, yi.M, yi.N
+    for other in (xinit, ti):
+        if other is not None and (other.B, other.M, other.N) != (B, M, N):
+            raise ValueError("'TRUE_X' and an array 'INITIALIZATION' must be images of the size of y")
+    Kmax = so.maxiter
+    xo = L.empty_like_images(yi)
+    objective, times, mses = np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1))
+    distance = np.zeros((B, Kmax))
+    numA, numAt, nout = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+    taps = A._cm(B)
+    keep = [L.dvec(v, B) for v in (tau, opts["MU"])]
+    tv, mu = (k[1] for k in keep)
+    ctx.check(ctx.lib.sbtv_SALSA_analysis(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, tv, mu, C.byref(so),
+                                          ti.ptr if ti else None, xinit.ptr if xinit else None, xo.ptr, _vp(objective),
+                                          _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
+              yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    x = L.images_result(xo, sq)
+    n = np.array(nout[:])
+    if sq or B == 1:
+        k = int(n[0])
+        return (x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(), times[0, :k + 1].copy(),
+                mses[0, :k + 1].copy() if ti else np.array([]))
+    return (x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
             [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
             [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
 
