@@ -10,7 +10,8 @@
 // sums it reads with the iteration's scalars and, should the rule ever fire before the last step, repeats the solve with
 // exact launches), and the host evaluates the outer stop rule one iteration late while the next iteration already runs
 // (x is double-buffered, so the result of the stopping iteration is intact).  The images of a batch are solved one after
-// another.
+// another.  What a pipelined single-image solve carries (AdmmRun) and the helpers of the element-wise kernels are in
+// admm_run.inc, shared with the wavelet-l1 solvers of wavelet_deconv.hip, which run the same loop without the TV prox.
 #include <chrono>
 #include <cmath>
 
@@ -22,44 +23,7 @@ namespace sbtv {
 
 namespace {
 
-constexpr int AB = 256;
-
-__device__ __forceinline__ double ad_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// block-reduce NQ running sums and store them as partials[q * gridDim.x + blockIdx.x]
-template <int NQ>
-__device__ __forceinline__ void ad_store_partials(double (&acc)[NQ], double *__restrict__ partials) {
-    __shared__ double red[NQ * 4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NQ; ++c) {
-        const double a = ad_wave_sum(acc[c]);
-        if (lane == 0) red[c * 4 + w] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NQ; ++c)
-            partials[(size_t)c * gridDim.x + blockIdx.x] = (red[c * 4] + red[c * 4 + 1]) + (red[c * 4 + 2] + red[c * 4 + 3]);
-    }
-}
-
-#define AD_LOOP(q, P) for (size_t q = (size_t)blockIdx.x * AB + threadIdx.x; q < (P) / 2; q += (size_t)gridDim.x * AB)
-#define AD_LD(p, q) (*reinterpret_cast<const double2 *>((p) + 2 * (q)))
-#define AD_ST(p, q, v) (*reinterpret_cast<double2 *>((p) + 2 * (q)) = (v))
-
-// g = x - b
-__global__ __launch_bounds__(AB) void ad_sub_kernel(const double *__restrict__ x, const double *__restrict__ b,
-                                                     double *__restrict__ g, size_t P) {
-    AD_LOOP(q, P) {
-        const double2 xv = AD_LD(x, q), bv = AD_LD(b, q);
-        AD_ST(g, q, make_double2(xv.x - bv.x, xv.y - bv.y));
-    }
-}
+#include "admm_run.inc"   // AB, ad_store_partials, AD_LOOP / AD_LD / AD_ST, ad_sub_kernel, ad_blocks, admm_common, upload_par, AdmmRun
 
 // ---- C-SALSA -----------------------------------------------------------------------------------
 // w = mu2 * (y + v + bv)                                                   (CSALSA_v2.m:467)
@@ -344,180 +308,6 @@ __global__ __launch_bounds__(AB) void masked_post_kernel(const double *__restric
     ad_store_partials<NQ>(acc, partials);
 }
 
-// ---- wavelet-l1 SALSA (wavelet_one) -------------------------------------------------------------------------------
-// l1 norm of the start xw and its distance to the true coefficients: partials [2][nb]
-__global__ __launch_bounds__(AB) void wav_init_kernel(const double *__restrict__ xw, const double *__restrict__ tru,
-                                                       double *__restrict__ partials, size_t C) {
-    double acc[2] = {0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 v = AD_LD(xw, q);
-        acc[0] += fabs(v.x) + fabs(v.y);
-        if (tru) {
-            const double2 t = AD_LD(tru, q);
-            const double m0 = v.x - t.x, m1 = v.y - t.y;
-            acc[1] += m0 * m0 + m1 * m1;
-        }
-    }
-    ad_store_partials<2>(acc, partials);
-}
-
-// The prox of an outer iteration on the state (s, we) of the previous one, xw = s + we and bu = -we:
-//   u = soft(xw - bu, T) = soft(s + 2 we, T) ; s' = u + bu = u - we ; partials [2][nb]: |u|, u^2
-__global__ __launch_bounds__(AB) void wav_prox_kernel(const double *__restrict__ s, const double *__restrict__ we,
-                                                       double *__restrict__ sn, double T, double *__restrict__ partials,
-                                                       size_t C) {
-    double acc[2] = {0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 sv = AD_LD(s, q), wv = AD_LD(we, q);
-        const double u0 = wav_soft(sv.x + 2.0 * wv.x, T), u1 = wav_soft(sv.y + 2.0 * wv.y, T);
-        AD_ST(sn, q, make_double2(u0 - wv.x, u1 - wv.y));
-        acc[0] += fabs(u0) + fabs(u1);
-        acc[1] += u0 * u0 + u1 * u1;
-    }
-    ad_store_partials<2>(acc, partials);
-}
-
-// After the analysis we' = W'(xi - z) of an outer iteration: xw' = s' + we', u = s' + we (we: the previous iteration's), so
-// xw' - u = we' - we.  partials [4][nb]: (xw'-u)^2, xw'^2, (xw'-true)^2, (xw'-xw)^2 with xw = s + we (sp == null: not summed)
-__global__ __launch_bounds__(AB) void wav_post_kernel(const double *__restrict__ sn, const double *__restrict__ wn,
-                                                       const double *__restrict__ we, const double *__restrict__ sp,
-                                                       const double *__restrict__ tru, double *__restrict__ partials,
-                                                       size_t C) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 sv = AD_LD(sn, q), wv = AD_LD(wn, q), wo = AD_LD(we, q);
-        const double x0 = sv.x + wv.x, x1 = sv.y + wv.y;
-        const double d0 = wv.x - wo.x, d1 = wv.y - wo.y;
-        acc[0] += d0 * d0 + d1 * d1;
-        acc[1] += x0 * x0 + x1 * x1;
-        if (tru) {
-            const double2 t = AD_LD(tru, q);
-            const double m0 = x0 - t.x, m1 = x1 - t.y;
-            acc[2] += m0 * m0 + m1 * m1;
-        }
-        if (sp) {
-            const double2 so = AD_LD(sp, q);
-            const double m0 = x0 - (so.x + wo.x), m1 = x1 - (so.y + wo.y);
-            acc[3] += m0 * m0 + m1 * m1;
-        }
-    }
-    ad_store_partials<4>(acc, partials);
-}
-
-// xw = s + we
-__global__ __launch_bounds__(AB) void wav_sum_kernel(const double *__restrict__ s, const double *__restrict__ we,
-                                                      double *__restrict__ xw, size_t C) {
-    AD_LOOP(q, C) {
-        const double2 sv = AD_LD(s, q), wv = AD_LD(we, q);
-        AD_ST(xw, q, make_double2(sv.x + wv.x, sv.y + wv.y));
-    }
-}
-
-// ---- analysis-prior wavelet SALSA (analysis_one) ------------------------------------------------------------------
-// The one coefficient pass of an outer iteration k, after the analysis w = W'x_k, on the state (s, bu) = (u_k + bu_{k-1}, bu_{k-1}):
-//   u = s - bu (exactly zero where the threshold cut it: there s == bu bit for bit) ; bu' = bu + (u - w)    (SALSA_v2.m:440)
-//   u' = soft(w - bu', T) ; s' = u' + bu'                                                                  (:431 of k + 1)
-//   partials [4][nb]: |u|, u^2, (w-u)^2, w^2
-// The start is the same pass with s = w_0 and bu = 0.
-__global__ __launch_bounds__(AB) void wav_astep_kernel(const double *__restrict__ s, const double *__restrict__ bu,
-                                                        const double *__restrict__ w, double *__restrict__ bun,
-                                                        double *__restrict__ sn, double T, double *__restrict__ partials,
-                                                        size_t C) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 sv = AD_LD(s, q), bv = AD_LD(bu, q), wv = AD_LD(w, q);
-        const double u0 = sv.x - bv.x, u1 = sv.y - bv.y;
-        const double d0 = wv.x - u0, d1 = wv.y - u1;
-        const double b0 = bv.x + (u0 - wv.x), b1 = bv.y + (u1 - wv.y);
-        AD_ST(bun, q, make_double2(b0, b1));
-        AD_ST(sn, q, make_double2(wav_soft(wv.x - b0, T) + b0, wav_soft(wv.y - b1, T) + b1));
-        acc[0] += fabs(u0) + fabs(u1);
-        acc[1] += u0 * u0 + u1 * u1;
-        acc[2] += d0 * d0 + d1 * d1;
-        acc[3] += wv.x * wv.x + wv.y * wv.y;
-    }
-    ad_store_partials<4>(acc, partials);
-}
-
-// the image-domain sums of an outer iteration: partials [3][nb]: (x-true)^2, (x-xprev)^2, x^2 (tru / xprev null: not summed)
-__global__ __launch_bounds__(AB) void ad_xsums_kernel(const double *__restrict__ x, const double *__restrict__ tru,
-                                                       const double *__restrict__ xprev, double *__restrict__ partials,
-                                                       size_t P) {
-    double acc[3] = {0.0, 0.0, 0.0};
-    AD_LOOP(q, P) {
-        const double2 xv = AD_LD(x, q);
-        if (tru) {
-            const double2 tv = AD_LD(tru, q);
-            const double m0 = xv.x - tv.x, m1 = xv.y - tv.y;
-            acc[0] += m0 * m0 + m1 * m1;
-        }
-        if (xprev) {
-            const double2 xo = AD_LD(xprev, q);
-            const double m0 = xv.x - xo.x, m1 = xv.y - xo.y;
-            acc[1] += m0 * m0 + m1 * m1;
-        }
-        acc[2] += xv.x * xv.x + xv.y * xv.y;
-    }
-    ad_store_partials<3>(acc, partials);
-}
-
-// ---- wavelet-l1 FISTA (fista_l1_one) ------------------------------------------------------------------------------
-// zy = zx + c (zx - zxo): the image W y of the momentum point y = x + c (x - xo), by linearity of W
-__global__ __launch_bounds__(AB) void fl1_momentum_kernel(const double *__restrict__ zx, const double *__restrict__ zxo,
-                                                           double c, double *__restrict__ zy, size_t P) {
-    AD_LOOP(q, P) {
-        const double2 a = AD_LD(zx, q), b = AD_LD(zxo, q);
-        AD_ST(zy, q, make_double2(a.x + c * (a.x - b.x), a.y + c * (a.y - b.y)));
-    }
-}
-
-// The step of an iteration (my_fista_l1.m:38-39,42 of the iteration before): y = x + c (x - xo) ; xn = soft(y - (1/L) g, T),
-// T = tau / L, written over xo.  partials [3 or 4][nb]: |xn|, xn^2, (xn - x)^2 and, TRU, (xn - true)^2
-template <bool TRU>
-__global__ __launch_bounds__(AB) void fl1_step_kernel(const double *__restrict__ x, double *__restrict__ xo,
-                                                       const double *__restrict__ g, const double *__restrict__ tru, double c,
-                                                       double invL, double T, double *__restrict__ partials, size_t C) {
-    constexpr int NQ = TRU ? 4 : 3;
-    double acc[NQ];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) acc[i] = 0.0;
-    AD_LOOP(q, C) {
-        const double2 xv = AD_LD(x, q), ov = AD_LD(xo, q), gv = AD_LD(g, q);
-        const double y0 = xv.x + c * (xv.x - ov.x), y1 = xv.y + c * (xv.y - ov.y);
-        const double n0 = wav_soft(y0 - invL * gv.x, T), n1 = wav_soft(y1 - invL * gv.y, T);
-        AD_ST(xo, q, make_double2(n0, n1));
-        acc[0] += fabs(n0) + fabs(n1);
-        acc[1] += n0 * n0 + n1 * n1;
-        const double d0 = n0 - xv.x, d1 = n1 - xv.y;
-        acc[2] += d0 * d0 + d1 * d1;
-        if constexpr (TRU) {
-            const double2 t = AD_LD(tru, q);
-            const double m0 = n0 - t.x, m1 = n1 - t.y;
-            acc[3] += m0 * m0 + m1 * m1;
-        }
-    }
-    ad_store_partials<NQ>(acc, partials);
-}
-
-inline int ad_blocks(size_t P) {
-    size_t nb = (P / 2 + AB - 1) / AB;
-    if (nb > 1024) nb = 1024;
-    return nb < 1 ? 1 : (int)nb;
-}
-
-// everything one single-image solve shares: the operator layer "admm" with the spectra of the PSF and (yd given) of y
-int admm_common(sbtv_ctx *ctx, int M, int N, const double *taps, int taille, const double *yd, BlurOp *c) {
-    SBTV_TRY(check_even_pixels(ctx, M, N));
-    SBTV_TRY(op_open(ctx, "admm", M, N, 1, "Y", c));
-    double *taps_d = nullptr;
-    SBTV_TRY(ws_get_t(ctx, "admm.taps", (size_t)taille * taille, &taps_d));
-    SBTV_HIP(ctx, hipMemcpyAsync(taps_d, taps, sizeof(double) * taille * taille, hipMemcpyHostToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SBTV_TRY(psf_spectrum(ctx, c->fp, taps_d, taille, c->Hs));
-    if (yd) SBTV_TRY(op_spectrum(ctx, c->fp, yd, nullptr, c->S, c->Ys));
-    return 0;
-}
-
 // C-SALSA: the constraint split (v, bv) as ONE spectrum and a scalar (default) or as images (SBTV_CSALSA_SPECTRAL=0)
 inline bool csalsa_spectral_wanted() {
     static const bool on = [] {
@@ -525,13 +315,6 @@ inline bool csalsa_spectral_wanted() {
         return !(e && e[0] == '0');
     }();
     return on;
-}
-
-// the four doubles of "admm.par" (each driver says what they are), on the device before anything is enqueued that reads them
-int upload_par(sbtv_ctx *ctx, double *par, const double (&h)[4]) {
-    SBTV_HIP(ctx, hipMemcpyAsync(par, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
 }
 
 // The warm-started TV prox of an outer iteration: a plan (of one image, or of CoRAL's two), its threshold(s) `lam` on the
@@ -568,99 +351,6 @@ struct AdmmProx {
     }
     // the host's rule on the step sums of an optimistic prox (SOLVE_RESTART_EXACT: it fired early)
     int check(sbtv_ctx *ctx, const double *stepsums) { return spec_stop_rule(ctx, pp, stepsums, K, tol); }
-};
-
-// What a solve carries through its pipelined loop.  Per-iteration scalars travel through two pinned slots; an event per
-// slot tells the host (which runs one iteration ahead) when the slot of an iteration holds its scalars.  Beside them: the
-// clock of `times`, the operator counts, the Chambolle iterations of sbtv_last_timing.
-struct AdmmRun {
-    static constexpr int NSUM = 94;                // doubles per slot, then the iteration counts of up to two exact proxes
-    sbtv_ctx *ctx = nullptr;
-    double *hs[2] = {nullptr, nullptr};            // the two slots (pinned): the sums ...
-    int *khs[2] = {nullptr, nullptr};              // ... and the counts, at [0] and [2]
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    long long opt_iters[2] = {0, 0};
-    std::chrono::steady_clock::time_point t0;
-    int numA = 0, numAt = 0;
-    long long prox_iters = 0;
-    int *numA_out = nullptr, *numAt_out = nullptr, *n_outer_out = nullptr;
-
-    ~AdmmRun() {
-        for (auto e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    int open(sbtv_ctx *c, int *numA_o, int *numAt_o, int *n_outer_o) {
-        ctx = c;
-        numA_out = numA_o;
-        numAt_out = numAt_o;
-        n_outer_out = n_outer_o;
-        PinnedLayout lay;
-        PinnedField<double> fs[2];
-        PinnedField<int> fk[2];
-        for (int s = 0; s < 2; ++s) {
-            fs[s] = lay.add<double>(NSUM);
-            fk[s] = lay.add<int>(4);
-        }
-        void *pz = nullptr;
-        SBTV_TRY(pinned_get(ctx, lay.bytes(), &pz));
-        for (int s = 0; s < 2; ++s) {
-            hs[s] = fs[s].at(pz);
-            khs[s] = fk[s].at(pz);
-        }
-        for (auto &e : ev) SBTV_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return 0;
-    }
-    // the loop begins: sbtv_last_timing and `times` count from here
-    int start() {
-        t0 = std::chrono::steady_clock::now();
-        SBTV_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        return 0;
-    }
-    // before the loop: the first n doubles of `sums`, read back through slot 0
-    int fetch(const double *sums, int n, const double **h) {
-        SBTV_HIP(ctx, hipMemcpyAsync(hs[0], sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        *h = hs[0];
-        return 0;
-    }
-    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-    // end of enqueue(outer): the first n doubles of `sums` into the iteration's slot.  Its Chambolle iterations are `iters` if
-    // its proxes were optimistic; exact ones hand the control blocks that count theirs (k0, k1: device)
-    int publish(int outer, const double *sums, int n, long long iters, const ProxCtrl *k0 = nullptr,
-                const ProxCtrl *k1 = nullptr) {
-        double *hsl = hs[outer & 1];
-        int *kh = khs[outer & 1];
-        kh[0] = kh[2] = 0;
-        opt_iters[outer & 1] = iters;
-        SBTV_HIP(ctx, hipGetLastError());
-        SBTV_HIP(ctx, hipMemcpyAsync(hsl, sums, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (k0) SBTV_HIP(ctx, hipMemcpyAsync(kh, &k0->k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        if (k1) SBTV_HIP(ctx, hipMemcpyAsync(kh + 2, &k1->k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SBTV_HIP(ctx, hipEventRecord(ev[outer & 1], ctx->stream));
-        return 0;
-    }
-    // head of process(outer): waits for the iteration's slot, books its Chambolle iterations
-    int wait(int outer, const double **hsl) {
-        *hsl = hs[outer & 1];
-        SBTV_HIP(ctx, hipEventSynchronize(ev[outer & 1]));
-        const int *kh = khs[outer & 1];
-        prox_iters += opt_iters[outer & 1] + kh[0] + kh[2];
-        return 0;
-    }
-    // after the loop: its device time (sbtv_last_timing), the result x (null: the caller fetches its own), the counters
-    int finish(size_t P, int last, const double *x, double *x_out) {
-        SBTV_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-        SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        SBTV_TRY(loop_timing(ctx, 0.0, prox_iters, 1, P));
-        if (x) {
-            SBTV_HIP(ctx, hipMemcpyAsync(x_out, x, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-            SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        if (numA_out) *numA_out = numA;
-        if (numAt_out) *numAt_out = numAt;
-        if (n_outer_out) *n_outer_out = last;
-        return 0;
-    }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1187,362 +877,6 @@ int masked_one(sbtv_ctx *ctx, const double *yd, const double *md, int M, int N, 
     return run.finish(P, last, xbuf[last & 1], x_out_dev);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Wavelet-l1 deconvolution in the synthesis form (SALSA/run_deblur_synthesis_L1.m:160-180):
-//     min over xw   0.5 ||y - B W xw||^2 + tau ||xw||_1,
-// W the Parseval frame of wavelet.hip (W W' = I), solved as SALSA_v2.m:389-494 does with Psi = soft, Phi = l1, A = B W,
-// AT = W' B' and invLS(r) = (r - W' F W r) / mu, F = |H|^2 / (|H|^2 + mu) in the Fourier domain.  With W W' = I one outer
-// iteration of that is exactly
-//     u = soft(xw - bu, tau / mu) ; s = u + bu ; z = W s ;
-//     X = (conj(H) fft2(y) + mu fft2(z)) / (|H|^2 + mu) ; xi = real(ifft2(X))      (the row pass OP_SALSA on z)
-//     we = W'(xi - z) ; xw = s + we ; bu = -we
-// with the image estimate W xw = xi and ||y - B xi||^2 from the row pass's Parseval sum.  The coefficient state is (s, we):
-// the next prox input is s + 2 we.  Both and xi are double-buffered, so the result of the stopping iteration is intact when
-// the host evaluates the stop rule one iteration late.  Per outer iteration: the prox pass, one synthesis (J launches), the
-// FFT triple, the difference, one analysis (J launches), the sums pass and one reduction launch.
-int wavelet_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
-                double mu, const sbtv_salsa_opts *opts, const double *td, const double *xwi, double *xw_out_dev,
-                double *x_out_dev, double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
-                int *n_outer) {
-    BlurOp c;
-    SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
-    const size_t P = c.P, C = P * wp.bands();
-    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
-    double *sbuf[2], *wbuf[2], *xibuf[2], *z, *d, *par, *partials, *sums, *acc;
-    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &sbuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &sbuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &wbuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "wav.we1", C, &wbuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &xibuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &xibuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &z));
-    SBTV_TRY(ws_get_t(ctx, "admm.g", P, &d));
-    SBTV_TRY(ws_get_t(ctx, "admm.par", (size_t)4, &par));               // mu
-    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..1] prox sums, [2..5] post sums, nb each
-    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0] |u|, [1] u^2, [2..5] post sums, [8] resid2
-    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
-    AdmmRun run;
-    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
-    SBTV_TRY(upload_par(ctx, par, {mu, 0.0, 0.0, 0.0}));
-    const double T = tau / mu;                                           // :394
-    const int maxiter = opts->maxiter;
-    run.numAt = 1;                                                       // ATy (:288)
-    ctx->calls += 2;                                                     // AT(y), invLS(ATy)
-    // the start xw as the state (s, we) = (xw, 0): bu = -we = 0 (:367-393)
-    double *s0 = sbuf[0];
-    if (opts->initialization == 0) {
-        SBTV_HIP(ctx, hipMemsetAsync(s0, 0, sizeof(double) * C, ctx->stream));
-        ctx->calls += 1;
-    } else if (opts->initialization == 2) {                              // xw = W' B' y
-        SBTV_TRY(op_apply(ctx, c, OP_MUL_HC, yd, d));
-        SBTV_TRY(wav_analysis(ctx, wp, d, s0, 1));
-    } else {
-        SBTV_HIP(ctx, hipMemcpyAsync(s0, xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    SBTV_HIP(ctx, hipMemsetAsync(wbuf[0], 0, sizeof(double) * C, ctx->stream));
-    // initial objective (:399-401): resid = y - B W xw
-    double obj_prev;
-    {
-        SBTV_TRY(wav_synthesis(ctx, wp, s0, xibuf[0], 1));
-        SBTV_TRY(op_resid(ctx, c, xibuf[0], acc));
-        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
-        hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)s0, td, partials, C);
-        RedJobs jb;
-        jb.add(partials, 2, nb, sums);
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        SBTV_HIP(ctx, hipGetLastError());
-        const double *hs;
-        SBTV_TRY(run.fetch(sums, 16, &hs));
-        run.numA += 1;
-        ctx->calls += 1;
-        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
-        if (objective) objective[0] = obj_prev;
-        if (times) times[0] = 0.0;
-        if (mses && td) mses[0] = hs[1] / (double)C;                     // :414
-    }
-    SBTV_TRY(run.start());
-    const int lag = (opts->speculate & 1) ? 1 : 0;
-    auto enqueue = [&](int outer) -> int {                               // :423
-        const int o = outer & 1, p = o ^ 1;
-        double *sn = sbuf[o], *wn = wbuf[o], *xi = xibuf[o];
-        const double *sp = sbuf[p], *we = wbuf[p];
-        hipLaunchKernelGGL(wav_prox_kernel, dim3(nb), dim3(AB), 0, ctx->stream, sp, we, sn, T, partials, C);      // :432
-        SBTV_TRY(wav_synthesis(ctx, wp, sn, z, 1));
-        SBTV_TRY(op_solve(ctx, c, z, nullptr, c.Ys, par, acc, xi));    // :434-436
-        hipLaunchKernelGGL(ad_sub_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xi, (const double *)z, d, P);
-        SBTV_TRY(wav_analysis(ctx, wp, d, wn, 1));
-        hipLaunchKernelGGL(wav_post_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sn, (const double *)wn, we,
-                           (opts->stopcriterion == 2) ? sp : (const double *)nullptr, td, partials + (size_t)2 * nb, C);
-        RedJobs jb;
-        jb.add(partials, 6, nb, sums);
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        return run.publish(outer, sums, 12, 0);
-    };
-    bool stop = false;
-    // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
-    auto process = [&](int outer) -> int {
-        const double *hsl;
-        SBTV_TRY(run.wait(outer, &hsl));
-        run.numA += 1;                                                   // :443
-        ctx->calls += 2;                                                 // invLS, A
-        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :444
-        if (objective) objective[outer] = f;
-        if (mses && td) mses[outer] = hsl[4] / (double)C;                // :446-449
-        if (distance) distance[outer - 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[1]);   // :451
-        if (times) times[outer] = run.seconds();
-        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[5], hsl[3], opts->tolA);
-        obj_prev = f;
-        return 0;
-    };
-    int last = 0;
-    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_TRY(run.finish(P, last, nullptr, nullptr));                     // the result: xw = s + we, and the image xi
-    hipLaunchKernelGGL(wav_sum_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sbuf[last & 1],
-                       (const double *)wbuf[last & 1], xw_out_dev, C);
-    SBTV_HIP(ctx, hipGetLastError());
-    if (x_out_dev)
-        SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, xibuf[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Wavelet-l1 deconvolution in the analysis form, the 'P' / 'PT' mode of SALSA_v2.m (:98-101, 198-203):
-//     min over the image x   0.5 ||y - B x||^2 + tau ||W' x||_1,
-// solved as SALSA_v2.m:389-494 does with Psi = soft, Phi = l1, A = B, AT = B', PT = W', P = W and invLS(r) =
-// real(ifft2(fft2(r) ./ (|H|^2 + mu))), the exact x-minimiser because W W' = I.  One outer iteration k on the coefficient
-// state (s, bu), s = u + bu:
-//     z = W s_k ;  X = (conj(H) fft2(y) + mu fft2(z)) / (|H|^2 + mu) ;  x_k = real(ifft2(X))      (the row pass OP_SALSA on z)
-//     w_k = W' x_k ;  the step pass (wav_astep_kernel): u_k = s_k - bu_{k-1}, its sums, bu_k, s_{k+1}
-// with ||y - B x_k||^2 from the row pass's Parseval sum and the image-domain sums of x_k from a pixel pass, launched only when
-// 'TRUE_X' or stop rule 2 ask for them.  s, bu and x are double-buffered, so the result of the stopping iteration is intact
-// when the host evaluates the stop rule one iteration late.  Per outer iteration: one synthesis (J launches), the FFT triple,
-// one analysis (J launches), the step pass, the pixel pass and one reduction launch.
-int analysis_one(sbtv_ctx *ctx, const double *yd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
-                 double mu, const sbtv_salsa_opts *opts, const double *td, const double *xi, double *x_out_dev,
-                 double *objective, double *distance, double *times, double *mses, int *numA, int *numAt, int *n_outer) {
-    BlurOp c;
-    SBTV_TRY(admm_common(ctx, M, N, taps, taille, yd, &c));
-    const size_t P = c.P, C = P * wp.bands();
-    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
-    double *sbuf[2], *bbuf[2], *xbuf[2], *w, *z, *par, *partials, *sums, *acc;
-    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &sbuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &sbuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &bbuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "wav.we1", C, &bbuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "wav.w", C, &w));
-    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &xbuf[0]));
-    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &xbuf[1]));
-    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &z));
-    SBTV_TRY(ws_get_t(ctx, "admm.par", (size_t)4, &par));               // mu
-    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..3] step sums, nb each, then [0..2] pixel sums, nbp each
-    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0..3] step sums, [4..6] pixel sums, [8] resid2
-    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
-    double *ppix = partials + (size_t)4 * nb;
-    AdmmRun run;
-    SBTV_TRY(run.open(ctx, numA, numAt, n_outer));
-    SBTV_TRY(upload_par(ctx, par, {mu, 0.0, 0.0, 0.0}));
-    const double T = tau / mu;                                           // :394
-    const int maxiter = opts->maxiter;
-    const bool rule2 = opts->stopcriterion == 2;
-    run.numAt = 1;                                                       // ATy (:288)
-    ctx->calls += 2;                                                     // AT(y), invLS(ATy)
-    if (opts->initialization == 0) ctx->calls += 1;                      // AT(zeros) (:369)
-    SBTV_TRY(op_init_x(ctx, c, opts->initialization, yd, xi, xbuf[0]));  // :367-381
-    // PTx = W'x ; u = PTx ; bu = 0 (:389-393) and the initial objective (:399-401): the step pass on (s, bu) = (PTx, 0)
-    double obj_prev;
-    {
-        SBTV_TRY(wav_analysis(ctx, wp, xbuf[0], w, 1));
-        SBTV_HIP(ctx, hipMemsetAsync(bbuf[1], 0, sizeof(double) * C, ctx->stream));
-        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
-        hipLaunchKernelGGL(wav_astep_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)w, (const double *)bbuf[1],
-                           (const double *)w, bbuf[0], sbuf[0], T, partials, C);
-        SBTV_TRY(op_resid(ctx, c, xbuf[0], acc));
-        RedJobs jb;
-        jb.add(partials, 4, nb, sums);
-        if (td) {
-            hipLaunchKernelGGL(ad_xsums_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xbuf[0], td,
-                               (const double *)nullptr, ppix, P);
-            jb.add(ppix, 3, nbp, sums + 4);
-        }
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        SBTV_HIP(ctx, hipGetLastError());
-        const double *hs;
-        SBTV_TRY(run.fetch(sums, 16, &hs));
-        run.numA += 1;
-        ctx->calls += 1;
-        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
-        if (objective) objective[0] = obj_prev;
-        if (times) times[0] = 0.0;
-        if (mses && td) mses[0] = hs[4] / (double)P;                     // :415
-    }
-    SBTV_TRY(run.start());
-    const int lag = (opts->speculate & 1) ? 1 : 0;
-    auto enqueue = [&](int outer) -> int {                               // :423
-        const int o = outer & 1, p = o ^ 1;
-        double *xn = xbuf[o];
-        SBTV_TRY(wav_synthesis(ctx, wp, sbuf[p], z, 1));                 // P(u + bu) (:434)
-        SBTV_TRY(op_solve(ctx, c, z, nullptr, c.Ys, par, acc, xn));      // :434-436
-        SBTV_TRY(wav_analysis(ctx, wp, xn, w, 1));                       // :438
-        hipLaunchKernelGGL(wav_astep_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)sbuf[p],
-                           (const double *)bbuf[p], (const double *)w, bbuf[o], sbuf[o], T, partials, C);   // :440, :431
-        RedJobs jb;
-        jb.add(partials, 4, nb, sums);
-        if (td || rule2) {
-            hipLaunchKernelGGL(ad_xsums_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)xn, td,
-                               rule2 ? (const double *)xbuf[p] : (const double *)nullptr, ppix, P);
-            jb.add(ppix, 3, nbp, sums + 4);
-        }
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        return run.publish(outer, sums, 12, 0);
-    };
-    bool stop = false;
-    // host side of iteration `outer`: traces and the stop rule of SALSA_v2.m:442-482
-    auto process = [&](int outer) -> int {
-        const double *hsl;
-        SBTV_TRY(run.wait(outer, &hsl));
-        run.numA += 1;                                                   // :443
-        ctx->calls += 2;                                                 // invLS, A
-        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :444
-        if (objective) objective[outer] = f;
-        if (mses && td) mses[outer] = hsl[4] / (double)P;                // :446-449
-        if (distance) distance[outer - 1] = sqrt(hsl[2]) / sqrt(hsl[3] + hsl[1]);   // :451
-        if (times) times[outer] = run.seconds();
-        stop = salsa_stop(opts->stopcriterion, outer, f, obj_prev, hsl[5], hsl[6], opts->tolA);
-        obj_prev = f;
-        return 0;
-    };
-    int last = 0;
-    SBTV_TRY(pipelined_loop(ctx, &last, maxiter, lag, false, enqueue, process, [&] { return !stop; }));
-    return run.finish(P, last, xbuf[last & 1], x_out_dev);
-}
-
-// ------------------------------------------------------------------------------------------------
-// FISTA on the same problem (SALSA/my_fista_l1.m:5-68): min over x  0.5 ||b - B W x||^2 + tau ||x||_1.  The reference's
-// iteration k = 2..maxiters is (:34-47)
-//     y = y - (1/L) W'B'(B W y - b) ; x = soft(y, tau/L) ; t = 0.5 (1 + sqrt(1 + 4 t_old^2)) ; y = x + ((t_old-1)/t)(x - x_old)
-//     objective(k) = 0.5 ||B W x - b||^2 + tau sum|x|
-// What runs keeps x_{k-1}, x_{k-2} and their images zx = W x in two buffers each and never stores y: with c the momentum
-// factor of the iteration before (0 for k = 2; t and c depend on no data, the host knows them when it enqueues)
-//     zy = zx_{k-1} + c (zx_{k-1} - zx_{k-2})              (= W y by linearity; fl1_momentum_kernel)
-//     g  = W' B'(B zy - b)                                  (op_gradf, wav_analysis)
-//     x_k = soft((x_{k-1} + c (x_{k-1} - x_{k-2})) - (1/L) g, tau/L)   over x_{k-2}, with its sums (fl1_step_kernel)
-//     zx_k = W x_k over zx_{k-2} ; ||B zx_k - b||^2         (wav_synthesis, op_resid)
-// one synthesis per iteration where the reference has two (W y inside A(y), W x for the objective).  The host books the
-// traces and the stop rule one iteration late (lag 1); iteration k + 1 writes the buffers of x_{k-1}, so x_k and zx_k are
-// intact when the rule of iteration k is seen.
-int fista_l1_one(sbtv_ctx *ctx, const double *bd, int M, int N, const double *taps, int taille, const WavPlan &wp, double tau,
-                 double L, int stopcriterion, double tolerance, int maxiters, int lag, const double *td, const double *xwi,
-                 double *xw_out_dev, double *x_out_dev, double *objective, double *times, double *mses, int *n_iter) {
-    BlurOp c;
-    SBTV_TRY(admm_common(ctx, M, N, taps, taille, bd, &c));
-    const size_t P = c.P, C = P * wp.bands();
-    const int nb = ad_blocks(C), nbp = ad_blocks(P), nrb = fft_rows_blocks(c.fp);
-    double *xb[2], *zb[2], *zy, *gi, *g, *partials, *sums, *acc;
-    SBTV_TRY(ws_get_t(ctx, "wav.s0", C, &xb[0]));
-    SBTV_TRY(ws_get_t(ctx, "wav.s1", C, &xb[1]));
-    SBTV_TRY(ws_get_t(ctx, "wav.we0", C, &g));
-    SBTV_TRY(ws_get_t(ctx, "admm.x0", P, &zb[0]));
-    SBTV_TRY(ws_get_t(ctx, "admm.x1", P, &zb[1]));
-    SBTV_TRY(ws_get_t(ctx, "admm.u", P, &zy));
-    SBTV_TRY(ws_get_t(ctx, "admm.g", P, &gi));
-    SBTV_TRY(ws_get_t(ctx, "admm.partials", (size_t)12 * 1024, &partials));   // [0..3] step sums, nb each
-    SBTV_TRY(ws_get_t(ctx, "admm.sums", (size_t)96, &sums));            // [0] |x|, [1] x^2, [2] (x-xprev)^2, [3] (x-true)^2, [8] resid2
-    SBTV_TRY(ws_get_t(ctx, "admm.acc", (size_t)3 * nrb, &acc));
-    AdmmRun run;
-    SBTV_TRY(run.open(ctx, nullptr, nullptr, n_iter));
-    const double T = tau / L, invL = 1.0 / L;                            // :38-39
-    const int nq = td ? 4 : 3;
-    ctx->calls += 2;                                                     // AT(b) (:20), A(x) (:28)
-    // iterate 1, the start (:20-22; x = y = xw_init): in the buffers of parity 1, and as "x_0" in those of parity 0, where
-    // c = 0 multiplies a zero difference
-    if (xwi) {
-        SBTV_HIP(ctx, hipMemcpyAsync(xb[1], xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
-        SBTV_HIP(ctx, hipMemcpyAsync(xb[0], xwi, sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-        SBTV_HIP(ctx, hipMemsetAsync(xb[1], 0, sizeof(double) * C, ctx->stream));
-        SBTV_HIP(ctx, hipMemsetAsync(xb[0], 0, sizeof(double) * C, ctx->stream));
-    }
-    double obj_prev;
-    {
-        SBTV_TRY(wav_synthesis(ctx, wp, xb[1], zb[1], 1));               // :27-29
-        SBTV_HIP(ctx, hipMemcpyAsync(zb[0], zb[1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-        SBTV_TRY(op_resid(ctx, c, zb[1], acc));
-        SBTV_HIP(ctx, hipMemsetAsync(sums, 0, sizeof(double) * 16, ctx->stream));
-        hipLaunchKernelGGL(wav_init_kernel, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[1], td, partials, C);
-        RedJobs jb;
-        jb.add(partials, 2, nb, sums);
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        SBTV_HIP(ctx, hipGetLastError());
-        const double *hs;
-        SBTV_TRY(run.fetch(sums, 16, &hs));
-        obj_prev = 0.5 * (hs[8] * c.parseval) + tau * hs[0];
-        if (objective) objective[0] = obj_prev;
-        if (times) times[0] = 0.0;
-        if (mses && td) mses[0] = hs[1] / (double)C;                     // :29
-    }
-    SBTV_TRY(run.start());
-    double t_enq = 1.0, c_enq = 0.0;                                     // t and the momentum factor as the next enqueue sees them
-    auto enqueue = [&](int k) -> int {                                   // :34
-        const int o = k & 1, p = o ^ 1;
-        const double cm = c_enq;
-        hipLaunchKernelGGL(fl1_momentum_kernel, dim3(nbp), dim3(AB), 0, ctx->stream, (const double *)zb[p],
-                           (const double *)zb[o], cm, zy, P);
-        SBTV_TRY(op_gradf(ctx, c, zy, acc, gi));                         // :38; its residual sum (of the momentum point) is not used
-        SBTV_TRY(wav_analysis(ctx, wp, gi, g, 1));
-        if (td)
-            hipLaunchKernelGGL(fl1_step_kernel<true>, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[p], xb[o],
-                               (const double *)g, td, cm, invL, T, partials, C);
-        else
-            hipLaunchKernelGGL(fl1_step_kernel<false>, dim3(nb), dim3(AB), 0, ctx->stream, (const double *)xb[p], xb[o],
-                               (const double *)g, td, cm, invL, T, partials, C);
-        SBTV_TRY(wav_synthesis(ctx, wp, xb[o], zb[o], 1));               // :43
-        SBTV_TRY(op_resid(ctx, c, zb[o], acc));                          // :44
-        RedJobs jb;
-        jb.add(partials, nq, nb, sums);
-        jb.add(acc, 1, nrb, sums + 8);
-        SBTV_TRY(reduce_jobs(ctx, jb));
-        const double t_old = t_enq;
-        t_enq = 0.5 * (1 + sqrt(1 + 4 * t_old * t_old));                 // :41
-        c_enq = (t_old - 1) / t_enq;                                     // :42
-        return run.publish(k, sums, 12, 0);
-    };
-    bool stop = false;
-    // host side of iteration k: traces and the stop rule (:44-66)
-    auto process = [&](int k) -> int {
-        const double *hsl;
-        SBTV_TRY(run.wait(k, &hsl));
-        ctx->calls += 3;                                                 // A(y), AT, A(x)
-        const double f = 0.5 * (hsl[8] * c.parseval) + tau * hsl[0];     // :44
-        if (objective) objective[k - 1] = f;
-        if (mses && td) mses[k - 1] = hsl[3] / (double)C;                // :45
-        if (times) times[k - 1] = run.seconds();
-        double crit;
-        if (stopcriterion == 1)
-            crit = fabs(f - obj_prev) / f;                               // :51
-        else if (stopcriterion == 2)
-            crit = sqrt(hsl[2]) / sqrt(hsl[1]);                          // :53 (0 / 0 = NaN at x = 0: never below the tolerance)
-        else
-            crit = f;                                                    // :55
-        obj_prev = f;
-        stop = crit < tolerance;                                         // :64
-        return 0;
-    };
-    int last = 1;
-    SBTV_TRY(pipelined_loop(ctx, &last, maxiters, lag, false, enqueue, process, [&] { return !stop; }));
-    SBTV_TRY(run.finish(P, last, nullptr, nullptr));
-    SBTV_HIP(ctx, hipMemcpyAsync(xw_out_dev, xb[last & 1], sizeof(double) * C, hipMemcpyDeviceToDevice, ctx->stream));
-    if (x_out_dev)
-        SBTV_HIP(ctx, hipMemcpyAsync(x_out_dev, zb[last & 1], sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
 // item b of a batch as its solver sees it (device pointers)
 struct AdmmItem {
     const double *y, *mask, *tru, *x_init;
@@ -1670,111 +1004,6 @@ int sbtv_SALSA_masked(sbtv_ctx *ctx, const double *y, const double *mask, int M,
                               it.x, off(objective, b * (mi + 1)), off(distance, b * mi * 2), off(times, b * (mi + 1)),
                               off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b), spec);
         });
-}
-
-int sbtv_SALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
-                       const double *h, int hlen, int levels, const double *tau, const double *mu,
-                       const sbtv_salsa_opts *opts, const double *true_xw, const double *xw_init, double *xw_out,
-                       double *x_out, double *objective, double *distance, double *times, double *mses, int *numA,
-                       int *numAt, int *n_outer, int flags) {
-    if (!ctx) return SBTV_ERR_BADARG;
-    SBTV_TRY(check_common(ctx, "SALSA_wavelet", y, taps, opts, xw_init, M, N, batch, taille, "xw_init", false));   // no TV prox
-    if (!tau || !mu || !xw_out) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: missing required argument");
-    WavPlan wp;
-    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
-    for (int b = 0; b < batch; ++b)
-        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_wavelet: mu must be > 0");
-    SBTV_TRY(check_even_pixels(ctx, M, N));
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    const size_t P = (size_t)M * N, C = P * wp.bands(), cnt = P * batch, ccnt = C * batch;
-    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "wav.in.true", true_xw, ccnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "wav.in.xinit", xw_init, ccnt, flags, &xi));
-    double *xwo = nullptr, *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "wav.out.xw", xw_out, ccnt, flags, &xwo));
-    if (x_out) SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const size_t mi = (size_t)opts->maxiter;
-    for (size_t b = 0; b < (size_t)batch; ++b)
-        SBTV_TRY(wavelet_one(ctx, yd + b * P, M, N, taps + b * taille * taille, taille, wp, tau[b], mu[b], opts, off(td, b * C),
-                             off(xi, b * C), xwo + b * C, off(xo, b * P), off(objective, b * (mi + 1)), off(distance, b * mi),
-                             off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
-    SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
-    if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
-}
-
-int sbtv_SALSA_analysis(sbtv_ctx *ctx, const double *y, int M, int N, int batch, const double *taps, int taille,
-                        const double *h, int hlen, int levels, const double *tau, const double *mu,
-                        const sbtv_salsa_opts *opts, const double *true_x, const double *x_init, double *x_out,
-                        double *objective, double *distance, double *times, double *mses, int *numA, int *numAt,
-                        int *n_outer, int flags) {
-    if (!ctx) return SBTV_ERR_BADARG;
-    SBTV_TRY(check_common(ctx, "SALSA_analysis", y, taps, opts, x_init, M, N, batch, taille, "x_init", false));   // no TV prox
-    if (!tau || !mu || !x_out) return fail(ctx, SBTV_ERR_BADARG, "SALSA_analysis: missing required argument");
-    WavPlan wp;
-    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
-    for (int b = 0; b < batch; ++b)
-        if (!(mu[b] > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "SALSA_analysis: mu must be > 0");
-    SBTV_TRY(check_even_pixels(ctx, M, N));
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    const size_t P = (size_t)M * N, cnt = P * batch;
-    const double *yd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", y, cnt, flags, &yd));
-    SBTV_TRY(stage_in(ctx, "admm.in.true", true_x, cnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "admm.in.xinit", x_init, cnt, flags, &xi));
-    double *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const size_t mi = (size_t)opts->maxiter;
-    for (size_t b = 0; b < (size_t)batch; ++b)
-        SBTV_TRY(analysis_one(ctx, yd + b * P, M, N, taps + b * taille * taille, taille, wp, tau[b], mu[b], opts, off(td, b * P),
-                              off(xi, b * P), xo + b * P, off(objective, b * (mi + 1)), off(distance, b * mi),
-                              off(times, b * (mi + 1)), off(mses, b * (mi + 1)), off(numA, b), off(numAt, b), off(n_outer, b)));
-    SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
-}
-
-int sbtv_fista_l1(sbtv_ctx *ctx, const double *b, int M, int N, int batch, const double *taps, int taille, const double *h,
-                  int hlen, int levels, const double *tau, double L, int stopcriterion, double tolerance, int maxiters,
-                  const double *true_xw, const double *xw_init, double *xw_out, double *x_out, double *objective,
-                  double *times, double *mses, int *n_iter, int flags) {
-    if (!ctx) return SBTV_ERR_BADARG;
-    if (!b || !taps || !h || !tau || !xw_out || batch < 1)
-        return fail(ctx, SBTV_ERR_BADARG, "fista_l1: missing required argument (b, taps, h, tau, xw_out; batch >= 1)");
-    if (stopcriterion < 1 || stopcriterion > 3) return fail(ctx, SBTV_ERR_STOPCRITERION, "Invalid stopping criterion!");   // :57
-    if (maxiters < 1) return fail(ctx, SBTV_ERR_MAXITER, "fista_l1: maxiters must be positive");
-    if (!std::isfinite(L) || !(L > 0.0)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: L must be finite and > 0");
-    if (std::isnan(tolerance)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: tolerance is NaN");
-    for (int i = 0; i < batch; ++i)
-        if (!std::isfinite(tau[i]) || !(tau[i] >= 0.0)) return fail(ctx, SBTV_ERR_BADARG, "fista_l1: tau must be finite and >= 0");
-    SBTV_TRY(check_psf_fits(ctx, taille, M, N));
-    WavPlan wp;
-    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, true, &wp));
-    SBTV_TRY(check_even_pixels(ctx, M, N));
-    SBTV_HIP(ctx, hipSetDevice(ctx->device));
-    { FftPlan chk; SBTV_TRY(fft_plan(ctx, M, N, 1, &chk)); }
-    const size_t P = (size_t)M * N, C = P * wp.bands(), cnt = P * batch, ccnt = C * batch;
-    const double *bd = nullptr, *td = nullptr, *xi = nullptr;
-    SBTV_TRY(stage_in(ctx, "admm.in.y", b, cnt, flags, &bd));
-    SBTV_TRY(stage_in(ctx, "wav.in.true", true_xw, ccnt, flags, &td));
-    SBTV_TRY(stage_in(ctx, "wav.in.xinit", xw_init, ccnt, flags, &xi));
-    double *xwo = nullptr, *xo = nullptr;
-    SBTV_TRY(stage_out_buf(ctx, "wav.out.xw", xw_out, ccnt, flags, &xwo));
-    if (x_out) SBTV_TRY(stage_out_buf(ctx, "admm.out.x", x_out, cnt, flags, &xo));
-    const size_t mi = (size_t)maxiters;
-    const int lag = (flags & SBTV_FISTA_L1_NOLAG) ? 0 : 1;
-    for (size_t i = 0; i < (size_t)batch; ++i)
-        SBTV_TRY(fista_l1_one(ctx, bd + i * P, M, N, taps + i * taille * taille, taille, wp, tau[i], L, stopcriterion, tolerance,
-                              maxiters, lag, off(td, i * C), off(xi, i * C), xwo + i * C, off(xo, i * P), off(objective, i * mi),
-                              off(times, i * mi), off(mses, i * mi), off(n_iter, i)));
-    SBTV_TRY(stage_out_copy(ctx, xw_out, xwo, ccnt, flags));
-    if (x_out) SBTV_TRY(stage_out_copy(ctx, x_out, xo, cnt, flags));
-    SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return canary_epilogue(ctx, 0);
 }
 
 }  // extern "C"

@@ -101,7 +101,7 @@ def my_fista_l1(b, h, tau, wavelet, levels, stopcriterion, tolerance, maxiters, 
     Extensions: L (the reference fixes 1), xw_init (start coefficients, x = y = xw_init; default the reference's zeros),
     lag=False (SBTV_FISTA_L1_NOLAG: the host waits for every iteration; same result), return_xw=True appends the
     coefficients of the stopping iteration.  b may be a batch (B, M, N) or a device tensor, as for SALSA_wavelet."""
-    from .wavelet import _bands, _filter, _resized
+    from .wavelet import _bands, _check_coefficients, _counters, _filter, _resized, _traces, _trimmed
     ctx = ctx or _lib.default_context()
     if getattr(ctx, "is_group", False):
         raise NotImplementedError("my_fista_l1 has no sharded variant")
@@ -121,17 +121,12 @@ def my_fista_l1(b, h, tau, wavelet, levels, stopcriterion, tolerance, maxiters, 
     ha, hp, K = _filter(wavelet)
     ti = _lib.Images(true) if true is not None else None
     xi = _lib.Images(xw_init) if xw_init is not None else None
-    for other in (ti, xi):
-        if other is not None:
-            if (other.B, other.M, other.N) != (B, M, nb * N):
-                raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
-            if other.flags != bi.flags:
-                raise ValueError("all image arguments must live in the same memory space")
+    _check_coefficients(bi, nb, ti, xi)
     Kmax = max(int(maxiters), 1)
     xwo = _resized(bi, nb * N)
     xo = _lib.empty_like_images(bi)
-    objective, times, mses = np.zeros((B, Kmax)), np.zeros((B, Kmax)), np.zeros((B, Kmax))
-    nit = (C.c_int * B)()
+    objective, times, mses = _traces(B, Kmax, Kmax, Kmax)
+    nit, = _counters(B, 1)
     taps = A._cm(B)
     tau_a, tau_p = _lib.dvec(tau, B)
     vp = _lib.vptr
@@ -141,11 +136,5 @@ def my_fista_l1(b, h, tau, wavelet, levels, stopcriterion, tolerance, maxiters, 
                                     vp(mses) if ti else None, nit, bi.flags | (0 if lag else _lib.FISTA_L1_NOLAG)), bi.flags)
     sq = (b.dim() == 2) if bi.torch else bi.squeeze
     Wx, xw = _lib.images_result(xo, sq), _lib.images_result(xwo, sq)
-    n = np.array(nit[:])
-    if sq or B == 1:
-        k = int(n[0])
-        out = (Wx, objective[0, :k].copy(), times[0, :k].copy(), mses[0, :k].copy() if ti else np.array([]))
-    else:
-        out = (Wx, [objective[i, :n[i]].copy() for i in range(B)], [times[i, :n[i]].copy() for i in range(B)],
-               [mses[i, :n[i]].copy() for i in range(B)] if ti else [])
+    out = (Wx,) + _trimmed(np.array(nit[:]), sq or B == 1, (objective, 0), (times, 0), (mses if ti else None, 0))
     return out + (xw,) if return_xw else out

@@ -98,6 +98,56 @@ def soft(x, T, ctx=None):
     return L.images_result(yo, (x.dim() == 2) if xi.torch else xi.squeeze)
 
 
+def _solver_options(name, varargin, kw, ctx):
+    """(options, context) of SALSA_wavelet / SALSA_analysis: the name / value pairs, keywords over them; no group."""
+    opts = _parse_varargin(varargin, _WAVELET_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError(f"{name} has no sharded variant")
+    return opts, ctx
+
+
+def _check_coefficients(yi, nb, *arrays):
+    """The coefficient arguments (None: not given) of a solve on the images yi: nb bands each, in the memory space of yi."""
+    for other in arrays:
+        if other is not None:
+            if (other.B, other.M, other.N) != (yi.B, yi.M, nb * yi.N):
+                raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
+            if other.flags != yi.flags:
+                raise ValueError("all image arguments must live in the same memory space")
+
+
+def _traces(B, *lengths):
+    """One zeroed (B, n) trace per length n."""
+    return [np.zeros((B, n)) for n in lengths]
+
+
+def _counters(B, count):
+    return [(C.c_int * B)() for _ in range(count)]
+
+
+def _trimmed(n, single, *traces):
+    """Each (trace, extra) cut to the n[b] + extra entries that image b wrote: one array for a single image, else a list
+    with one per image; a trace of None (not asked for) comes back empty."""
+    out = []
+    for t, extra in traces:
+        if t is None:
+            out.append(np.array([]) if single else [])
+        elif single:
+            out.append(t[0, :int(n[0]) + extra].copy())
+        else:
+            out.append([t[b, :n[b] + extra].copy() for b in range(len(n))])
+    return tuple(out)
+
+
+def _salsa_result(images, single, numA, numAt, nout, objective, distance, times, mses):
+    """The return tuple of SALSA_wavelet / SALSA_analysis after `images`: the counters and the traces of the iterations run."""
+    counts = (int(numA[0]), int(numAt[0])) if single else (np.array(numA[:]), np.array(numAt[:]))
+    return images + counts + _trimmed(np.array(nout[:]), single, (objective, 1), (distance, 0), (times, 1), (mses, 1))
+
+
 def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
     """[xw, x, numA, numAt, objective, distance, times, mses] = SALSA_wavelet(y, A, tau, 'MU', mu, 'WAVELET', h, 'LEVELS', L,
     'AT', A.T, ...)
@@ -108,12 +158,7 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
     'LEVELS' (4), 'AT', 'STOPCRITERION', 'TOLERANCEA', 'MAXITERA', 'TRUE_X' (the true COEFFICIENTS, e.g. mrdwt_TI2D(x_true)),
     'INITIALIZATION' (0, 2 = W' A' y, or a coefficient array), 'VERBOSE', and 'SPECULATE' (sbtv_salsa_opts.speculate: 0 makes the
     host evaluate the stop rule without the one-iteration lag; the result is the same)."""
-    opts = _parse_varargin(varargin, _WAVELET_OPTIONS)
-    for k, v in kw.items():
-        opts[k.upper()] = v
-    ctx = ctx or L.default_context()
-    if getattr(ctx, "is_group", False):
-        raise NotImplementedError("SALSA_wavelet has no sharded variant")
+    opts, ctx = _solver_options("SALSA_wavelet", varargin, kw, ctx)
     levels = int(opts.get("LEVELS", 4))
     nb = max(_bands(levels), 1)
     # the coefficient arguments have (3J+1) N columns: _common compares TRUE_X with y, so they are handled here
@@ -135,18 +180,12 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
     true = opts.get("TRUE_X", None)
     ti = L.Images(true) if true is not None else None
     so.compute_mse = 1 if ti is not None else 0
-    for other in (xinit, ti):
-        if other is not None:
-            if (other.B, other.M, other.N) != (B, M, nb * N):
-                raise ValueError("coefficient arrays must be (M, (3 (levels-1) + 1) N) per image")
-            if other.flags != yi.flags:
-                raise ValueError("all image arguments must live in the same memory space")
+    _check_coefficients(yi, nb, xinit, ti)
     Kmax = so.maxiter
     xwo = _resized(yi, nb * N)
     xo = L.empty_like_images(yi)
-    objective, times, mses = np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1))
-    distance = np.zeros((B, Kmax))
-    numA, numAt, nout = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+    objective, distance, times, mses = _traces(B, Kmax + 1, Kmax, Kmax + 1, Kmax + 1)
+    numA, numAt, nout = _counters(B, 3)
     taps = A._cm(B)
     keep = [L.dvec(v, B) for v in (tau, opts["MU"])]
     tv, mu = (k[1] for k in keep)
@@ -155,15 +194,8 @@ def SALSA_wavelet(y, A, tau, *varargin, ctx=None, **kw):
                                          _vp(objective), _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt,
                                          nout, yi.flags), yi.flags)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
-    xw, x = L.images_result(xwo, sq), L.images_result(xo, sq)
-    n = np.array(nout[:])
-    if sq or B == 1:
-        k = int(n[0])
-        return (xw, x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(),
-                times[0, :k + 1].copy(), mses[0, :k + 1].copy() if ti else np.array([]))
-    return (xw, x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
-            [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
-            [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
+    return _salsa_result((L.images_result(xwo, sq), L.images_result(xo, sq)), sq or B == 1, numA, numAt, nout, objective,
+                         distance, times, mses if ti else None)
 
 
 def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
@@ -175,12 +207,7 @@ def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
     389-440) with 'Psi' = soft and 'LS' = real(ifft2(fft2(r) ./ (|H|^2 + mu))); the iteration is stated in include/sbtv.h
     (sbtv_SALSA_analysis).  The options of SALSA_wavelet; 'TRUE_X' is the true IMAGE and an array 'INITIALIZATION' a start image
     (0: zeros, 2: A' y).  distance is ||W'x - u|| / sqrt(||W'x||^2 + ||u||^2), mses ||x - true||^2 / numel(x)."""
-    opts = _parse_varargin(varargin, _WAVELET_OPTIONS)
-    for k, v in kw.items():
-        opts[k.upper()] = v
-    ctx = ctx or L.default_context()
-    if getattr(ctx, "is_group", False):
-        raise NotImplementedError("SALSA_analysis has no sharded variant")
+    opts, ctx = _solver_options("SALSA_analysis", varargin, kw, ctx)
     levels = int(opts.get("LEVELS", 4))
     init = opts.get("INITIALIZATION", 0)
     if not (np.ndim(init) > 0 or L._is_torch(init)) and int(init) not in (0, 2):
@@ -195,9 +222,8 @@ def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
             raise ValueError("'TRUE_X' and an array 'INITIALIZATION' must be images of the size of y")
     Kmax = so.maxiter
     xo = L.empty_like_images(yi)
-    objective, times, mses = np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1)), np.zeros((B, Kmax + 1))
-    distance = np.zeros((B, Kmax))
-    numA, numAt, nout = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+    objective, distance, times, mses = _traces(B, Kmax + 1, Kmax, Kmax + 1, Kmax + 1)
+    numA, numAt, nout = _counters(B, 3)
     taps = A._cm(B)
     keep = [L.dvec(v, B) for v in (tau, opts["MU"])]
     tv, mu = (k[1] for k in keep)
@@ -206,15 +232,8 @@ def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
                                           _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
               yi.flags)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
-    x = L.images_result(xo, sq)
-    n = np.array(nout[:])
-    if sq or B == 1:
-        k = int(n[0])
-        return (x, int(numA[0]), int(numAt[0]), objective[0, :k + 1].copy(), distance[0, :k].copy(), times[0, :k + 1].copy(),
-                mses[0, :k + 1].copy() if ti else np.array([]))
-    return (x, np.array(numA[:]), np.array(numAt[:]), [objective[b, :n[b] + 1].copy() for b in range(B)],
-            [distance[b, :n[b]].copy() for b in range(B)], [times[b, :n[b] + 1].copy() for b in range(B)],
-            [mses[b, :n[b] + 1].copy() for b in range(B)] if ti else [])
+    return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
+                         mses if ti else None)
 
 
 def _op(op, name, default=None):

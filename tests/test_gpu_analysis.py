@@ -1,4 +1,4 @@
-"""GPU: the analysis-prior wavelet SALSA driver (sbtv_SALSA_analysis, csrc/admm.hip; sbtv.SALSA_analysis) against SALSA_v2.m
+"""GPU: the analysis-prior wavelet SALSA driver (sbtv_SALSA_analysis, csrc/wavelet_deconv.hip; sbtv.SALSA_analysis) against SALSA_v2.m
 restated line for line in NumPy with P = W, PT = W' (tests/analysis_restatement.py, salsa_analysis_literal) on the cases of
 tests/analysis_cases.py.
 

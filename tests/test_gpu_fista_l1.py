@@ -1,4 +1,4 @@
-"""GPU: the wavelet-l1 FISTA driver (sbtv_fista_l1, csrc/admm.hip; sbtv.my_fista_l1) against my_fista_l1.m restated line for
+"""GPU: the wavelet-l1 FISTA driver (sbtv_fista_l1, csrc/wavelet_deconv.hip; sbtv.my_fista_l1) against my_fista_l1.m restated line for
 line in NumPy (tests/fista_l1_restatement.py, fista_l1_literal) on the cases of tests/fista_l1_cases.py.
 
 The bars are those tests/test_gpu_wavelet.py uses for this frame and operator: the same stopping iteration, objective / mses

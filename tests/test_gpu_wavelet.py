@@ -1,5 +1,5 @@
 """GPU: the redundant wavelet frame (sbtv_mrdwt_TI2D / sbtv_mirdwt_TI2D, csrc/wavelet.hip), sbtv_soft and the wavelet-l1
-SALSA driver (sbtv_SALSA_wavelet, csrc/admm.hip) against the NumPy restatement (tests/wavelet_restatement.py).
+SALSA driver (sbtv_SALSA_wavelet, csrc/wavelet_deconv.hip) against the NumPy restatement (tests/wavelet_restatement.py).
 
 Transforms: atol 1e-12 max|x| (about 2 K J roundings of 1.1e-16 per output: under 1e-14 relative); adjoint and Parseval
 identities on the device's own output to 1e-11 relative.  Solver: the bars of tests/test_gpu_admm.py and test_gpu_masked.py

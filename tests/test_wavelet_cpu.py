@@ -134,7 +134,7 @@ def test_wavelet_tile_kernels_fit_two_workgroups_per_cu_without_scratch():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_wavelet_solver_elementwise_kernels_use_no_scratch():
-    rep = _report("admm.hip")
+    rep = _report("wavelet_deconv.hip")
     for name in ("wav_init_kernel", "wav_prox_kernel", "wav_post_kernel", "wav_sum_kernel"):
         k = _find(rep, name)
         print(name, k)
