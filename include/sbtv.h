@@ -363,6 +363,46 @@ int sbtv_SALSA_analysis(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                         const double *true_x, const double *x_init, double *x_out,
                         double *objective, double *distance, double *times, double *mses,
                         int *numA, int *numAt, int *n_outer, int flags);
+/* min over the IMAGE x  0.5 ||y - B x||^2 + tau1 TV(x) + tau2 ||W' x||_1: CoRAL (SALSA/CoRAL_v2.m:2-476) with the compound
+ * regulariser it exists for, TV on the image plus l1 on the coefficients of the redundant wavelet frame.  In the reference's
+ * terms P1 = P1' = identity with TVINITIALIZATION1 = 1, P2 = W = mirdwt_TI2D, P2' = W' = mrdwt_TI2D, Psi2 = soft, Phi2 = l1,
+ * TVINITIALIZATION2 = 0, and invLS(r) = real(ifft2(fft2(r) ./ (abs(H).^2 + mu))), mu = mu1 + mu2 (:137), the exact
+ * x-minimiser because W W' = I:
+ *     start:  x by opts->initialization (0 zeros, 2 B'y, 33333 x_init) ;  u = x ;  bu = u ;  v = W'x ;  bv = v     (:349-361)
+ *             objective(1) = 0.5 ||y - B x||^2 + tau1 TVnorm(u) + tau2 ||v||_1 ;  mses(1)                           (:366-382)
+ *             pux = puy = 0
+ *     outer:  u = chambolle_prox_TV_stop(x - bu, 'lambda', tau1/mu1, 'maxiter', TViters, 'dualvars', [pux puy])     (:401)
+ *             v = soft(W'x - bv, tau2/mu2)                                                                          (:408)
+ *             x = invLS(B'y + mu1 * (u + bu) + mu2 * W(v + bv))                                                     (:411-413)
+ *             bu = bu + (u - x) ;  bv = bv + (v - W'x)                                                              (:417-421)
+ *             objective(outer+1) = 0.5 ||y - B x||^2 + tau1 TVnorm(u) + tau2 ||v||_1 ;  mses(outer+1)               (:423-430)
+ *             distance(outer, 1) = ||x - u|| / sqrt(||x||^2 + ||u||^2)                                              (:432)
+ *             distance(outer, 2) = ||W'x - v|| / sqrt(||W'x||^2 + ||v||^2)                                          (:433)
+ *             stop rules 1, 2, 3 from outer = 2 on (:435-466); rule 2 is ||x - xprev|| / ||x|| on the image
+ * What runs keeps the pixel state x, u, bu, g1 = x - bu and the coefficient state (sv, bv), sv = v + bv, as
+ * sbtv_SALSA_analysis does: z = W sv, s = (mu1 (u + bu) + mu2 z) / mu, X = (conj(H) .* fft2(y) + mu * fft2(s)) ./ (abs(H).^2 + mu),
+ * x = real(ifft2(X)), w = W'x, then one pass over the coefficients recovers v = sv - bv (exactly zero where the threshold cut
+ * it), takes its sums, forms bv + (v - w) and the next sv, and one pass over the pixels updates bu and forms the next prox
+ * input.  The start is sv = bv = W'x: the first soft argument is exactly zero, as the first prox input is.
+ * opts->TViters is the Chambolle count and the Chambolle knobs apply.  true_x / x_init / x_out: [batch][M*N] images; x_out is
+ * required.  objective / times / mses: [batch*(maxiter+1)]; distance: [batch*maxiter*2], entry (outer-1)*2+{0,1}.
+ * numA = 1 + one per outer iteration, numAt = 2 (B'y is formed twice, :189,219); P2 and P2' are not counted.
+ * `speculate` as for sbtv_CoRAL_v2: bit 0 the host books an iteration one iteration late (x, sv and bv are double-buffered:
+ * the result is that of the stopping iteration), bit 1 never launch the TV prox optimistically; the result is always that of
+ * the exact Chambolle stop rule.  Images of a batch are solved one after another, image k bit for bit as alone; there is no
+ * sharded variant.  SBTV_DEVICE_PTRS applies to y / true_x / x_init / x_out.
+ * Errors before any GPU work, with the codes of sbtv_SALSA_analysis and sbtv_CoRAL_v2: h not orthonormal, tau1 / tau2 / mu1 /
+ * mu2 / x_out NULL -> SBTV_ERR_BADARG; mu1[b] <= 0 or mu2[b] <= 0 -> SBTV_ERR_MISSING_LS; odd pixel count or tap reach >=
+ * min(M, N) -> SBTV_ERR_SIZE; levels < 2 -> SBTV_ERR_BADARG; TViters <= 0 or maxiter < 1 -> SBTV_ERR_MAXITER; stop criterion,
+ * initialization and PSF fit as sbtv_SALSA_v2. */
+int sbtv_CoRAL_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                       const double *taps, int taille,
+                       const double *h, int hlen, int levels,
+                       const double *tau1, const double *tau2, const double *mu1, const double *mu2,
+                       const sbtv_salsa_opts *opts,
+                       const double *true_x, const double *x_init, double *x_out,
+                       double *objective, double *distance, double *times, double *mses,
+                       int *numA, int *numAt, int *n_outer, int flags);
 
 /* ---- empirical-Bayes estimate of theta for the wavelet-l1 prior (SALSA/run_deblur_synthesis_L1.m:125-156) -----------------
  * The script estimates the regularisation parameter before it solves the MAP problem: a MYULA chain on the wavelet

@@ -1,9 +1,9 @@
 // ---- what the single-image ADMM-style drivers share -------------------------------------------------------------
-// admm.hip (the TV front-ends) and wavelet_deconv.hip (the wavelet-l1 solvers) include this file inside their anonymous
-// namespace in namespace sbtv, after <chrono> and sbtv_internal.h, as the SAPG drivers include sapg_step.inc; nothing here
-// is relocatable device code, so each unit carries its own copy of ad_sub_kernel.  The element-wise kernels of both units
-// are written with AD_LOOP / AD_LD / AD_ST and end in ad_store_partials; their drivers open the operator layer with
-// admm_common and carry their pipelined loop in an AdmmRun.
+// admm.hip (the TV front-ends), wavelet_deconv.hip (the wavelet-l1 solvers) and coral_wavelet.hip (CoRAL with both
+// regularisers) include this file inside their anonymous namespace in namespace sbtv, after <chrono> and sbtv_internal.h, as
+// the SAPG drivers include sapg_step.inc; nothing here is relocatable device code, so each unit carries its own copy of
+// ad_sub_kernel.  The element-wise kernels of these units are written with AD_LOOP / AD_LD / AD_ST and end in
+// ad_store_partials; their drivers open the operator layer with admm_common and carry their pipelined loop in an AdmmRun.
 constexpr int AB = 256;
 
 __device__ __forceinline__ double ad_wave_sum(double v) {

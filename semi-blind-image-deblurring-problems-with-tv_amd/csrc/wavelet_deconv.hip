@@ -19,24 +19,9 @@ namespace sbtv {
 namespace {
 
 #include "admm_run.inc"   // AB, ad_store_partials, AD_LOOP / AD_LD / AD_ST, ad_sub_kernel, ad_blocks, admm_common, upload_par, AdmmRun
+#include "wav_step.inc"   // wav_init_kernel, wav_astep_kernel
 
 // ---- wavelet-l1 SALSA (wavelet_one) -------------------------------------------------------------------------------
-// l1 norm of the start xw and its distance to the true coefficients: partials [2][nb]
-__global__ __launch_bounds__(AB) void wav_init_kernel(const double *__restrict__ xw, const double *__restrict__ tru,
-                                                       double *__restrict__ partials, size_t C) {
-    double acc[2] = {0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 v = AD_LD(xw, q);
-        acc[0] += fabs(v.x) + fabs(v.y);
-        if (tru) {
-            const double2 t = AD_LD(tru, q);
-            const double m0 = v.x - t.x, m1 = v.y - t.y;
-            acc[1] += m0 * m0 + m1 * m1;
-        }
-    }
-    ad_store_partials<2>(acc, partials);
-}
-
 // The prox of an outer iteration on the state (s, we) of the previous one, xw = s + we and bu = -we:
 //   u = soft(xw - bu, T) = soft(s + 2 we, T) ; s' = u + bu = u - we ; partials [2][nb]: |u|, u^2
 __global__ __launch_bounds__(AB) void wav_prox_kernel(const double *__restrict__ s, const double *__restrict__ we,
@@ -90,30 +75,7 @@ __global__ __launch_bounds__(AB) void wav_sum_kernel(const double *__restrict__ 
 }
 
 // ---- analysis-prior wavelet SALSA (analysis_one) ------------------------------------------------------------------
-// The one coefficient pass of an outer iteration k, after the analysis w = W'x_k, on the state (s, bu) = (u_k + bu_{k-1}, bu_{k-1}):
-//   u = s - bu (exactly zero where the threshold cut it: there s == bu bit for bit) ; bu' = bu + (u - w)    (SALSA_v2.m:440)
-//   u' = soft(w - bu', T) ; s' = u' + bu'                                                                  (:431 of k + 1)
-//   partials [4][nb]: |u|, u^2, (w-u)^2, w^2
-// The start is the same pass with s = w_0 and bu = 0.
-__global__ __launch_bounds__(AB) void wav_astep_kernel(const double *__restrict__ s, const double *__restrict__ bu,
-                                                        const double *__restrict__ w, double *__restrict__ bun,
-                                                        double *__restrict__ sn, double T, double *__restrict__ partials,
-                                                        size_t C) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    AD_LOOP(q, C) {
-        const double2 sv = AD_LD(s, q), bv = AD_LD(bu, q), wv = AD_LD(w, q);
-        const double u0 = sv.x - bv.x, u1 = sv.y - bv.y;
-        const double d0 = wv.x - u0, d1 = wv.y - u1;
-        const double b0 = bv.x + (u0 - wv.x), b1 = bv.y + (u1 - wv.y);
-        AD_ST(bun, q, make_double2(b0, b1));
-        AD_ST(sn, q, make_double2(wav_soft(wv.x - b0, T) + b0, wav_soft(wv.y - b1, T) + b1));
-        acc[0] += fabs(u0) + fabs(u1);
-        acc[1] += u0 * u0 + u1 * u1;
-        acc[2] += d0 * d0 + d1 * d1;
-        acc[3] += wv.x * wv.x + wv.y * wv.y;
-    }
-    ad_store_partials<4>(acc, partials);
-}
+// the pass itself, wav_astep_kernel, is in wav_step.inc
 
 // the image-domain sums of an outer iteration: partials [3][nb]: (x-true)^2, (x-xprev)^2, x^2 (tru / xprev null: not summed)
 __global__ __launch_bounds__(AB) void ad_xsums_kernel(const double *__restrict__ x, const double *__restrict__ tru,

@@ -142,9 +142,10 @@ def CoRAL(y, A, tau1, tau2, *varargin, ctx=None, **kw):
         if (a in opts) != (b in opts):
             raise ValueError(f"If you give {a} you must also give {b}, and vice versa.")       # :143,153
         if a in opts:
-            raise NotImplementedError("'P1'/'P2' other than the identity are not supported")
+            raise NotImplementedError("'P1'/'P2' other than the identity are not supported (TV + wavelet-l1, P2 = mirdwt_TI2D: "
+                                      "use sbtv.CoRAL_wavelet)")
     if not (opts.get("TVINITIALIZATION1", 0) and opts.get("TVINITIALIZATION2", 0)):
-        raise NotImplementedError("only the TV/TV configuration runs on the GPU")
+        raise NotImplementedError("only the TV/TV configuration runs on the GPU (TV + wavelet-l1: use sbtv.CoRAL_wavelet)")
     print("WARNING: TV with initialization has been specified for both Phi1 and Phi2. Try reformulating with a "
           "single regularizer term for efficiency.", file=sys.stdout)                          # :224
     so.TViters = int(opts.get("TVITERS1", 5))

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib as L
 from .admm import _common
+from .operators import _InvLS
 from .sapg import _moment_buffers, _moments_opts
 from .tv import _parse_varargin
 
@@ -230,6 +231,63 @@ def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
     ctx.check(ctx.lib.sbtv_SALSA_analysis(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, tv, mu, C.byref(so),
                                           ti.ptr if ti else None, xinit.ptr if xinit else None, xo.ptr, _vp(objective),
                                           _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
+              yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
+                         mses if ti else None)
+
+
+_CORAL_WAVELET_OPTIONS = {"MU1", "MU2", "WAVELET", "LEVELS", "TVITERS", "AT", "LS", "STOPCRITERION", "TOLERANCEA", "MAXITERA",
+                          "INITIALIZATION", "TRUE_X", "VERBOSE", "SPECULATE"}
+
+
+def CoRAL_wavelet(y, A, tau1, tau2, *varargin, ctx=None, **kw):
+    """[x, numA, numAt, objective, distance, times, mses] = CoRAL_wavelet(y, A, tau1, tau2, 'MU1', mu1, 'MU2', mu2, 'WAVELET', h,
+    'LEVELS', L, 'TVITERS', K, 'AT', A.T, 'LS', A.LS(mu1 + mu2), ...)
+
+    minimise 0.5 ||y - A x||^2 + tau1 TV(x) + tau2 ||W' x||_1 over the IMAGE x: CoRAL (SALSA/CoRAL_v2.m:2-476) with the compound
+    regulariser TV + wavelet-l1, i.e. 'P1' = identity with 'TVINITIALIZATION1' = 1, 'P2' = W = `mirdwt_TI2D`, 'P2T' = W' =
+    `mrdwt_TI2D`, 'PSI2' = soft; the iteration is stated in include/sbtv.h (sbtv_CoRAL_wavelet).  'MU1' and 'MU2' are required,
+    'LS' is `A.LS(mu1 + mu2)` (the reference's convention, :137; another mu is refused).  Other options: 'WAVELET' (an
+    orthonormal scaling filter, default daubcqf(2)), 'LEVELS' (4), 'TVITERS' (5), 'STOPCRITERION', 'TOLERANCEA', 'MAXITERA',
+    'INITIALIZATION' (0 zeros, 2 = A' y, or a start image), 'TRUE_X' (the true image), 'VERBOSE', 'SPECULATE'
+    (sbtv_salsa_opts.speculate; the result is the same).  The return values are shaped as `CoRAL` returns them: distance is
+    (outer, 2), column 0 the TV split ||x - u||, column 1 the wavelet split ||W'x - v||, both relative."""
+    opts = _parse_varargin(varargin, _CORAL_WAVELET_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("CoRAL_wavelet has no sharded variant")
+    init = opts.get("INITIALIZATION", 0)
+    if not (np.ndim(init) > 0 or L._is_torch(init)) and int(init) not in (0, 2):
+        raise L.SbtvError(-7, "Unknown 'Initialization' option")          # the random start of CoRAL_v2 is not offered
+    so, yi, xinit, ti = _common(y, A, opts, ctx, 1)
+    if "MU1" not in opts or "MU2" not in opts:
+        raise L.SbtvError(-1, "CoRAL_wavelet: 'MU1' and 'MU2' are required")
+    B, M, N = yi.B, yi.M, yi.N
+    LS = opts.get("LS", None)
+    if not isinstance(LS, _InvLS) or LS.op is not A:
+        raise L.SbtvError(-9, "(A^T A + \\mu I)^(-1) must be specified as a function handle.")   # :197
+    keep = [L.dvec(v, B) for v in (tau1, tau2, opts["MU1"], opts["MU2"])]
+    t1, t2, m1, m2 = (k[1] for k in keep)
+    if not np.array_equal(np.broadcast_to(np.asarray(LS.mu, dtype=np.float64), (B,)), keep[2][0] + keep[3][0]):
+        raise L.SbtvError(-9, "CoRAL_wavelet: 'LS' must be A.LS(mu1 + mu2)")                  # :137
+    so.TViters = int(opts.get("TVITERS", 5))
+    ha, hp, K = _filter(opts.get("WAVELET", daubcqf(2)))
+    levels = int(opts.get("LEVELS", 4))
+    for other in (xinit, ti):
+        if other is not None and (other.B, other.M, other.N) != (B, M, N):
+            raise ValueError("'TRUE_X' and an array 'INITIALIZATION' must be images of the size of y")
+    Kmax = so.maxiter
+    xo = L.empty_like_images(yi)
+    objective, times, mses = _traces(B, Kmax + 1, Kmax + 1, Kmax + 1)
+    distance = np.zeros((B, Kmax, 2))
+    numA, numAt, nout = _counters(B, 3)
+    taps = A._cm(B)
+    ctx.check(ctx.lib.sbtv_CoRAL_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, t1, t2, m1, m2, C.byref(so),
+                                         ti.ptr if ti else None, xinit.ptr if xinit else None, xo.ptr, _vp(objective),
+                                         _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
               yi.flags)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
     return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
