@@ -213,7 +213,8 @@ int sbtv_SALSA_v2(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
 
 /* ---- f-3: the other ADMM front-ends over the same kernels ----------------
  * (never called by the reference's demos)  Only the TV paths exist
- * ('TVINITIALIZATION*' = 1, P/PT = identity).  Images of a batch are solved one after another.
+ * ('TVINITIALIZATION*' = 1, P/PT = identity) in these two entries; with the wavelet frame as P / PT see sbtv_CSALSA_wavelet and
+ * sbtv_CoRAL_wavelet below.  Images of a batch are solved one after another.
  *
  * sbtv_CSALSA_v2 replaces
  *   [x,numA,numAt,objective,distance1,distance2,criterion,times,mses] = csalsa(y,A,mu1,mu2,sigma,
@@ -403,6 +404,47 @@ int sbtv_CoRAL_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                        const double *true_x, const double *x_init, double *x_out,
                        double *objective, double *distance, double *times, double *mses,
                        int *numA, int *numAt, int *n_outer, int flags);
+/* min over the IMAGE x  ||W' x||_1  s.t.  ||B x - y||_2 <= epsilon: C-SALSA (SALSA/CSALSA_v2.m:160-561) with the wavelet analysis
+ * prior, its 'P' / 'PT' mode (:111-114, 208-213, 402, 467-478, 492), for the caller who knows the noise level and not a
+ * regularisation parameter.  In the reference's terms TVINITIALIZATION = 0, Psi = soft, A = B, AT = B', PT = W' = mrdwt_TI2D,
+ * P = W = mirdwt_TI2D, and invLS(r, mu1) = real(ifft2(fft2(r) ./ (abs(H).^2 + mu1))) exactly as sbtv_CSALSA_v2 defines it.
+ * That is the exact x-minimiser only for mu2 = 1; other mu2 run as the reference would run them with this handle.
+ *     start:  x by opts->initialization (0 zeros, 2 B'y, 33333 x_init) ;  PTx = W'x ;  u = bu = 0 ;  v = bv = 0     (:378-408)
+ *             epsilon = sqrt(M N + 8 sqrt(M N)) * sigma when epsilon[b] = 0 (or epsilon == NULL)                     (:413)
+ *             criterion(1) = distance1(1) = ||B x - y|| ;  distance2(1) = ||PTx|| ;  mses(1)                         (:416-448)
+ *     outer = 2..maxiter:
+ *             x   = invLS(mu1 * W(u + bu) + mu2 * B'(y + v + bv), mu1) ;  PTx = W'x                                  (:467-473)
+ *             u   = soft(PTx - bu, 1/mu1)                                                                            (:478)
+ *             ve  = B x - y - bv ;  v = ve if ||ve|| <= epsilon, else ve / ||ve|| * epsilon                          (:481-489)
+ *             bv  = bv - (B x - y - v) ;  bu = bu - (PTx - u)                                                        (:491-492)
+ *             criterion(outer) = ||B x - y|| ;  distance1(outer) = ||B x - y - v|| ;  distance2(outer) = ||PTx - u|| (:494-497)
+ *             mu1 *= continuationfactor ;  mu2 *= continuationfactor                                                 (:517-518)
+ *             stop when the rule's value < tolA AND criterion(outer) <= epsilon; rules 1, 2, 3 (:521-541), rule 2 is
+ *             ||x - xprev|| / ||x|| on the image
+ * ONE DEVIATION: objective(outer) = ||W' x||_1, the objective of the problem, which stop rule 1 then uses.  The reference
+ * records phi(x) with x the IMAGE (:423, 498), i.e. with its default Phi the l1 norm of the pixels, and probes a user's Phi
+ * with coefficients (:357); this entry fixes Phi = ||W' .||_1.
+ * What runs keeps the coefficient state (s, bu), s = u + bu, in one buffer each (only x is returned; x is double-buffered),
+ * and by default the constraint split as the spectrum of ve and one scalar, as sbtv_CSALSA_v2 does.  A continuation factor
+ * != 1, an image size whose FFT plan has no such row pass, or SBTV_CSALSA_SPECTRAL=0 keep v and bv as images.
+ * Traces are 1-based like the reference: entry 0 is the state before the loop; every trace row has maxiter entries;
+ * n_outer[b] = the last `outer`.  numA = 2 + one per iteration, numAt = 1 (+ 1 for initialization 2) + one per iteration, as
+ * sbtv_CSALSA_v2 counts them; P and PT are not counted.  opts->TViters and the Chambolle knobs are ignored; opts->speculate bit 0:
+ * the host evaluates the stop rule one iteration late (not with a continuation factor != 1); the result is the same.
+ * true_x / x_init / x_out: [batch][M*N] images; x_out is required.  Images of a batch are solved one after another, image k
+ * bit for bit as alone; there is no sharded variant.  SBTV_DEVICE_PTRS applies to y / true_x / x_init / x_out.
+ * Errors before any GPU work, with the codes of sbtv_SALSA_analysis and sbtv_CSALSA_v2: h not orthonormal, levels < 2, mu1 /
+ * mu2 / sigma / x_out NULL -> SBTV_ERR_BADARG; mu1[b] <= 0 or mu2[b] <= 0 -> SBTV_ERR_MISSING_LS; odd pixel count or tap
+ * reach >= min(M, N) -> SBTV_ERR_SIZE; maxiter < 1 -> SBTV_ERR_MAXITER; stop criterion, initialization and PSF fit as
+ * sbtv_SALSA_v2. */
+int sbtv_CSALSA_wavelet(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
+                        const double *taps, int taille,
+                        const double *h, int hlen, int levels,
+                        const double *mu1, const double *mu2, const double *sigma, const double *epsilon,
+                        double continuationfactor, const sbtv_salsa_opts *opts,
+                        const double *true_x, const double *x_init, double *x_out,
+                        double *objective, double *distance1, double *distance2, double *criterion,
+                        double *times, double *mses, int *numA, int *numAt, int *n_outer, int flags);
 
 /* ---- empirical-Bayes estimate of theta for the wavelet-l1 prior (SALSA/run_deblur_synthesis_L1.m:125-156) -----------------
  * The script estimates the regularisation parameter before it solves the MAP problem: a MYULA chain on the wavelet

@@ -1,7 +1,7 @@
 // ---- coefficient passes shared by the wavelet-l1 solvers -----------------------------------------------------------
-// wavelet_deconv.hip (the three wavelet-l1 solvers) and coral_wavelet.hip (CoRAL with the TV + wavelet-l1 regulariser)
-// include this file inside their anonymous namespace, after admm_run.inc; nothing here is relocatable device code, so
-// each unit carries its own copy of the two kernels.
+// wavelet_deconv.hip (the three wavelet-l1 solvers), coral_wavelet.hip (CoRAL with the TV + wavelet-l1 regulariser) and
+// csalsa_wavelet.hip (C-SALSA with the analysis prior) include this file inside their anonymous namespace, after
+// admm_run.inc; nothing here is relocatable device code, so each unit carries its own copy of the kernels.
 
 // l1 norm of the start xw and its distance to the true coefficients: partials [2][nb]
 __global__ __launch_bounds__(AB) void wav_init_kernel(const double *__restrict__ xw, const double *__restrict__ tru,
@@ -42,4 +42,26 @@ __global__ __launch_bounds__(AB) void wav_astep_kernel(const double *__restrict_
         acc[3] += wv.x * wv.x + wv.y * wv.y;
     }
     ad_store_partials<4>(acc, partials);
+}
+
+// The coefficient pass of C-SALSA's outer iteration k, after the analysis w = W'x_k, on the multiplier bu (updated in place):
+//   u = soft(w - bu, T) ; bu' = bu - (w - u) ; s' = u + bu', the next synthesis input       (CSALSA_v2.m:478, 492, 467 of k + 1)
+//   partials [2][nb]: |w| (the objective ||W'x_k||_1), (w-u)^2                                (:498 with Phi = ||W'.||_1, :497)
+// The threshold follows the analysis of the same iteration, so u is formed here and never recovered from s - bu: four arrays,
+// 32 B per coefficient.  The arithmetic is the reference's, term for term.
+__global__ __launch_bounds__(AB) void wav_cstep_kernel(const double *__restrict__ w, double *__restrict__ bu,
+                                                        double *__restrict__ sn, double T, double *__restrict__ partials,
+                                                        size_t C) {
+    double acc[2] = {0.0, 0.0};
+    AD_LOOP(q, C) {
+        const double2 wv = AD_LD(w, q), bv = AD_LD(bu, q);
+        const double u0 = wav_soft(wv.x - bv.x, T), u1 = wav_soft(wv.y - bv.y, T);
+        const double d0 = wv.x - u0, d1 = wv.y - u1;
+        const double b0 = bv.x - d0, b1 = bv.y - d1;
+        AD_ST(bu, q, make_double2(b0, b1));
+        AD_ST(sn, q, make_double2(u0 + b0, u1 + b1));
+        acc[0] += fabs(wv.x) + fabs(wv.y);
+        acc[1] += d0 * d0 + d1 * d1;
+    }
+    ad_store_partials<2>(acc, partials);
 }

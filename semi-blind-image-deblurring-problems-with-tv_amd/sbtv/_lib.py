@@ -165,6 +165,8 @@ SIGNATURES = {
                                  _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_CoRAL_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
                                 _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sbtv_CSALSA_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
+                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_opts), _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _I]),
     "sbtv_SAPG_wavelet_semiblind": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, C.POINTER(sbtv_sapg_wavelet_sb_opts), _P, _P, _P, _P,

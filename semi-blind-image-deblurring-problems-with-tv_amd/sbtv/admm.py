@@ -84,9 +84,10 @@ def csalsa(y, A, mu1, mu2, sigma, *varargin, ctx=None, **kw):
     if ("P" in opts) != ("PT" in opts):
         raise ValueError("If you give P you must also give PT, and vice versa.")               # :265
     if "P" in opts:
-        raise NotImplementedError("'P'/'PT' other than the identity are not supported")
+        raise NotImplementedError("'P'/'PT' other than the identity are not supported (the wavelet frame, P = mirdwt_TI2D: use "
+                                  "sbtv.csalsa_wavelet)")
     if not opts.get("TVINITIALIZATION", 0):
-        raise NotImplementedError("only the TV path ('TVINITIALIZATION', 1) runs on the GPU")
+        raise NotImplementedError("only the TV path ('TVINITIALIZATION', 1) runs on the GPU (wavelet-l1: use sbtv.csalsa_wavelet)")
     if "PSI" in opts:
         print("Warning: user specified Phi and Psi will not be used as TV with initialization flag has been set to 1.",
               file=sys.stdout)                                                                 # :333

@@ -2,7 +2,8 @@
 `mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
 with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
 `SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), `SALSA_analysis` (its analysis-prior form, 'P' = W and
-'PT' = W', on the image), and `SAPG_wavelet`, the empirical-Bayes estimate of the regularisation parameter that the script runs
+'PT' = W', on the image), `csalsa_wavelet` (the constrained form of that, csalsa with the same 'P' / 'PT', for a known noise
+level), and `SAPG_wavelet`, the empirical-Bayes estimate of the regularisation parameter that the script runs
 first (the theta part of SALSA/SAPG_algorithm_1.m), and `myula_wavelet`, the MYULA chain at a fixed theta with the posterior
 mean / variance of its samples.  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
 [a_J | LH1 HL1 HH1 | LH2 ...], or (B, M, (3J+1) N) for a batch; host and device arrays as everywhere in this package."""
@@ -292,6 +293,59 @@ def CoRAL_wavelet(y, A, tau1, tau2, *varargin, ctx=None, **kw):
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
     return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
                          mses if ti else None)
+
+
+_CSALSA_WAVELET_OPTIONS = {"WAVELET", "LEVELS", "AT", "STOPCRITERION", "TOLERANCEA", "MAXITERA", "INITIALIZATION", "TRUE_X",
+                           "CONTINUATIONFACTOR", "EPSILON", "SPECULATE", "VERBOSE"}
+
+
+def csalsa_wavelet(y, A, mu1, mu2, sigma, *varargin, ctx=None, **kw):
+    """[x, numA, numAt, objective, distance1, distance2, criterion, times, mses] = csalsa_wavelet(y, A, mu1, mu2, sigma,
+    'WAVELET', h, 'LEVELS', L, 'AT', A.T, ...)
+
+    minimise ||W' x||_1 subject to ||A x - y||_2 <= epsilon over the IMAGE x: C-SALSA (SALSA/CSALSA_v2.m:160-561) with the wavelet
+    analysis prior, i.e. `csalsa` with 'P' = W = `mirdwt_TI2D`, 'PT' = W' = `mrdwt_TI2D`, 'PSI' = soft and 'LS' = A.invLS; the
+    iteration is stated in include/sbtv.h (sbtv_CSALSA_wavelet).  For the user who knows the noise level sigma (from the sensor, or
+    the sigma2 of SAPG_wavelet_semiblind) and not a regularisation parameter: 'EPSILON' defaults to sqrt(n + 8 sqrt n) sigma.
+    A.invLS(r, mu1) is the exact x-minimiser only for mu2 = 1; other mu2 run as the reference would run them.
+    Options: 'WAVELET' (an orthonormal scaling filter, default daubcqf(2)), 'LEVELS' (4), 'AT', 'STOPCRITERION' (3), 'TOLERANCEA',
+    'MAXITERA', 'INITIALIZATION' (0 zeros, 2 = A' y, or a start image), 'TRUE_X' (the true image), 'CONTINUATIONFACTOR' (1),
+    'EPSILON' (0: the default), 'SPECULATE' (sbtv_salsa_opts.speculate bit 0; the result is the same), 'VERBOSE'.
+    objective is ||W' x||_1, the objective of the problem (the reference records phi of the image).  Traces are 1-based in the
+    reference; the returned arrays hold entries 1..outer in positions 0..outer-1, as `csalsa` returns them."""
+    opts = _parse_varargin(varargin, _CSALSA_WAVELET_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("csalsa_wavelet has no sharded variant")
+    init = opts.get("INITIALIZATION", 0)
+    if not (np.ndim(init) > 0 or L._is_torch(init)) and int(init) not in (0, 2):
+        raise L.SbtvError(-7, "Unknown 'Initialization' option")          # the random start of CSALSA_v2 is not offered
+    so, yi, xinit, ti = _common(y, A, opts, ctx, 3)                       # default :171
+    ha, hp, K = _filter(opts.get("WAVELET", daubcqf(2)))
+    levels = int(opts.get("LEVELS", 4))
+    B, M, N = yi.B, yi.M, yi.N
+    for other in (xinit, ti):
+        if other is not None and (other.B, other.M, other.N) != (B, M, N):
+            raise ValueError("'TRUE_X' and an array 'INITIALIZATION' must be images of the size of y")
+    Kmax = max(so.maxiter, 1)
+    xo = L.empty_like_images(yi)
+    objective, distance1, distance2, criterion, times, mses = _traces(B, *([Kmax] * 6))
+    numA, numAt, nout = _counters(B, 3)
+    taps = A._cm(B)
+    keep = [L.dvec(v, B) for v in (mu1, mu2, sigma, opts.get("EPSILON", 0.0))]
+    m1, m2, sg, ep = (k[1] for k in keep)
+    ctx.check(ctx.lib.sbtv_CSALSA_wavelet(ctx.h, yi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, m1, m2, sg, ep,
+                                          float(opts.get("CONTINUATIONFACTOR", 1.0)), C.byref(so), ti.ptr if ti else None,
+                                          xinit.ptr if xinit else None, xo.ptr, _vp(objective), _vp(distance1), _vp(distance2),
+                                          _vp(criterion), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
+              yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    single = sq or B == 1
+    counts = (int(numA[0]), int(numAt[0])) if single else (np.array(numA[:]), np.array(numAt[:]))
+    return (L.images_result(xo, sq),) + counts + _trimmed(np.array(nout[:]), single, (objective, 0), (distance1, 0),
+                                                          (distance2, 0), (criterion, 0), (times, 0), (mses if ti else None, 0))
 
 
 def _op(op, name, default=None):
