@@ -1155,6 +1155,16 @@ int sbtv_SALSA_masked_sharded(sbtv_group *g, const double *y, const double *mask
  *   values of l per thread of the tap-spectrum launch (`lch`), 1 = a shared-spectrum batch of this size folds into
  *   grid.x, bits: 1 = forward TV partials, 2 = the step / sub / skip_x column epilogues, 4 = OP_CSALSA available} -
  *   lets a test derive its sizes and assert which kernels it ran from the library instead of copied constants.
+ * sbtv_diag_wavelet_geometry: the tile geometry of ONE level (1 .. levels - 1) of the wavelet frame kernels for an M x N
+ *   image, a scaling filter of length hlen and `levels`, from the host functions and constants the launches of
+ *   sbtv_mrdwt_TI2D / sbtv_mirdwt_TI2D themselves use; nothing is launched.  out = {J = levels - 1, stride s = 2^(level-1),
+ *   run Q1 along dimension 1, Q2 along dimension 2, runs per stride s / Q1, s / Q2, outputs of a tile along dimension 1,
+ *   along dimension 2 for analysis, along dimension 2 for synthesis, tiles along dimension 1, along dimension 2 for
+ *   analysis, along dimension 2 for synthesis, halo samples (hlen - 1) Q1, (hlen - 1) Q2, static LDS bytes of the analysis
+ *   kernel of this filter length, of the synthesis kernel}.  Refuses what the transforms refuse, with their codes
+ *   (SBTV_ERR_BADARG: hlen not 2, 4, 6, 8 or levels < 2; SBTV_ERR_SIZE: (hlen - 1) 2^(levels - 2) >= min(M, N)), and a level
+ *   outside 1 .. levels - 1 with SBTV_ERR_BADARG - lets a test derive the image sizes that sit on a tile seam, on a run cap
+ *   or on a wrap of the halo from the library instead of copying constants.
  * sbtv_diag_spectral_pass: ONE forward-column, row, inverse-column triple of the solver loops on caller data (host
  *   pointers, column-major images), everything observable handed back; see sbtv_diag_pass.  Every refused argument is
  *   refused before the first launch, with the error the pass itself would give.
@@ -1191,6 +1201,7 @@ int sbtv_diag_time_pass(sbtv_ctx *ctx, int pass, int M, int N, int batch, int re
 int sbtv_diag_prox_variant(sbtv_ctx *ctx, int M, int N, int batch, int out[6]);
 int sbtv_diag_prox_geometry(sbtv_ctx *ctx, int M, int N, int batch, int out[16]);
 int sbtv_diag_fft_plan(sbtv_ctx *ctx, int M, int N, int batch, int out[16]);
+int sbtv_diag_wavelet_geometry(sbtv_ctx *ctx, int M, int N, int hlen, int levels, int level, int out[16]);
 /* op: the spectral operator of the row pass, 0 none, 1 X H, 2 X conj(H), 3 X / (|H|^2 + mu), 4 SALSA solve, 5 residual
  * sum only, 6 gradient with both PSF-parameter sums, 7 X |H|^2, 8 gradient, 9 C-SALSA solve with its state spectrum.
  * epilogue of the inverse column pass: 0 plain, 1 SALSA bookkeeping (bu in / out, g_out, sums; tru, xprev optional),

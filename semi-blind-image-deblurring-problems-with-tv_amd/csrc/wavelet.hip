@@ -244,6 +244,15 @@ inline unsigned wav_tiles(int n, int ls, int lq, int nr, int T) {
     return (unsigned)(((steps + A - 1) / A) * nr);
 }
 
+// the grids of the two launches of a level (sbtv_diag_wavelet_geometry reports them from here)
+inline dim3 wav_grid_analysis(const WavPlan &pl, const WavGeom &g, int batch) {
+    return dim3(wav_tiles(pl.M, g.ls, g.lq1, g.nr1, WT1), wav_tiles(pl.N, g.ls, g.lq2, g.nr2, WA_T2), (unsigned)batch);
+}
+
+inline dim3 wav_grid_synthesis(const WavPlan &pl, const WavGeom &g, int batch) {
+    return dim3(wav_tiles(pl.M, g.ls, g.lq1, g.nr1, WT1), wav_tiles(pl.N, g.ls, g.lq2, g.nr2, WS_T2), (unsigned)batch);
+}
+
 template <int K>
 int wav_level_analysis(sbtv_ctx *ctx, const WavPlan &pl, int level, const double *in, size_t in_img, double *ll,
                        size_t ll_img, double *det, int batch) {
@@ -256,7 +265,7 @@ int wav_level_analysis(sbtv_ctx *ctx, const WavPlan &pl, int level, const double
         tp.f0[k] = pl.f0[k];
         tp.f1[k] = pl.f1[k];
     }
-    const dim3 grid(wav_tiles(pl.M, g.ls, g.lq1, g.nr1, WT1), wav_tiles(pl.N, g.ls, g.lq2, g.nr2, WA_T2), (unsigned)batch);
+    const dim3 grid = wav_grid_analysis(pl, g, batch);
     hipLaunchKernelGGL(wav_analysis_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, in, ll, det, det + P, det + 2 * P, ll_img,
                        tp, g);
     return 0;
@@ -274,7 +283,7 @@ int wav_level_synthesis(sbtv_ctx *ctx, const WavPlan &pl, int level, const doubl
         tp.f0[k] = pl.f0[k];
         tp.f1[k] = pl.f1[k];
     }
-    const dim3 grid(wav_tiles(pl.M, g.ls, g.lq1, g.nr1, WT1), wav_tiles(pl.N, g.ls, g.lq2, g.nr2, WS_T2), (unsigned)batch);
+    const dim3 grid = wav_grid_synthesis(pl, g, batch);
     if (mom)
         hipLaunchKernelGGL(wav_synthesis_moments_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, ll, det, det + P, det + 2 * P,
                            ll_img, out, tp, g, *mom);
@@ -282,6 +291,43 @@ int wav_level_synthesis(sbtv_ctx *ctx, const WavPlan &pl, int level, const doubl
         hipLaunchKernelGGL(wav_synthesis_kernel<K>, grid, dim3(WNW * 64), 0, ctx->stream, ll, det, det + P, det + 2 * P, ll_img,
                            out, tp, g);
     return 0;
+}
+
+template <int K>
+int wav_lds_bytes(sbtv_ctx *ctx, int *analysis, int *synthesis) {
+    hipFuncAttributes fa;
+    SBTV_HIP(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(wav_analysis_kernel<K>)));
+    *analysis = (int)fa.sharedSizeBytes;
+    SBTV_HIP(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(wav_synthesis_kernel<K>)));
+    *synthesis = (int)fa.sharedSizeBytes;
+    return 0;
+}
+
+// what sbtv_diag_wavelet_geometry reports: wav_geom / wav_tiles and the tile constants exactly as the two launches above use
+// them, and the static LDS of the two kernels as the loaded code object states it
+int wav_report(sbtv_ctx *ctx, const WavPlan &pl, int level, int out[16]) {
+    const WavGeom g = wav_geom(pl, level);
+    out[0] = pl.J;
+    out[1] = 1 << g.ls;
+    out[2] = 1 << g.lq1;
+    out[3] = 1 << g.lq2;
+    out[4] = g.nr1;
+    out[5] = g.nr2;
+    out[6] = WT1;
+    out[7] = WA_T2;
+    out[8] = WS_T2;
+    const dim3 ga = wav_grid_analysis(pl, g, 1), gs = wav_grid_synthesis(pl, g, 1);
+    out[9] = (int)ga.x;
+    out[10] = (int)ga.y;
+    out[11] = (int)gs.y;
+    out[12] = (pl.K - 1) << g.lq1;
+    out[13] = (pl.K - 1) << g.lq2;
+    switch (pl.K) {
+        case 2: return wav_lds_bytes<2>(ctx, &out[14], &out[15]);
+        case 4: return wav_lds_bytes<4>(ctx, &out[14], &out[15]);
+        case 6: return wav_lds_bytes<6>(ctx, &out[14], &out[15]);
+        default: return wav_lds_bytes<8>(ctx, &out[14], &out[15]);
+    }
 }
 
 }  // namespace
@@ -442,6 +488,16 @@ int sbtv_soft(sbtv_ctx *ctx, const double *x, int M, int N, int batch, const dou
     SBTV_TRY(stage_out_copy(ctx, out, od, n, flags));
     SBTV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return canary_epilogue(ctx, 0);
+}
+
+int sbtv_diag_wavelet_geometry(sbtv_ctx *ctx, int M, int N, int hlen, int levels, int level, int out[16]) {
+    if (!ctx || !out) return SBTV_ERR_BADARG;
+    static const double h[8] = {0.0};                                     // wav_plan reads it after its checks only
+    WavPlan pl;
+    SBTV_TRY(wav_plan(ctx, M, N, h, hlen, levels, false, &pl));
+    if (level < 1 || level > pl.J) return fail(ctx, SBTV_ERR_BADARG, "diag_wavelet_geometry: the level must lie in 1..levels - 1");
+    SBTV_HIP(ctx, hipSetDevice(ctx->device));
+    return wav_report(ctx, pl, level, out);
 }
 
 }  // extern "C"

@@ -223,6 +223,7 @@ SIGNATURES = {
     "sbtv_diag_prox_variant": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
     "sbtv_diag_prox_geometry": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
     "sbtv_diag_fft_plan": (_I, [_P, _I, _I, _I, C.POINTER(_I)]),
+    "sbtv_diag_wavelet_geometry": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sbtv_diag_spectral_pass": (_I, [_P, C.POINTER(sbtv_diag_pass)]),
     "sbtv_last_host_stats": (_I, [_P, C.POINTER(_D)]),
     "sbtv_diag_workspace": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t)]),
@@ -378,6 +379,18 @@ class Context:
         p["rows_kind"] = {0: "workgroup", 1: "pipelined", 2: "pointwise"}[p["rows_kind"]]
         p.update(tv_ok=bool(caps & 1), step_ok=bool(caps & 2), csalsa_ok=bool(caps & 4))
         return p
+
+    WAVELET_GEOMETRY = ("J", "s", "Q1", "Q2", "nr1", "nr2", "T1", "TA2", "TS2", "tiles1", "tilesA2", "tilesS2", "halo1",
+                        "halo2", "lds_analysis", "lds_synthesis")
+
+    def wavelet_geometry(self, M, N, hlen, levels, level):
+        """Tile geometry of level `level` (1 .. levels - 1) of the wavelet frame kernels for an M x N image and a filter of
+        length hlen (sbtv_diag_wavelet_geometry): J, stride s, runs Q1 / Q2 and runs per stride nr1 / nr2, tile outputs
+        along dimension 1 (T1) and along dimension 2 for analysis / synthesis (TA2 / TS2), the tile counts, the halo
+        samples and the static LDS bytes of the two kernels."""
+        out = (_I * 16)()
+        self.check(self.lib.sbtv_diag_wavelet_geometry(self.h, int(M), int(N), int(hlen), int(levels), int(level), out))
+        return dict(zip(self.WAVELET_GEOMETRY, out))
 
     SPEC_OPS = {"none": 0, "mul_h": 1, "mul_hc": 2, "invls": 3, "salsa": 4, "resid": 5, "grad": 6, "ata": 7, "gradf": 8,
                 "csalsa": 9}

@@ -24,7 +24,9 @@ TRANSFORM_CASES = [
     ((256, 192), 2, 5, 1),
     ((512, 512), 2, 4, 1),        # full launch geometry
     # strides beyond the run caps of csrc/wavelet.hip (16 / 8 / 4 rows, 4 / 2 columns by filter length): the tiles of the
-    # deepest levels are combs of runs along both dimensions, and no size is a multiple of the stride
+    # deepest levels are combs of runs along both dimensions.  96 = 3 * 32 and 160 = 5 * 32 = 10 * 16 ARE multiples of the
+    # deepest strides of the first two (every run has the same number of steps); only 150 and 131 leave the last step of a
+    # comb partial, for filter lengths 6 and 8.  tests/test_gpu_wavelet_sweep.py has that class for every length.
     ((96, 160), 2, 7, 1),         # s = 32 > 16
     ((160, 96), 4, 6, 2),         # s = 16 > 8, reach 48, a batch
     ((150, 131), 8, 5, 1),        # s = 8 > 4, reach 56, odd sizes

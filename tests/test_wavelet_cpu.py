@@ -92,7 +92,8 @@ def test_wavelet_entry_points_declared_exported_and_bound():
     from sbtv import _lib
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sbtv.h")).read(), flags=re.S)
     lib = sbtv.load_library()
-    for name, nargs in (("sbtv_mrdwt_TI2D", 10), ("sbtv_mirdwt_TI2D", 10), ("sbtv_soft", 8), ("sbtv_SALSA_wavelet", 25)):
+    for name, nargs in (("sbtv_mrdwt_TI2D", 10), ("sbtv_mirdwt_TI2D", 10), ("sbtv_soft", 8), ("sbtv_SALSA_wavelet", 25),
+                        ("sbtv_diag_wavelet_geometry", 7)):
         m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", text, flags=re.S)
         assert m, f"{name} is not declared in include/sbtv.h"
         assert len(m.group(1).split(",")) == nargs
