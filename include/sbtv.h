@@ -364,6 +364,45 @@ int sbtv_SALSA_analysis(sbtv_ctx *ctx, const double *y, int M, int N, int batch,
                         const double *true_x, const double *x_init, double *x_out,
                         double *objective, double *distance, double *times, double *mses,
                         int *numA, int *numAt, int *n_outer, int flags);
+/* min over the IMAGE x  0.5 * sum( m .* (B x - y).^2 ) + tau ||W' x||_1: the masked-observation likelihood of sbtv_SALSA_masked
+ * (unknown boundaries, missing or weighted pixels) with the analysis prior of sbtv_SALSA_analysis.  No entry of the reference:
+ * the mask-decoupling ADMM of Almeida & Figueiredo (IEEE TIP 2013), which states it for frame-analysis priors as for TV.
+ * B: the circular blur of `taps`; m = mask: non-negative weights like y (0 = not observed), exactly as for sbtv_SALSA_masked (y
+ * enters only as m .* y, its values under m = 0 must be finite); W' = mrdwt_TI2D, W = mirdwt_TI2D with an orthonormal h
+ * (W W' = I).  The splits are u = W'x (coefficients) and v = B x (pixels), the scaled multipliers bu, bv follow SALSA_v2's
+ * sign convention (SALSA/SALSA_v2.m:429-440):
+ *     start:  x by opts->initialization (0 zeros, 2 B'(m .* y), 33333 x_init)
+ *             Bx = B x ;  PTx = W'x ;  u = PTx ;  bu = 0 ;  v = Bx ;  bv = 0
+ *             objective(1) = 0.5 sum(m .* (Bx - y).^2) + tau ||u||_1 ;  mses(1) = ||x - true_x||^2 / (M N)
+ *     outer:  u   = soft(PTx - bu, tau/mu1)
+ *             v   = (m .* y + mu2 * (Bx - bv)) ./ (m + mu2)
+ *             X   = (mu1 * fft2(W(u + bu)) + mu2 * conj(H) .* fft2(v + bv)) ./ (mu1 + mu2 * abs(H).^2)
+ *             x   = real(ifft2(X)) ;  Bx = real(ifft2(H .* X)) ;  PTx = W'x
+ *             bu  = bu + (u - PTx) ;  bv = bv + (v - Bx)
+ *             objective(outer+1) = 0.5 sum(m .* (Bx - y).^2) + tau ||u||_1 ;  mses(outer+1) = ||x - true_x||^2 / (M N)
+ *             distance(outer, :) = ||PTx - u|| / sqrt(||PTx||^2 + ||u||^2),  ||Bx - v|| / sqrt(||Bx||^2 + ||v||^2)
+ *             stop rules 1, 2, 3 of SALSA_v2.m:453-482 from outer = 2 on; rule 2 is ||x - xprev|| / ||x|| on the image
+ * What runs keeps the coefficient state (s, bu), s = u + bu, as sbtv_SALSA_analysis does (u = s - bu is recovered by the one
+ * pass over the coefficients), and the pixel state x, Bx, v, bv: z = W s, X = (conj(H) .* fft2(v + bv) + r * fft2(z)) ./
+ * (abs(H).^2 + r) with r = mu1/mu2, then one pass over the pixels forms bv + (v - Bx), the next v and the sums of the traces.
+ * true_x / x_init / x_out: [batch][M*N] images; x_out is required.  objective / times / mses: [batch*(maxiter+1)]; distance:
+ * [batch*maxiter*2], entry (outer-1)*2 + {0,1}.  numA = 1 (the start's B x) + one per outer iteration (H .* X), numAt = one per
+ * outer iteration (conj(H) .* fft2(v + bv)) + 1 when initialization = 2; P and PT are not counted.
+ * mu2 decides the speed, not the answer.  opts->TViters and the Chambolle knobs are ignored; opts->speculate bit 0 as for
+ * sbtv_SALSA_analysis (x, s and bu are double-buffered: the result is that of the stopping iteration).  Images of a batch are
+ * solved one after another, image k bit for bit as alone.  SBTV_DEVICE_PTRS applies to y / mask / true_x / x_init / x_out.
+ * Errors before any GPU work, with the codes of the two parents: mask, tau, mu1, mu2, x_out or h NULL, mu1[b] <= 0, mu2[b] <= 0,
+ * h not orthonormal, levels < 2 -> SBTV_ERR_BADARG; odd pixel count or tap reach >= min(M, N) -> SBTV_ERR_SIZE; stop
+ * criterion, initialization, maxiter and PSF fit as sbtv_SALSA_analysis.  With SBTV_HOST_PTRS a mask with a negative or
+ * non-finite entry is rejected (SBTV_ERR_BADARG); a device-resident mask (it lives where y lives) is the caller's
+ * responsibility, as for sbtv_SALSA_masked. */
+int sbtv_SALSA_masked_analysis(sbtv_ctx *ctx, const double *y, const double *mask, int M, int N, int batch,
+                               const double *taps, int taille,
+                               const double *h, int hlen, int levels,
+                               const double *tau, const double *mu1, const double *mu2, const sbtv_salsa_opts *opts,
+                               const double *true_x, const double *x_init, double *x_out,
+                               double *objective, double *distance, double *times, double *mses,
+                               int *numA, int *numAt, int *n_outer, int flags);
 /* min over the IMAGE x  0.5 ||y - B x||^2 + tau1 TV(x) + tau2 ||W' x||_1: CoRAL (SALSA/CoRAL_v2.m:2-476) with the compound
  * regulariser it exists for, TV on the image plus l1 on the coefficients of the redundant wavelet frame.  In the reference's
  * terms P1 = P1' = identity with TVINITIALIZATION1 = 1, P2 = W = mirdwt_TI2D, P2' = W' = mrdwt_TI2D, Psi2 = soft, Phi2 = l1,

@@ -179,14 +179,7 @@ __global__ __launch_bounds__(AB) void coral_post_kernel(const double *__restrict
 }
 
 // ---- masked-observation SALSA (masked_one) ------------------------------------------------------
-// w = m .* y: the right-hand side of the start x = B'(m .* y) ('INITIALIZATION' 2)
-__global__ __launch_bounds__(AB) void masked_my_kernel(const double *__restrict__ m, const double *__restrict__ y,
-                                                        double *__restrict__ w, size_t P) {
-    AD_LOOP(q, P) {
-        const double2 mv = AD_LD(m, q), yv = AD_LD(y, q);
-        AD_ST(w, q, make_double2(mv.x * yv.x, mv.y * yv.y));
-    }
-}
+#include "masked_my.inc"  // masked_my_kernel: w = m .* y, shared with masked_wavelet.hip
 
 // The one element-wise pass of an outer iteration, after the two inverse transforms (x, Bx) and with this iteration's u and v:
 //   bu += u - x ; bv += v - Bx ; g = x - bu (the next prox input) ; v <- (m .* y + mu2 (Bx - bv)) ./ (m + mu2) (the next v)

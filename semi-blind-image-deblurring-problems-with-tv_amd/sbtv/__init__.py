@@ -11,7 +11,7 @@ from .operators import (BlurOperator, A_wrapper, Gaussian_psf, psf_gaussian, psf
                         rfft2_packed, unpack_half_spectrum, conv2c, diffh, diffv)
 from .salsa import SALSA_v2
 from .admm import csalsa, CSALSA_v2, CoRAL, CoRAL_v2, SALSA_masked, valid_mask, embed_observation
-from .wavelet import mrdwt_TI2D, mirdwt_TI2D, soft, daubcqf, SALSA_wavelet, SALSA_analysis, CoRAL_wavelet, csalsa_wavelet, SAPG_wavelet, myula_wavelet, SAPG_wavelet_semiblind, skrock_wavelet, skrock_coefficients, skrock_max_step
+from .wavelet import mrdwt_TI2D, mirdwt_TI2D, soft, daubcqf, SALSA_wavelet, SALSA_analysis, SALSA_masked_analysis, CoRAL_wavelet, csalsa_wavelet, SAPG_wavelet, myula_wavelet, SAPG_wavelet_semiblind, skrock_wavelet, skrock_coefficients, skrock_max_step
 from .diagnostics import ssim, save_results, load_results, plot_traces, save_image
 from .metrics import PSNR, MSE
 from .fista import my_fista, my_deblur_fista, my_fista_l1, Psi_TV
@@ -27,5 +27,5 @@ __all__ = [
     "chambolle_prox_TV_stop", "TVnorm", "BlurOperator", "A_wrapper", "Gaussian_psf", "psf_gaussian",
     "psf_moffat", "psf_laplace", "psf_family", "rfft2_packed", "unpack_half_spectrum", "SALSA_v2", "PSNR", "MSE",
     "csalsa", "CSALSA_v2", "CoRAL", "CoRAL_v2", "SALSA_masked", "valid_mask", "embed_observation",
-    "mrdwt_TI2D", "mirdwt_TI2D", "soft", "daubcqf", "SALSA_wavelet", "SALSA_analysis", "CoRAL_wavelet", "csalsa_wavelet", "SAPG_wavelet", "myula_wavelet", "SAPG_wavelet_semiblind", "skrock_wavelet", "skrock_coefficients", "skrock_max_step", "ssim", "save_results", "load_results", "plot_traces", "save_image", "conv2c", "diffh", "diffv",
+    "mrdwt_TI2D", "mirdwt_TI2D", "soft", "daubcqf", "SALSA_wavelet", "SALSA_analysis", "SALSA_masked_analysis", "CoRAL_wavelet", "csalsa_wavelet", "SAPG_wavelet", "myula_wavelet", "SAPG_wavelet_semiblind", "skrock_wavelet", "skrock_coefficients", "skrock_max_step", "ssim", "save_results", "load_results", "plot_traces", "save_image", "conv2c", "diffh", "diffv",
 ]

@@ -163,6 +163,8 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_SALSA_analysis": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
                                  _P, _P, _P, _P, _P, _P, _P, _I]),
+    "sbtv_SALSA_masked_analysis": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P,
+                                        _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_CoRAL_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, C.POINTER(sbtv_salsa_opts), _P, _P, _P,
                                 _P, _P, _P, _P, _P, _P, _P, _I]),
     "sbtv_CSALSA_wavelet": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, C.POINTER(sbtv_salsa_opts), _P, _P, _P,

@@ -2,7 +2,8 @@
 `mrdwt_TI2D` / `mirdwt_TI2D` (SALSA/mrdwt_TI2D.m, mirdwt_TI2D.m; the Rice Wavelet Toolbox MEX behind them is not shipped
 with the reference, the transform is defined in include/sbtv.h), `soft` (SALSA/soft.m), `daubcqf` and the solver
 `SALSA_wavelet` (SALSA_v2 with 'Psi' = soft and the 'LS' of the demo), `SALSA_analysis` (its analysis-prior form, 'P' = W and
-'PT' = W', on the image), `csalsa_wavelet` (the constrained form of that, csalsa with the same 'P' / 'PT', for a known noise
+'PT' = W', on the image), `SALSA_masked_analysis` (the same prior on the masked-observation likelihood of SALSA_masked),
+`csalsa_wavelet` (the constrained form of that, csalsa with the same 'P' / 'PT', for a known noise
 level), and `SAPG_wavelet`, the empirical-Bayes estimate of the regularisation parameter that the script runs
 first (the theta part of SALSA/SAPG_algorithm_1.m), and `myula_wavelet`, the MYULA chain at a fixed theta with the posterior
 mean / variance of its samples.  Coefficients are (M, (3J+1) N) arrays, J = levels - 1:
@@ -233,6 +234,68 @@ def SALSA_analysis(y, A, tau, *varargin, ctx=None, **kw):
                                           ti.ptr if ti else None, xinit.ptr if xinit else None, xo.ptr, _vp(objective),
                                           _vp(distance), _vp(times), _vp(mses) if ti else None, numA, numAt, nout, yi.flags),
               yi.flags)
+    sq = (y.dim() == 2) if yi.torch else yi.squeeze
+    return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
+                         mses if ti else None)
+
+
+_MASKED_ANALYSIS_OPTIONS = {"MU1", "MU2", "WAVELET", "LEVELS", "AT", "STOPCRITERION", "TOLERANCEA", "MAXITERA", "TRUE_X",
+                            "INITIALIZATION", "VERBOSE", "SPECULATE"}
+
+
+def SALSA_masked_analysis(y, A, mask, tau, *varargin, ctx=None, **kw):
+    """[x, numA, numAt, objective, distance, times, mses] = SALSA_masked_analysis(y, A, mask, tau, 'MU1', mu1, 'MU2', mu2,
+    'WAVELET', h, 'LEVELS', L, 'AT', A.T, ...)
+
+    minimise 0.5 * sum(mask .* (A x - y).^2) + tau ||W' x||_1 over the IMAGE x: the likelihood of `SALSA_masked` (`mask` holds
+    non-negative weights of the shape of y, 0 = pixel not observed: unknown boundaries, missing or weighted pixels) with the
+    analysis prior of `SALSA_analysis` (W' = `mrdwt_TI2D`); the iteration is stated in include/sbtv.h
+    (sbtv_SALSA_masked_analysis).  Options: 'MU1' (required, the weight of the coefficient split, SALSA_analysis's 'MU'), 'MU2'
+    (the weight of the data split, default 0.1, the value of SALSA_masked: it decides the speed, not the answer; the default
+    rests on NumPy prototype runs of this iteration at 64 x 64 and 128 x 128 with mu2 = 1 and 0.1 and on the one problem
+    SALSA_masked's default was measured on, all with pixel values in 0..255), 'WAVELET' (an orthonormal scaling filter, default
+    daubcqf(2)), 'LEVELS' (4), 'AT', 'STOPCRITERION', 'TOLERANCEA', 'MAXITERA', 'TRUE_X' (the true image), 'INITIALIZATION'
+    (0 zeros, 2 = AT(mask .* y), or a start image), 'VERBOSE', 'SPECULATE' (sbtv_salsa_opts.speculate bit 0; the result is the
+    same).  The return values are shaped as `SALSA_masked` returns them: distance is (outer, 2), column 0 the coefficient split
+    ||W'x - u||, column 1 the data split ||Ax - v||, both relative.  For an observation without wrapped pixels see
+    `embed_observation`."""
+    opts = _parse_varargin(varargin, _MASKED_ANALYSIS_OPTIONS)
+    for k, v in kw.items():
+        opts[k.upper()] = v
+    ctx = ctx or L.default_context()
+    if getattr(ctx, "is_group", False):
+        raise NotImplementedError("SALSA_masked_analysis has no sharded variant")
+    init = opts.get("INITIALIZATION", 0)
+    if not (np.ndim(init) > 0 or L._is_torch(init)) and int(init) not in (0, 2):
+        raise L.SbtvError(-7, "Unknown 'Initialization' option")          # no random start
+    so, yi, xinit, ti = _common(y, A, opts, ctx, 1)
+    if mask is None:
+        raise L.SbtvError(-1, "SALSA_masked_analysis: the mask is missing")
+    mi = L.Images(mask)
+    B, M, N = yi.B, yi.M, yi.N
+    if (mi.B, mi.M, mi.N) != (B, M, N):
+        raise ValueError("the mask must have the shape of y")
+    if mi.flags != yi.flags:
+        raise ValueError("all image arguments must live in the same memory space")
+    if "MU1" not in opts:
+        raise L.SbtvError(-1, "SALSA_masked_analysis: 'MU1' is required")
+    ha, hp, K = _filter(opts.get("WAVELET", daubcqf(2)))
+    levels = int(opts.get("LEVELS", 4))
+    for other in (xinit, ti):
+        if other is not None and (other.B, other.M, other.N) != (B, M, N):
+            raise ValueError("'TRUE_X' and an array 'INITIALIZATION' must be images of the size of y")
+    Kmax = so.maxiter
+    xo = L.empty_like_images(yi)
+    objective, times, mses = _traces(B, Kmax + 1, Kmax + 1, Kmax + 1)
+    distance = np.zeros((B, Kmax, 2))
+    numA, numAt, nout = _counters(B, 3)
+    taps = A._cm(B)
+    keep = [L.dvec(v, B) for v in (tau, opts["MU1"], opts.get("MU2", 0.1))]
+    tv, m1, m2 = (k[1] for k in keep)
+    ctx.check(ctx.lib.sbtv_SALSA_masked_analysis(ctx.h, yi.ptr, mi.ptr, M, N, B, _vp(taps), A.taille, hp, K, levels, tv, m1, m2,
+                                                 C.byref(so), ti.ptr if ti else None, xinit.ptr if xinit else None, xo.ptr,
+                                                 _vp(objective), _vp(distance), _vp(times), _vp(mses) if ti else None, numA,
+                                                 numAt, nout, yi.flags), yi.flags)
     sq = (y.dim() == 2) if yi.torch else yi.squeeze
     return _salsa_result((L.images_result(xo, sq),), sq or B == 1, numA, numAt, nout, objective, distance, times,
                          mses if ti else None)
