@@ -82,11 +82,17 @@ def _setup(kind, x, noise, evMax, taille):
                 d_exp=0.8, d_scale=0.01 / th_init, min_th=1e-3, max_th=1.0)
 
 
-@functools.lru_cache(maxsize=None)
 def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
-    """dict(setup, model, kind, mask, noise (steps, M, N), kw: what the restatement takes beyond setup / mask / noise,
-    op, c: what sbtv.SAPG_masked takes)."""
-    q = CASES[name]
+    return build(tuple(sorted(CASES[name].items())), samples, warmup, burnIn)
+
+
+@functools.lru_cache(maxsize=None)
+def build(case, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
+    """The problem of an explicit case, given as its sorted items (tests/tv_sampler_geometry_cases.py has further ones; a case
+    may name its own chambolleit): dict(setup, model, kind, mask, noise (steps, M, N), kw: what the restatement takes beyond
+    setup / mask / noise, op, c: what sbtv.SAPG_masked takes)."""
+    q = dict(case)
+    cit = q.get("chambolleit", CHAMBOLLEIT)
     kind, M, N = q["kind"], q["M"], q["N"]
     d = o.DEMO[kind]
     rng = np.random.default_rng(q["seed"])
@@ -98,8 +104,8 @@ def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
     mask = q["mask"]((M, N))
     fix = tuple(q.get("fix", d["fix"]))
     cr = dict(theta=SCALE * d["c_theta"], p=tuple(SCALE * v for v in d["c_p"]), sigma=SCALE * d["c_sigma"])
-    kw = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=CHAMBOLLEIT, model=model, fix=fix, c=cr)
-    op = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=CHAMBOLLEIT, psf_size=taille, phi=0.0,
+    kw = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=cit, model=model, fix=fix, c=cr)
+    op = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=cit, psf_size=taille, phi=0.0,
               th_init=st["th_init"], min_th=st["min_th"], max_th=st["max_th"], sigma=st["sigma"], sigma_init=st["sigma_init"],
               sigma_min=st["sigma_min"], sigma_max=st["sigma_max"], d_scale=st["d_scale"], d_exp=st["d_exp"], fix_sigma=0,
               gamma=st["gamma"])
@@ -112,11 +118,14 @@ def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
     return dict(setup=st, model=model, kind=kind, mask=mask, noise=noise, kw=kw, op=op, c=c)
 
 
-def chain(name, noise=None, mask=None, **kw):
-    """The restatement on a case (its own noise and mask unless given; kw overrides what the restatement takes)."""
-    q = problem(name)
+def chain_of(q, noise=None, mask=None, **kw):
+    """The restatement on a problem (its own noise and mask unless given; kw overrides what the restatement takes)."""
     return msr.sapg_masked_chain(q["setup"], q["mask"] if mask is None else mask, noise=q["noise"] if noise is None else noise,
                                  **dict(q["kw"], **kw))
+
+
+def chain(name, **kw):
+    return chain_of(problem(name), **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -129,23 +138,31 @@ def reference(name):
 MYULA_SAMPLES = 8
 
 
-@functools.lru_cache(maxsize=None)
 def myula_problem(name):
-    """dict(y, mask, model, p, lam, gam, theta, s2, samples, noise (samples-2, M, N))."""
-    q = problem(name)
+    return myula_build(tuple(sorted(CASES[name].items())))
+
+
+@functools.lru_cache(maxsize=None)
+def myula_build(case, samples=MYULA_SAMPLES):
+    """dict(y, mask, model, p, lam, gam, theta, s2, samples, noise (samples-2, M, N), chambolleit) of an explicit case."""
+    q = build(case)
     st = q["setup"]
     M, N = st["y"].shape
-    noise = np.random.default_rng(CASES[name]["seed"] + 1).standard_normal((MYULA_SAMPLES - 2, M, N))
+    noise = np.random.default_rng(dict(case)["seed"] + 1).standard_normal((samples - 2, M, N))
     return dict(y=st["y"], mask=q["mask"], model=q["model"], p=st["p_true"], lam=st["lam"], gam=st["gamma"], theta=st["th_init"],
-                s2=st["sigma"] ** 2, samples=MYULA_SAMPLES, noise=noise)
+                s2=st["sigma"] ** 2, samples=samples, noise=noise, chambolleit=q["kw"]["chambolleit"])
 
 
-def myula_chain(name, noise=None, **kw):
-    q = dict(myula_problem(name), **kw)
+def myula_chain_of(q, noise=None, **kw):
+    q = dict(q, **kw)
     if noise is not None:
         q["noise"] = noise
     return msr.myula_masked_chain(q["y"], q["mask"], q["model"], q["p"], q["lam"], q["gam"], q["theta"], q["s2"], q["samples"],
-                                  q["noise"], chambolleit=CHAMBOLLEIT)
+                                  q["noise"], **{k: q[k] for k in ("chambolleit", "alt_tols", "perturb") if k in q})
+
+
+def myula_chain(name, **kw):
+    return myula_chain_of(myula_problem(name), **kw)
 
 
 @functools.lru_cache(maxsize=None)

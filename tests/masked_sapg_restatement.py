@@ -50,30 +50,36 @@ def G_sigma(model, x, p, s2, y, mask):
     return residual(model, x, p, y, mask)[1] / (2 * s2 ** 2) - n_obs(mask) / (2 * s2)
 
 
-def myula_masked_chain(y, mask, model, p, lam, gam, theta, s2, samples, noise, chambolleit=25):
+def myula_masked_chain(y, mask, model, p, lam, gam, theta, s2, samples, noise, chambolleit=25, alt_tols=(), perturb=None):
     """SALSA/myula.m:1-22 on the masked likelihood: x = y as given, then ii = 2..samples-1.  noise: (samples-2, M, N).
-    Returns dict(x: the last sample, samples: X(1..samples-1), k, err [calls])."""
+    alt_tols, perturb: as sapg_masked_chain takes them.
+    Returns dict(x: the last sample, samples: X(1..samples-1), k, err [calls], k_alt [calls][len(alt_tols)])."""
     y = np.asarray(y, dtype=np.float64)
     m = np.asarray(mask, dtype=np.float64)
     x = y.copy()
-    xs, ks, errs = [x], [], []
+    xs, ks, errs, k_alt = [x], [], [], []
     nz = iter(np.asarray(noise, dtype=np.float64))
     for ii in range(2, int(samples)):
         z = next(nz)
         prox, _, _, k, err = o.chambolle_prox_TV_stop(x, lam=lam * theta, maxiter=chambolleit, tol=TOL, return_info=True)
+        k_alt.append([o.chambolle_prox_TV_stop(x, lam=lam * theta, maxiter=chambolleit, tol=t, return_info=True)[3]
+                      for t in alt_tols])
         ks.append(k)
         errs.append(err)
+        if perturb is not None:
+            prox = perturb(prox, len(ks) - 1)
         x = (1 - gam / lam) * x - gam * (gradF(model, x, p, s2, y, m) - prox / lam) + math.sqrt(2 * gam) * z
         xs.append(x)
-    return dict(x=x, samples=np.stack(xs), k=np.array(ks), err=np.array(errs))
+    return dict(x=x, samples=np.stack(xs), k=np.array(ks), err=np.array(errs), k_alt=np.array(k_alt))
 
 
 def sapg_masked_chain(setup, mask, samples, warmup, burnIn, noise, chambolleit=25, model=None, p_init=None, fix=None,
-                      fix_sigma=False, c=None, x0=None, sigma_init=None, iter_offset=0, y=None, alt_tols=()):
+                      fix_sigma=False, c=None, x0=None, sigma_init=None, iter_offset=0, y=None, alt_tols=(), perturb=None):
     """setup: the oracle's demo_setup; y: the observation unless setup's; model: its BlurModel unless given (another psf_size);
     noise: (max(warmup-1, 0) + samples-1, M, N), warm-up first; p_init, fix, fix_sigma, c = dict(theta, p, sigma), x0,
     sigma_init, iter_offset: as the oracle's SAPG_algorithm takes them.
     alt_tols: further stop tolerances at which every prox call is run again on the same input, for its k alone.
+    perturb: None, or f(prox_output, call_number) -> the prox output the chain goes on with.
     Returns dict(thetas, sigmas (S,), ps (npar, S), logpi (S,), logpi_wu (max(warmup, 1),), gx (S,), grads (npar + 2, S),
     theta_EB, p_EB, sigma_EB, samples (S, M, N): X(1..S), k, err [calls], k_alt [calls][len(alt_tols)])."""
     kind = setup["kind"]
@@ -102,7 +108,7 @@ def sapg_masked_chain(setup, mask, samples, warmup, burnIn, noise, chambolleit=2
         k_alt.append([o.chambolle_prox_TV_stop(v, lam=lamb * theta, maxiter=K, tol=t, return_info=True)[3] for t in alt_tols])
         ks.append(k)
         errs.append(err)
-        return f
+        return f if perturb is None else perturb(f, len(ks) - 1)
 
     def move(X, prox, p, s2):
         r, _ = residual(model, X, p, y, m)

@@ -32,11 +32,17 @@ CASES = {
 NAMES = list(CASES)
 
 
-@functools.lru_cache(maxsize=None)
 def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
-    """dict(setup, model, kind, stages, dt, noise (steps, M, N), kw: what the restatement takes beyond setup / noise,
-    op, c: what sbtv.SAPG_skrock takes)."""
-    q = CASES[name]
+    return build(tuple(sorted(CASES[name].items())), samples, warmup, burnIn)
+
+
+@functools.lru_cache(maxsize=None)
+def build(case, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
+    """The problem of an explicit case, given as its sorted items (tests/tv_sampler_geometry_cases.py has further ones; a case
+    may name its own chambolleit): dict(setup, model, kind, stages, dt, noise (steps, M, N), kw: what the restatement takes
+    beyond setup / noise, op, c: what sbtv.SAPG_skrock takes)."""
+    q = dict(case)
+    cit = q.get("chambolleit", CHAMBOLLEIT)
     kind, M, N, stages = q["kind"], q["M"], q["N"], q["stages"]
     d = o.DEMO[kind]
     rng = np.random.default_rng(q["seed"])
@@ -48,9 +54,9 @@ def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
     fix = tuple(q.get("fix", d["fix"]))
     dt = 0.8 * ssr.max_step(stages, ETA, min(st["sigma_min"], st["sigma_max"]), st["lam"])
     cr = dict(theta=SCALE * d["c_theta"], p=tuple(SCALE * v for v in d["c_p"]), sigma=SCALE * d["c_sigma"])
-    kw = dict(samples=samples, warmup=warmup, burnIn=burnIn, stages=stages, dt=dt, eta=ETA, chambolleit=CHAMBOLLEIT, model=model,
+    kw = dict(samples=samples, warmup=warmup, burnIn=burnIn, stages=stages, dt=dt, eta=ETA, chambolleit=cit, model=model,
               fix=fix, c=cr)
-    op = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=CHAMBOLLEIT, psf_size=taille, phi=0.0,
+    op = dict(samples=samples, warmup=warmup, burnIn=burnIn, chambolleit=cit, psf_size=taille, phi=0.0,
               th_init=st["th_init"], min_th=st["min_th"], max_th=st["max_th"], sigma=st["sigma"], sigma_init=st["sigma_init"],
               sigma_min=st["sigma_min"], sigma_max=st["sigma_max"], d_scale=st["d_scale"], d_exp=st["d_exp"], fix_sigma=0)
     op["lambda"] = st["lam"]
@@ -62,10 +68,13 @@ def problem(name, samples=SAMPLES, warmup=WARMUP, burnIn=BURNIN):
     return dict(setup=st, model=model, kind=kind, stages=stages, dt=dt, noise=noise, kw=kw, op=op, c=c)
 
 
-def chain(name, noise=None, **kw):
-    """The restatement on a case (its own noise unless given; kw overrides what the restatement takes)."""
-    q = problem(name)
+def chain_of(q, noise=None, **kw):
+    """The restatement on a problem (its own noise unless given; kw overrides what the restatement takes)."""
     return ssr.sapg_skrock_chain(q["setup"], noise=q["noise"] if noise is None else noise, **dict(q["kw"], **kw))
+
+
+def chain(name, **kw):
+    return chain_of(problem(name), **kw)
 
 
 @functools.lru_cache(maxsize=None)

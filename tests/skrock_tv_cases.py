@@ -22,23 +22,30 @@ NAMES = list(CASES)
 
 
 @functools.lru_cache(maxsize=None)
-def problem(name):
-    """dict(y, model, p (PSF parameters), sigma2, lambda, noise (steps, M, N), op, theta)."""
-    M, N, stages, steps, seed = CASES[name]
+def build(M, N, stages, steps, seed, chambolleit=CHAMBOLLEIT):
+    """The problem of an explicit case (tests/tv_sampler_geometry_cases.py has further ones):
+    dict(y, model, p (PSF parameters), sigma2, lambda, noise (steps, M, N), op, theta)."""
     rng = np.random.default_rng(seed)
     st = o.demo_setup("gaussian", synth_image(M, N, 21), rng.standard_normal((M, N)), evMax=0.99)
     s2, lam = st["sigma"] ** 2, st["lam"]
     op = {"samples": steps + 1, "stages": stages, "lambda": lam, "delta": 0.8 * skr.max_step(stages, ETA, s2, lam),
-          "eta": ETA, "chambolleit": CHAMBOLLEIT}
+          "eta": ETA, "chambolleit": chambolleit}
     return dict(y=st["y"], model=st["model"], p=st["p_true"], sigma2=s2, noise=rng.standard_normal((steps, M, N)), op=op,
                 theta=THETA, **{"lambda": lam})
 
 
-def chain(name, noise=None, theta=None, sigma2=None, **kw):
-    """The restatement on a case (its own noise, theta and sigma2 unless given)."""
-    q = problem(name)
+def problem(name):
+    return build(*CASES[name])
+
+
+def chain_of(q, noise=None, theta=None, sigma2=None, **kw):
+    """The restatement on a problem (its own noise, theta and sigma2 unless given)."""
     return skr.skrock_tv_chain(q["y"], q["model"], q["p"], q["op"], q["theta"] if theta is None else theta,
                                q["sigma2"] if sigma2 is None else sigma2, q["noise"] if noise is None else noise, **kw)
+
+
+def chain(name, **kw):
+    return chain_of(problem(name), **kw)
 
 
 @functools.lru_cache(maxsize=None)
